@@ -4,8 +4,15 @@
 One step = one MultiScaleUP_Retinex forward over one resident batch of 32
 synthetic 512x512 images per GPU.  The headline (`value`) is configs[1]
 (random-init plain model, fp32); `--precision fp16 --variant preact_aspp`
-makes configs[2] the headline instead.  A default run (no --no-nested) adds
-two nested objects to the same JSON line, each with its own roofline, parity
+makes configs[2] the headline instead.
+
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline
+needs: it builds the seeded model and inputs, warms up, times the N steps,
+writes the last step's outputs when `--dump-outputs DIR` is given, and prints
+the line (with the roofline object from the per-launch events of the last
+timed step).  Everything else is behind `--full`: the PMC traffic passes,
+parity against the CPU oracle, the CPU baselines, and (unless --no-nested)
+three nested objects on the same JSON line, each with its own roofline, parity
 and CPU baseline:
   fp16_preact_aspp  configs[2]: bs 32 512^2 fp16 preact+ASPP forward
   enhance           the enhancers main.py --mode enhance runs after the model (CLAHE-in-Lab,
@@ -26,7 +33,7 @@ and rank 0 reports the max over ranks.  `--dry-run` replaces the GPU work by a
 small CPU step over gloo and emits the same keys (tests the launcher / rank /
 report plumbing on a machine without a GPU).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (traffic, parity and cpu_baseline with --full only):
   roofline      the conv kernel family (CONV_KERNELS below, ~97% of device time), timed live with HIP events around every
                 launch of the last timed step on the model's stream
                 (upr_model_profile); traffic from rocprofv3 FETCH_SIZE/WRITE_SIZE
@@ -93,7 +100,47 @@ def parse(argv=None):
                     help=argparse.SUPPRESS)  # internal: the enhancer CPU baseline's child process
     ap.add_argument("--amp", action="store_true",
                     help="with --train: the reference's AMP branch (autocast fp16 convs + GradScaler)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the rocprofv3 PMC traffic passes, the nested "
+                         "fp16_preact_aspp / enhance / train_amp objects, parity against the CPU oracle, the CPU "
+                         "baselines and the training leg's extra profiled step (--no-traffic, --no-nested and "
+                         "--cpu-seconds 0 trim it).  Without it a run sets up, warms up, times the steps and prints "
+                         "the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps rank 0 writes what the last timed step returned as DIR/<name>.npy "
+                         "(float32; outputs over 16 MiB as a fixed seeded sample of their elements)")
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: the headline only
+        args.no_traffic = True
+        args.no_nested = True
+        args.cpu_seconds = 0.0
+    return args
+
+
+# ----------------------------------------------------------------------------
+# --dump-outputs: what the timed path returned in its last step
+# ----------------------------------------------------------------------------
+DUMP_MAX_ELEMS = 4 << 20  # per array: 16 MiB of float32 (at most three arrays per headline: 48 MiB)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(dirname, named):
+    """Write each (name, tensor) as dirname/name.npy in float32 (float64 stays
+    float64).  An array of more than DUMP_MAX_ELEMS elements is written as a
+    1-D sample: the elements at DUMP_MAX_ELEMS flat (C-order) indices drawn
+    with replacement by a CPU generator seeded with DUMP_SEED, in ascending
+    order; the indices depend on the element count alone, so two builds run
+    with the same arguments write the same elements."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in named:
+        t = torch.as_tensor(t).detach()
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).contiguous()
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy())
 
 
 # ----------------------------------------------------------------------------
@@ -404,9 +451,10 @@ def conv_roofline(stats, precision, B, traffic):
     }
 
 
-def forward_leg(args, world, rank, dev, precision, variant, B, S, traffic, cpu_sample):
+def forward_leg(args, world, rank, dev, precision, variant, B, S, traffic, cpu_sample, dump=None):
     """One forward config: build the seeded model, time `args.steps` forwards of
-    this rank's resident shard, report roofline / parity / CPU baseline."""
+    this rank's resident shard, report the roofline and, with --full, parity and
+    the CPU baseline; `dump` is the --dump-outputs directory of the headline leg."""
     from models.model import UP_Retinex
     pre = aspp = variant == "preact_aspp"
     torch.manual_seed(0)
@@ -484,7 +532,9 @@ def forward_leg(args, world, rank, dev, precision, variant, B, S, traffic, cpu_s
                 gbs = s["bytes"] / (s["ms"] * 1e-3) / 1e9 if s["ms"] else 0
                 print(f"{s['name']:44s} {s['kind']:10s} {s['ms'] / max(s['calls'], 1):9.3f} ms "
                       f"{tf:8.1f} TF/s {gbs:8.1f} GB/s", file=sys.stderr)
-    if rank == 0:
+    if rank == 0 and dump:
+        dump_outputs(dump, zip(("enhanced", "reflectance", "illumination"), last))
+    if rank == 0 and args.full:
         out["parity"] = parity_vs_cpu(sd_cpu, pre, aspp, x, last, precision)
         if world == 1 and args.cpu_seconds > 0 and cpu_sample:
             n, note = cpu_sample
@@ -582,7 +632,7 @@ def train_roofline(recs, step_ms, B, S):
             "whole_step_frac_fp16_peak": TRAIN_GFLOP_PER_IMG * (S / 512.0) ** 2 * B / step_ms / PEAK_TFLOPS["fp16"]}
 
 
-def train_leg(args, world, rank, dev, B, S, amp, steps, warmup, variant):
+def train_leg(args, world, rank, dev, B, S, amp, steps, warmup, variant, dump=None):
     from models.model import UP_Retinex
     from losses.loss import TotalLoss
     from trainers.train import make_optimizer, train_step
@@ -606,14 +656,22 @@ def train_leg(args, world, rank, dev, B, S, amp, steps, warmup, variant):
 
     _, d0 = tstep()  # first warm-up step: its loss dict (initial weights) is the parity sample
     elapsed, last = timed_loop(world, dev, steps, max(warmup - 1, 0), tstep)
-    # one more (untimed) step with per-conv HIP events for the roofline split
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    T.profile_begin()
-    tstep()
-    recs = T.profile_end()
-    prof_ms = 1000.0 * (time.perf_counter() - t0)
+    if rank == 0 and dump:
+        # what the step's caller holds afterwards: the loss, its terms (sorted by name) and the updated parameters
+        terms = sorted((k, float(v)) for k, v in last[1].items() if isinstance(v, (int, float)))
+        dump_outputs(dump, [("loss", torch.tensor([float(last[0])], dtype=torch.float64)),
+                            ("loss_terms", torch.tensor([v for _, v in terms], dtype=torch.float64)),
+                            ("parameters", torch.cat([p.detach().reshape(-1).float() for p in model.parameters()]))])
     step_ms = 1000.0 * elapsed / steps
+    recs, prof_ms = None, None
+    if args.full:
+        # one more (untimed) step with per-conv HIP events for the roofline split
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        T.profile_begin()
+        tstep()
+        recs = T.profile_end()
+        prof_ms = 1000.0 * (time.perf_counter() - t0)
     imgs = world * B * steps
     out = {
         "metric": f"train images/sec at {S}x{S} bs={B} (UP-Retinex fwd + TotalLoss + bwd + clip + Adam)",
@@ -629,10 +687,11 @@ def train_leg(args, world, rank, dev, B, S, amp, steps, warmup, variant):
                    "parallelism": f"data-parallel x{world} (per-rank shard"
                                   + (", RCCL all-reduce of the flat gradient buffer)" if world > 1 else ")")},
         "last_loss": last[1] if last is not None else None,
-        "roofline": train_roofline(recs, step_ms, B, S),
-        "profiled_step_wall_ms": prof_ms,
     }
-    if rank == 0:
+    if recs is not None:
+        out["roofline"] = train_roofline(recs, step_ms, B, S)
+        out["profiled_step_wall_ms"] = prof_ms
+    if rank == 0 and args.full:
         out["parity"] = train_parity(sd_cpu, x, d0, amp, variant == "preact_aspp", variant == "preact_aspp")
         if world == 1 and args.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_train_baseline(sd_cpu, S)
@@ -711,7 +770,7 @@ def cpu_enhance_child(n, size):
         return {"value": None, "error": f"{type(e).__name__}: {e}"[:300]}
 
 
-def enhance_leg(args, world, rank, dev, B, S, traffic, cpu_res):
+def enhance_leg(args, world, rank, dev, B, S, traffic, cpu_res, dump=None):
     """One step = the enhancers over a resident batch of B SxS images: the
     CLAHE-in-Lab pipeline of apply_clahe_enhancement on the enhanced images
     (upr_clahe_enhance: quantise + Lab + tile histograms -> LUTs -> blend +
@@ -780,7 +839,9 @@ def enhance_leg(args, world, rank, dev, B, S, traffic, cpu_res):
                                              "clamp (read enh, write out)"},
         },
     }
-    if rank == 0:
+    if rank == 0 and dump:
+        dump_outputs(dump, zip(("clahe", "multiscale"), last))
+    if rank == 0 and args.full:
         # parity: images 0 and B-1 of the last step vs the restatement (bit-exact bytes expected)
         from oracle import enhancers as oenh  # checker only
         idx = [0, B - 1] if B > 1 else [0]
@@ -811,7 +872,9 @@ def dry_run(args):
             col(a[0][:4].half(), 4 * world)
         return a[0]
 
-    elapsed, _ = timed_loop(world, dev, args.steps, args.warmup, step)
+    elapsed, last = timed_loop(world, dev, args.steps, args.warmup, step)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("dry_run", last)])
     ranks = [None] * world
     if world > 1:
         torch.distributed.all_gather_object(ranks, (rank, os.getpid()))
@@ -824,8 +887,10 @@ def dry_run(args):
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": 1000.0 * elapsed / args.steps, "ranks": ranks, "data": "none",
                "config": {"workload": wl, "parallelism": f"batch-shard x{world} collect={args.collect}"},
-               "roofline": dict(stand_in, traffic=None), "parity": dict(stand_in, max_abs_diff=None)}
-        if world == 1:
+               "roofline": dict(stand_in, traffic=None)}
+        if args.full:
+            out["parity"] = dict(stand_in, max_abs_diff=None)
+        if args.full and world == 1:
             out["cpu_baseline"] = dict(stand_in, cpu=cpu_info())
         if not args.no_nested and not args.train and not (args.precision == "fp16" and args.variant == "preact_aspp"):
             out["fp16_preact_aspp"] = {"value": None, "roofline": None, "parity": dict(stand_in),
@@ -921,7 +986,7 @@ def main():
         if world == 1 and args.cpu_seconds > 0:
             cpuE = cpu_enhance_child(args.batch, args.size) if not _under_profiler() else _CPU_SKIPPED
         world, rank, dev = dist_setup(args)
-        out = enhance_leg(args, world, rank, dev, args.batch, args.size, trE, cpuE)
+        out = enhance_leg(args, world, rank, dev, args.batch, args.size, trE, cpuE, args.dump_outputs)
         if rank == 0:
             emit(out, args)
         if world > 1:
@@ -930,7 +995,7 @@ def main():
     if args.train:
         world, rank, dev = dist_setup(args)
         out = train_leg(args, world, rank, dev, args.batch if args.batch != 32 else 8, args.size, args.amp,
-                        args.steps, args.warmup, args.variant)
+                        args.steps, args.warmup, args.variant, args.dump_outputs)
         if rank == 0:
             emit(out, args)
         if world > 1:
@@ -950,7 +1015,7 @@ def main():
     world, rank, dev = dist_setup(args)
     B, S = args.batch, args.size
     out = forward_leg(args, world, rank, dev, args.precision, args.variant, B, S, traffic,
-                      (B, "the full timed batch"))
+                      (B, "the full timed batch"), args.dump_outputs)
     if nested:
         out["fp16_preact_aspp"] = forward_leg(args, world, rank, dev, "fp16", "preact_aspp", B, S, traffic16,
                                               (B, "the full timed batch"))

@@ -155,7 +155,7 @@ def test_bench_gpus2_line_carries_evidence_keys():
     """An N>1 line carries rank 0's parity, the roofline object and the nested
     fp16 object; cpu_baseline and train_amp are N=1 only; --collect rank0 runs
     the gather-to-rank-0 collect through the same timed loop (gloo here)."""
-    out = _bench_json(["--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "1", "--collect", "rank0"])
+    out = _bench_json(["--gpus", "2", "--dry-run", "--full", "--steps", "2", "--warmup", "1", "--collect", "rank0"])
     assert out["n_gpus"] == 2
     for k in ("roofline", "parity", "fp16_preact_aspp", "config"):
         assert k in out, k
@@ -165,7 +165,7 @@ def test_bench_gpus2_line_carries_evidence_keys():
 
 
 def test_bench_n1_line_carries_cpu_and_train_keys():
-    out = _bench_json(["--dry-run", "--steps", "2", "--warmup", "1"])
+    out = _bench_json(["--dry-run", "--full", "--steps", "2", "--warmup", "1"])
     for k in ("roofline", "parity", "cpu_baseline", "fp16_preact_aspp", "train_amp"):
         assert k in out, k
     ci = out["cpu_baseline"]["cpu"]
@@ -187,7 +187,7 @@ def test_bench_config_labels():
     for args in (("fp16", "plain", 512, 32), ("fp32", "preact_aspp", 512, 32), ("fp32", "plain", 512, 8),
                  ("fp16", "preact_aspp", 512, 16), ("fp32", "plain", 1024, 32), ("fp16", "preact_aspp", 256, 32)):
         assert b.cfg_label(*args) == "off-config", args
-    out = _bench_json(["--dry-run", "--steps", "1", "--warmup", "0"])
+    out = _bench_json(["--dry-run", "--full", "--steps", "1", "--warmup", "0"])
     assert out["config"]["workload"] == "configs[1]"
     assert out["fp16_preact_aspp"]["config"]["workload"] == "configs[2]"
     out = _bench_json(["--dry-run", "--steps", "1", "--warmup", "0", "--precision", "fp16"])
@@ -195,3 +195,68 @@ def test_bench_config_labels():
     out = _bench_json(["--dry-run", "--steps", "1", "--warmup", "0", "--precision", "fp16", "--variant",
                        "preact_aspp", "--size", "1024"])
     assert out["config"]["workload"] == "configs[3]" and "fp16_preact_aspp" not in out
+
+
+def test_bench_plain_run_is_headline_only():
+    """Without --full the line carries the headline and its roofline object and
+    none of what --full adds (parity, CPU baseline, nested objects), whatever
+    the trimming flags say; --steps sets the number of timed steps."""
+    out = _bench_json(["--gpus", "1", "--dry-run", "--steps", "3", "--warmup", "1", "--cpu-seconds", "5"])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert "roofline" in out
+    for k in ("parity", "cpu_baseline", "fp16_preact_aspp", "enhance", "train_amp"):
+        assert k not in out, k
+
+
+def _load_bench():
+    import importlib.util
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(repo, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+def test_bench_full_flag_gates_the_extras():
+    """parse(): a plain run switches the traffic passes, the nested objects and
+    the CPU baselines off; --full leaves them to their own flags."""
+    b = _load_bench()
+    a = b.parse(["--gpus", "1", "--steps", "4", "--warmup", "2"])
+    assert not a.full and a.no_traffic and a.no_nested and a.cpu_seconds == 0 and a.dump_outputs is None
+    a = b.parse(["--full"])
+    assert a.full and not a.no_traffic and not a.no_nested and a.cpu_seconds > 0
+    a = b.parse(["--full", "--no-nested", "--cpu-seconds", "0"])
+    assert a.full and a.no_nested and a.cpu_seconds == 0 and not a.no_traffic
+
+
+def test_bench_dump_outputs_small_and_sampled(tmp_path):
+    """dump_outputs writes float32 .npy files: a small array whole, a large one
+    as the same DUMP_MAX_ELEMS seeded flat positions on every call; float64
+    stays float64."""
+    import numpy as np
+    b = _load_bench()
+    small = torch.arange(24, dtype=torch.float16).reshape(2, 3, 4)
+    big = torch.arange(b.DUMP_MAX_ELEMS + 1001, dtype=torch.float32) % 8191
+    d1, d2 = str(tmp_path / "a"), str(tmp_path / "b" / "c")
+    b.dump_outputs(d1, [("small", small), ("big", big), ("f64", torch.ones(3, dtype=torch.float64))])
+    b.dump_outputs(d2, [("big", big + 1)])
+    s = np.load(os.path.join(d1, "small.npy"))
+    assert s.dtype == np.float32 and s.shape == (2, 3, 4) and np.array_equal(s, small.float().numpy())
+    assert np.load(os.path.join(d1, "f64.npy")).dtype == np.float64
+    g1, g2 = np.load(os.path.join(d1, "big.npy")), np.load(os.path.join(d2, "big.npy"))
+    assert g1.dtype == np.float32 and g1.shape == (b.DUMP_MAX_ELEMS,) and g1.nbytes <= 16 << 20
+    assert np.array_equal(g2, g1 + 1)          # the same positions both times
+    assert len(np.unique(g1)) == 8191          # spread over the array, not a prefix
+
+
+def test_bench_dump_outputs_same_inputs_every_run(tmp_path):
+    """Two runs with the same arguments write identical arrays (the dry run's
+    CPU stand-in step here; the GPU legs seed their inputs the same way)."""
+    import numpy as np
+    outs = []
+    for name in ("r1", "r2"):
+        d = str(tmp_path / name)
+        _bench_json(["--gpus", "1", "--dry-run", "--steps", "2", "--warmup", "1", "--dump-outputs", d])
+        assert os.listdir(d) == ["dry_run.npy"]
+        outs.append(np.load(os.path.join(d, "dry_run.npy")))
+    assert outs[0].dtype == np.float32 and np.array_equal(outs[0], outs[1])

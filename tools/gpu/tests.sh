@@ -9,6 +9,6 @@ rc=$?
 echo "pytest rc=$rc"; grep -E "passed|failed|FAILED|Error" $out/gpu_tests.log | tail -15
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 if [ -n "$BENCH" ]; then
-  timeout -k 10 600 python bench.py > $out/bench.json 2> $out/bench.err || exit $?
+  timeout -k 10 600 python bench.py --full > $out/bench.json 2> $out/bench.err || exit $?
 fi
 exit $rc
