@@ -83,6 +83,16 @@ int upr_t_conv_direct_wgrad_relu(const UprView* x, const UprView* dy, const UprV
 int upr_t_conv_stem_wgrad_relu16(const UprView* x, const float* dy, const void* y16, int B, int H, int W, float* dw,
                                  float* dbias, void* stream);
 
+/* Bits of the `store` argument of upr_t_conv_mfma (the first only) and
+ * upr_t_conv_mfma16 (all, OR-ed together); the prose below names them by
+ * value. */
+#define UPR_T_STORE_CONVT2X2 1      /* ConvTranspose2d k2 s2 pixel shuffle */
+#define UPR_T_STORE_KEEP16 2        /* y16 must afterwards hold (half)y */
+#define UPR_T_STORE_ONLY16 4        /* with KEEP16: y need not be written */
+#define UPR_T_STORE_S2_1X1 8        /* input gradient of a 1x1 stride-2 conv */
+#define UPR_T_STORE_S2_3X3_DGRAD 16 /* input gradient of a 3x3 stride-2 pad-1 conv */
+#define UPR_T_STORE_X16_STRIDED 32  /* the ready x16 keeps x's channel stride */
+
 /* MFMA implicit-GEMM conv (the inference kernels of conv.hip/conv_halo.hip) on
  * NHWC sources with channel stride/offset; Cin, Cout multiples of 32.
  * wp: packed [N][kh*kw*Cin] (upr_t_pack_weight).  res (nullable) is added

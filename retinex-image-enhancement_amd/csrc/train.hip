@@ -1,181 +1,15 @@
 // Training kernels for gfx950: the backward pass of MultiScaleUP_Retinex, the
 // TotalLoss terms with their gradients, and the clip + Adam optimiser step
 // (reference trainers/train.py:63-103, losses/loss.py:12-753, models/model.py).
-// Contract of every entry: include/upr_train.h.
-//
-// Layout: activations are addressed through UprView strides (NCHW inputs,
-// NHWC activations, channel slices of concat buffers).  Everything computes in
-// fp32; per-channel / per-image reductions accumulate in fp64 (block partials
-// in registers + LDS, one fp64 atomic per block and channel).
+// Contract of every entry: include/upr_train.h; layout and precision:
+// train_common.h.
 #include <cstdlib>
 #include <cmath>
 #include <cstring>
-#include <mutex>
-#include <thread>
 
-#include "upr_common.h"
-#include "../../include/upr.h"
-#include "../../include/upr_train.h"
+#include "train_common.h"
 
 namespace upr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct V {
-  float* d;
-  long long sb, sh, sw, sc;
-  __device__ __forceinline__ long long at(int b, int y, int x, int c) const {
-    return b * sb + y * sh + x * sw + c * sc;
-  }
-};
-
-static V mkv(const UprView* u) {
-  V v;
-  v.d = (float*)u->data;
-  v.sb = u->sb; v.sh = u->sh; v.sw = u->sw; v.sc = u->sc;
-  return v;
-}
-
-// channel-contiguous view with 32-bit strides: the 4-channels-per-thread
-// resampling / copy kernels (the generic V kernels' 64-bit div/mod per element
-// run below 1 TB/s)
-struct V4 {
-  float* d;
-  int sb, sh, sw;
-  __device__ __forceinline__ float* at(int b, int y, int x, int c) const { return d + b * sb + y * sh + x * sw + c; }
-};
-
-// usable as a V4 over [B, H, W, C]: unit channel stride, C and the strides
-// multiples of 4, 16-byte aligned, every offset below 2^31
-static bool vec4_view_ok(const UprView* v, int B, int H, int W, int C) {
-  if (v->sc != 1 || C % 4 || (uintptr_t)v->data % 16 || v->sw % 4 || v->sh % 4 || v->sb % 4) return false;
-  if ((long long)B * H * W * C >= (1LL << 31)) return false;
-  const long long ext = (long long)(B - 1) * v->sb + (long long)(H - 1) * v->sh + (long long)(W - 1) * v->sw + C;
-  return ext < (1LL << 31) && v->sb < (1LL << 31) && v->sh < (1LL << 31) && v->sw < (1LL << 31);
-}
-
-// 4 consecutive channels as floats, from fp32 or an fp16 copy
-__device__ __forceinline__ float4 ld4f(const float* p) { return *(const float4*)p; }
-__device__ __forceinline__ float4 ld4f(const half_t* p) {
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-  const h4 v = *(const h4*)p;
-  return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-}
-
-static V4 mkv4(const UprView* u) {
-  V4 v;
-  v.d = (float*)u->data;
-  v.sb = (int)u->sb; v.sh = (int)u->sh; v.sw = (int)u->sw;
-  return v;
-}
-
-static inline int grid_for(long long n, int per = 256, int cap = 65536) {
-  long long g = (n + per - 1) / per;
-  if (g < 1) g = 1;
-  return (int)(g > cap ? cap : g);
-}
-
-#define GSTRIDE(i, n) for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < (n); \
-                           i += (long long)gridDim.x * blockDim.x)
-
-#define LAUNCH_CHECK() return (int)hipGetLastError()
-
-// train_small.hip: pixel-tiled / MFMA forms of the small-channel convs
-int small_conv_fwd(const UprView* xv, int B, int H, int W, int Cin, const float* w, const float* bias, int Cout,
-                   int kh, int kw, int stride, int pad, int dil, const UprView* yv, int Ho, int Wo, int relu,
-                   int accumulate, hipStream_t st, void* y16 = nullptr, int skip32 = 0);
-int small_stem_wgrad_relu16(const UprView* xv, const float* dy, const void* y16, int B, int H, int W, float* dw,
-                            float* dbias, hipStream_t st);
-int small_conv_dgrad(const UprView* dyv, int Ho, int Wo, const float* w, int B, int H, int W, int Cin, int Cout,
-                     int kh, int kw, int stride, int pad, int dil, const UprView* dxv, int accumulate, hipStream_t st);
-int small_conv_dgrad_c3_16(const void* dy16, int B, int H, int W, const float* w, int Cout, const UprView* dxv,
-                           int accumulate, hipStream_t st);
-int small_conv_wgrad(const UprView* xv, const UprView* dyv, int B, int H, int W, int Cin, int Ho, int Wo, int Cout,
-                     int kh, int kw, int stride, int pad, int dil, float* dw, float* dbias, hipStream_t st,
-                     const UprView* ymask = nullptr);
-// train_wgrad.hip: split-K GEMM weight gradient (the conv_wgrad_kernel below takes the shapes it does not)
-int wgrad_gemm(const float* x, int B, int H, int W, int Cin, int x_cs, int x_coff, const float* dy, int Ho, int Wo,
-               int Cout, int dy_cs, int dy_coff, int kh, int kw, int stride, int pad, int dil, float* dwp,
-               hipStream_t st, int torch_ci = 0);
-int wgrad16_gemm(const void* x16, int B, int H, int W, int Cin, const float* dy, int Ho, int Wo, int Cout, int dy_cs,
-                 int dy_coff, int kh, int kw, int stride, int pad, int dil, float* dwp, hipStream_t st,
-                 int torch_ci = 0, const void* dy16 = nullptr);
-
-// scratch(): see upr_common.h
-void* scratch(int slot, size_t bytes, hipStream_t st, bool* fresh) {
-  struct Entry {
-    int dev;
-    hipStream_t st;
-    void* p[kSlotCount];
-    size_t n[kSlotCount];
-    std::thread::id owner;     // the one thread that used the entry (unless shared)
-    bool shared;               // used by more than one thread: never reclaimed
-    unsigned long long tick;   // last use (LRU)
-  };
-  static std::mutex mu;
-  static Entry tab[kScratchStreams];
-  static int used = 0;
-  static unsigned long long clock = 0;
-  if (fresh) *fresh = false;
-  if (slot < 0 || slot >= kSlotCount) return nullptr;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  const std::thread::id me = std::this_thread::get_id();
-  std::lock_guard<std::mutex> lock(mu);
-  Entry* e = nullptr;
-  for (int i = 0; i < used; ++i)
-    if (tab[i].dev == dev && tab[i].st == st) e = &tab[i];
-  if (!e) {
-    if (used < kScratchStreams) {
-      e = &tab[used++];
-    } else {
-      // full: reclaim the least recently used entry that only THIS thread
-      // ever used.  Its buffers went out only in this thread's earlier calls,
-      // which returned after enqueueing their launches, so once the device is
-      // idle nobody reads them (another thread's entries may be mid-call:
-      // their pointers can still be waiting for a launch, so they are never
-      // taken).  The device synchronise is not allowed while the caller's
-      // stream is being captured: then the call fails as before.
-      Entry* v = nullptr;
-      for (int i = 0; i < used; ++i)
-        if (!tab[i].shared && tab[i].owner == me && tab[i].dev == dev && (!v || tab[i].tick < v->tick)) v = &tab[i];
-      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-      if (!v || hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
-        (void)hipGetLastError();
-        return nullptr;
-      }
-      if (hipDeviceSynchronize() != hipSuccess) return nullptr;
-      for (int k = 0; k < kSlotCount; ++k)
-        if (v->p[k]) (void)hipFree(v->p[k]);
-      e = v;
-    }
-    *e = Entry{};
-    e->dev = dev;
-    e->st = st;
-    e->owner = me;
-  } else if (e->owner != me) {
-    e->shared = true;
-  }
-  e->tick = ++clock;
-  if (bytes == 0) bytes = 16;
-  if (e->n[slot] < bytes) {
-    if (e->p[slot]) {
-      if (hipStreamSynchronize(st) != hipSuccess) return nullptr;  // earlier kernels may still read it
-      (void)hipFree(e->p[slot]);
-      e->p[slot] = nullptr;
-      e->n[slot] = 0;
-    }
-    const size_t grow = bytes + bytes / 4;  // headroom: one growth covers nearby sizes
-    if (hipMalloc(&e->p[slot], grow) != hipSuccess) {
-      (void)hipGetLastError();
-      e->p[slot] = nullptr;
-      return nullptr;
-    }
-    e->n[slot] = grow;
-    if (fresh) *fresh = true;
-  }
-  return e->p[slot];
-}
 
 // ---------------------------------------------------------------------------
 // Direct convolution (small channel counts): forward / dgrad / wgrad
@@ -563,6 +397,53 @@ __global__ __launch_bounds__(256) void zero_upsample16_kernel(const float* __res
   }
 }
 
+// ---- autocast (AMP) convs: fp16 operands, fp32 accumulate, fp32 activations ----
+// x[m][coff + c] (fp32, pixel stride cs) -> dense fp16 [m][C], 8 channels per thread
+__global__ __launch_bounds__(256) void cast_act_f16_kernel(const float* __restrict__ x, long long M, int C, int cs,
+                                                           int coff, half_t* __restrict__ y) {
+  const int C8 = C / 8;
+  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+  if (256 % C8 == 0) {  // fixed channels per thread, rows by addition (no 64-bit div per element)
+    const int c = (threadIdx.x % C8) * 8, rpb = 256 / C8;
+    for (long long m = (long long)blockIdx.x * rpb + threadIdx.x / C8; m < M; m += (long long)gridDim.x * rpb) {
+      const float4* src = (const float4*)(x + m * cs + coff + c);
+      const float4 a = src[0], b = src[1];
+      *(h8*)(y + m * C + c) =
+          h8{(half_t)a.x, (half_t)a.y, (half_t)a.z, (half_t)a.w, (half_t)b.x, (half_t)b.y, (half_t)b.z, (half_t)b.w};
+    }
+    return;
+  }
+  GSTRIDE(i, M * C8) {
+    const long long m = i / C8;
+    const int c = (int)(i - m * C8) * 8;
+    const float4* src = (const float4*)(x + m * cs + coff + c);
+    const float4 a = src[0], b = src[1];
+    h8 o = {(half_t)a.x, (half_t)a.y, (half_t)a.z, (half_t)a.w, (half_t)b.x, (half_t)b.y, (half_t)b.z, (half_t)b.w};
+    *(h8*)(y + m * C + c) = o;
+  }
+}
+// dense fp16 [m][C] -> y[m][coff + c] (fp32) (+ res[m * res_cs + c], fp32; res may alias y)
+__global__ __launch_bounds__(256) void cast_act_f32_kernel(const half_t* __restrict__ x, long long M, int C,
+                                                           const float* res, int res_cs, float* y, int cs, int coff,
+                                                           int xcs) {
+  const int C4 = C / 4;
+  GSTRIDE(i, M * C4) {
+    const long long m = i / C4;
+    const int c = (int)(i - m * C4) * 4;
+    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+    const h4 v = *(const h4*)(x + m * xcs + c);
+    float4 o = make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+    if (res) {
+      const float4 r = *(const float4*)(res + m * res_cs + c);
+      o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
+    }
+    *(float4*)(y + m * cs + coff + c) = o;
+  }
+}
+__global__ __launch_bounds__(256) void cast_f16_kernel(const float* __restrict__ x, long long n, half_t* __restrict__ y) {
+  GSTRIDE(i, n) y[i] = (half_t)x[i];
+}
+
 // ---------------------------------------------------------------------------
 // per-channel reductions over M rows: mode 0 (x, x^2), mode 1 (g, g*xhat),
 // mode 2 (g) -> float out via atomics
@@ -849,8 +730,55 @@ static int chan_reduce2(const TA* a, int a_cs, int a_coff, const TX* x, int x_cs
   return (int)hipGetLastError();
 }
 
-
-
+// chan_fin (mode 0) and bn_finalize in one launch: a block owns 32 channels,
+// lanes 0-31 their sums and 32-63 their sums of squares (the same slot order
+// and partial-sum tree as chan_fin: bit-identical acc), then lanes 0-31
+// finalise their channel as bn_finalize_kernel does
+__global__ __launch_bounds__(256) void chan_fin_bn_kernel(const double* __restrict__ part, int slots, int C,
+                                                          double* __restrict__ acc, int M, float momentum, float eps,
+                                                          float* __restrict__ rm, float* __restrict__ rv,
+                                                          long long* nbt, float* __restrict__ mean,
+                                                          float* __restrict__ invstd) {
+  __shared__ double red[4][64];
+  __shared__ double fin[64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int c = blockIdx.x * 32 + (lane & 31);
+  const bool ok = c < C;
+  const int t = lane < 32 ? c : C + c;
+  double sum = 0.0;  // (chan_fin_kernel's order and batching)
+  if (ok) {
+    for (int k0 = w; k0 < slots; k0 += 64) {
+      double v[16];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int k = k0 + 4 * u;
+        v[u] = k < slots ? part[(size_t)k * 2 * C + t] : 0.0;
+      }
+#pragma unroll
+      for (int u = 0; u < 16; ++u) sum += v[u];
+    }
+  }
+  red[w][lane] = sum;
+  __syncthreads();
+  if (w == 0) {
+    const double v = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+    fin[lane] = v;
+    if (ok) acc[t] = v;
+  }
+  __syncthreads();
+  if (blockIdx.x == 0 && threadIdx.x == 0 && nbt) *nbt += 1;
+  if (w != 0 || lane >= 32 || !ok) return;
+  const double mu = fin[lane] / M;
+  double var = fin[lane + 32] / M - mu * mu;
+  if (var < 0) var = 0;
+  mean[c] = (float)mu;
+  invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
+  if (rm) rm[c] = (1.f - momentum) * rm[c] + momentum * (float)mu;
+  if (rv) {
+    const double unb = M > 1 ? var * M / (M - 1) : var;
+    rv[c] = (1.f - momentum) * rv[c] + momentum * (float)unb;
+  }
+}
 
 __global__ void bn_finalize_kernel(const double* __restrict__ acc, int M, int C, float momentum, float eps,
                                    float* __restrict__ rm, float* __restrict__ rv, long long* nbt,
@@ -1208,6 +1136,18 @@ __global__ void pointwise_kernel(const float* a, const float* b, float* out, lon
   }
 }
 
+// out = a + b with its fp16 copy (a residual / skip sum feeding an autocast conv)
+__global__ __launch_bounds__(256) void add16_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                    float* __restrict__ out, half_t* __restrict__ out16, int n4) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  const float4 u = ((const float4*)a)[i], v = ((const float4*)b)[i];
+  const float4 r = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
+  ((float4*)out)[i] = r;
+  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+  ((h4*)out16)[i] = h4{(half_t)r.x, (half_t)r.y, (half_t)r.z, (half_t)r.w};
+}
+
 // ---------------------------------------------------------------------------
 // pooling / resampling
 // ---------------------------------------------------------------------------
@@ -1232,6 +1172,248 @@ __global__ void maxpool_kernel(V x, int B, int H, int W, int C, int k, int s, in
     }
     y.d[y.at(b, oy, ox, c)] = m;
   }
+}
+
+// Max-pool backward as two deterministic passes (no float atomics):
+//  1. per output element the window position of its max, PyTorch's rule
+//     (max_pool2d CPU kernel: the first in-bounds tap, then every tap with
+//     v > max or v NaN), as a byte code ky * k + kx;
+//  2. per input element, in output order, the dy of every window whose code
+//     points at it, added to dx.
+template <int VEC>
+__global__ void maxpool_arg_kernel(V x, int B, int H, int W, int C, int k, int s, int p, int Ho, int Wo,
+                                   unsigned char* __restrict__ code) {
+  const int CV = C / VEC;
+  const long long n = (long long)B * Ho * Wo * CV;
+  GSTRIDE(i, n) {
+    const int c = (int)(i % CV) * VEC;
+    long long r = i / CV;
+    const int ox = (int)(r % Wo); r /= Wo;
+    const int oy = (int)(r % Ho);
+    const int b = (int)(r / Ho);
+    float m[VEC];
+    int best[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) { m[v] = -INFINITY; best[v] = -1; }
+    for (int ky = 0; ky < k; ++ky) {
+      const int iy = oy * s - p + ky;
+      if (iy < 0 || iy >= H) continue;
+      for (int kx = 0; kx < k; ++kx) {
+        const int ix = ox * s - p + kx;
+        if (ix < 0 || ix >= W) continue;
+        float val[VEC];
+        if constexpr (VEC == 4) {
+          const float4 q = *(const float4*)(x.d + x.at(b, iy, ix, c));
+          val[0] = q.x; val[1] = q.y; val[2] = q.z; val[3] = q.w;
+        } else {
+          val[0] = x.d[x.at(b, iy, ix, c)];
+        }
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+          if (best[v] < 0) best[v] = ky * k + kx;  // the first in-bounds tap is the default index
+          if (val[v] > m[v] || isnan(val[v])) {
+            m[v] = val[v];
+            best[v] = ky * k + kx;
+          }
+        }
+      }
+    }
+    unsigned char* o = code + (((long long)b * Ho + oy) * Wo + ox) * C + c;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) o[v] = (unsigned char)(best[v] < 0 ? 255 : best[v]);
+  }
+}
+
+template <int VEC>
+__global__ void maxpool_bwd_gather_kernel(const unsigned char* __restrict__ code, V dy, int B, int H, int W, int C, int k,
+                                          int s, int p, int Ho, int Wo, V dx) {
+  const int CV = C / VEC;
+  const long long n = (long long)B * H * W * CV;
+  GSTRIDE(i, n) {
+    const int c = (int)(i % CV) * VEC;
+    long long r = i / CV;
+    const int ix = (int)(r % W); r /= W;
+    const int iy = (int)(r % H);
+    const int b = (int)(r / H);
+    float* dp = dx.d + dx.at(b, iy, ix, c);
+    float acc[VEC];
+    if constexpr (VEC == 4) {
+      const float4 q = *(const float4*)dp;
+      acc[0] = q.x; acc[1] = q.y; acc[2] = q.z; acc[3] = q.w;
+    } else {
+      acc[0] = *dp;
+    }
+    // windows containing (iy, ix): oy*s - p <= iy <= oy*s - p + k - 1
+    const int oy0 = max(0, (iy + p - k + 1 + s - 1 + s * k) / s - k), oy1 = min(Ho - 1, (iy + p) / s);
+    const int ox0 = max(0, (ix + p - k + 1 + s - 1 + s * k) / s - k), ox1 = min(Wo - 1, (ix + p) / s);
+    for (int oy = oy0; oy <= oy1; ++oy) {
+      const int ty = iy - (oy * s - p);
+      if (ty < 0 || ty >= k) continue;
+      for (int ox = ox0; ox <= ox1; ++ox) {
+        const int tx = ix - (ox * s - p);
+        if (tx < 0 || tx >= k) continue;
+        const unsigned char want = (unsigned char)(ty * k + tx);
+        const unsigned char* cd = code + (((long long)b * Ho + oy) * Wo + ox) * C + c;
+        const float* g = dy.d + dy.at(b, oy, ox, c);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v)
+          if (cd[v] == want) acc[v] += g[v * dy.sc];
+      }
+    }
+    if constexpr (VEC == 4) {
+      *(float4*)dp = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    } else {
+      *dp = acc[0];
+    }
+  }
+}
+
+// Fast paths for the two pools of the training step -- EnhancedFAM's 3x3/1/1
+// (models/model.py:32) and the VGG 2x2/2 (losses/loss.py perceptual
+// features[4], [9], [18]) -- on channel-contiguous views: 4 channels per
+// thread, 32-bit index math (the generic kernels' 64-bit div/mod per element
+// ran at <1 TB/s), compile-time windows.  The forward optionally writes the
+// argmax byte codes (PyTorch's rule, as maxpool_arg_kernel) so the backward
+// is the gather alone.
+// TI = half_t: the input is an activation's compact fp16 copy (the autocast
+// VGG activations live in fp16 only, as the reference's under autocast)
+template <int K, int S, int P, typename TI = float>
+__global__ __launch_bounds__(256) void maxpool4_kernel(const TI* __restrict__ x, int xsb, int xsh, int xsw, int H,
+                                                       int W, int CV, int Ho, int Wo, int n, float* __restrict__ y,
+                                                       int ysb, int ysh, int ysw, unsigned* __restrict__ code,
+                                                       half_t* __restrict__ y16) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int c = (i % CV) * 4;
+  int r = i / CV;
+  const int ox = r % Wo;
+  r /= Wo;
+  const int oy = r % Ho, b = r / Ho;
+  float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  int best[4] = {-1, -1, -1, -1};
+  const TI* xb = x + b * xsb + c;
+#pragma unroll
+  for (int ky = 0; ky < K; ++ky) {
+    const int iy = oy * S - P + ky;
+    if ((unsigned)iy >= (unsigned)H) continue;
+#pragma unroll
+    for (int kx = 0; kx < K; ++kx) {
+      const int ix = ox * S - P + kx;
+      if ((unsigned)ix >= (unsigned)W) continue;
+      const float4 q = ld4f(xb + iy * xsh + ix * xsw);
+      const float val[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        if (best[v] < 0) best[v] = ky * K + kx;
+        if (val[v] > m[v] || isnan(val[v])) {
+          m[v] = val[v];
+          best[v] = ky * K + kx;
+        }
+      }
+    }
+  }
+  if (y) *(float4*)(y + b * ysb + oy * ysh + ox * ysw + c) = make_float4(m[0], m[1], m[2], m[3]);
+  if (y16) {  // compact [b][oy][ox][C] fp16 copy: element index 4 i
+    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+    *(h4*)(y16 + (size_t)i * 4) = h4{(half_t)m[0], (half_t)m[1], (half_t)m[2], (half_t)m[3]};
+  }
+  if (code) {
+    unsigned w = 0;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) w |= (unsigned)(best[v] < 0 ? 255 : best[v]) << (8 * v);
+    code[i] = w;
+  }
+}
+
+// dx[b][iy][ix][c..c+3] += dy of every window (ascending oy, then ox: the
+// generic gather's order) whose code points at (iy, ix).  O16: the result
+// goes to the compact fp16 g16 instead (element 4 i), masked by the producing
+// ReLU's fp16 output y16 when given -- the frozen VGG's pool backward, whose
+// only reader is the masked fp16 dgrad operand (relu_mask16h fused away)
+template <int K, int S, int P, int O16 = 0>
+__global__ __launch_bounds__(256) void maxpool_gather4_kernel(const unsigned* __restrict__ code,
+                                                              const float* __restrict__ dy, int dsb, int dsh, int dsw,
+                                                              int H, int W, int CV, int Ho, int Wo, int n,
+                                                              float* __restrict__ dx, int xsb, int xsh, int xsw,
+                                                              int accumulate, const half_t* __restrict__ y16 = nullptr,
+                                                              half_t* __restrict__ g16 = nullptr) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int cv = i % CV, c = cv * 4;
+  int r = i / CV;
+  const int ix = r % W;
+  r /= W;
+  const int iy = r % H, b = r / H;
+  float* dp = O16 ? nullptr : dx + b * xsb + iy * xsh + ix * xsw + c;
+  float4 acc = !O16 && accumulate ? *(const float4*)dp : make_float4(0.f, 0.f, 0.f, 0.f);
+  // every window's code word and gradient run is loaded first (independent
+  // loads, one round trip each; a window outside the output reads nothing and
+  // gets the no-hit code 0xffffffff), then the hits are added in the same
+  // window order as before (the 3x3 pool's code -> dy -> next window chain
+  // was 18 dependent round trips per thread: 1.6 TB/s at 512^2)
+  unsigned wv[K * K];
+  float4 gv[K * K];
+#pragma unroll
+  for (int t = 0; t < K; ++t) {
+    const int ky = K - 1 - t, ny = iy + P - ky;  // oy * S
+    const bool oky = ny >= 0 && ny % S == 0 && ny / S < Ho;
+    const int oy = oky ? ny / S : 0;
+#pragma unroll
+    for (int u = 0; u < K; ++u) {
+      const int kx = K - 1 - u, nx = ix + P - kx;
+      const bool ok = oky && nx >= 0 && nx % S == 0 && nx / S < Wo;
+      const int ox = ok ? nx / S : 0;
+      wv[t * K + u] = ok ? code[((b * Ho + oy) * Wo + ox) * CV + cv] : 0xffffffffu;
+      gv[t * K + u] = ok ? *(const float4*)(dy + b * dsb + oy * dsh + ox * dsw + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < K; ++t) {
+    const int ky = K - 1 - t;
+#pragma unroll
+    for (int u = 0; u < K; ++u) {
+      const int kx = K - 1 - u;
+      const unsigned want = (unsigned)(ky * K + kx) * 0x01010101u;
+      const unsigned hit = wv[t * K + u] ^ want;  // a zero byte marks a window whose max sits here
+      const float4 g = gv[t * K + u];
+      if ((hit & 0xffu) == 0) acc.x += g.x;
+      if ((hit & 0xff00u) == 0) acc.y += g.y;
+      if ((hit & 0xff0000u) == 0) acc.z += g.z;
+      if ((hit & 0xff000000u) == 0) acc.w += g.w;
+    }
+  }
+  if (O16) {
+    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+    if (y16) {
+      const h4 y = *(const h4*)(y16 + (size_t)i * 4);
+      if (!(y[0] > (half_t)0)) acc.x = 0.f;
+      if (!(y[1] > (half_t)0)) acc.y = 0.f;
+      if (!(y[2] > (half_t)0)) acc.z = 0.f;
+      if (!(y[3] > (half_t)0)) acc.w = 0.f;
+    }
+    *(h4*)(g16 + (size_t)i * 4) = h4{(half_t)acc.x, (half_t)acc.y, (half_t)acc.z, (half_t)acc.w};
+    return;
+  }
+  *(float4*)dp = acc;
+}
+
+__global__ void zero_view_kernel(V v, int B, int H, int W, int C) {
+  const long long n = (long long)B * H * W * C;
+  GSTRIDE(i, n) {
+    const int c = (int)(i % C);
+    long long r = i / C;
+    const int x = (int)(r % W);
+    r /= W;
+    v.d[v.at((int)(r / H), (int)(r % H), x, c)] = 0.f;
+  }
+}
+
+// shape of a fast-path pool: (k, s, p) one of the two instantiated windows,
+// channel-contiguous 16-byte aligned views whose extents fit 32-bit offsets
+static int pool_fast_kind(int k, int s, int p) {
+  if (k == 3 && s == 1 && p == 1) return 1;
+  if (k == 2 && s == 2 && p == 0) return 2;
+  return 0;
 }
 
 __device__ __forceinline__ void bilin_src(int o, int in, float scale, int& i0, int& i1, float& l) {
@@ -1650,8 +1832,6 @@ __global__ void fam_sa_bwd32_kernel(const float* __restrict__ g, int g_cs, const
     if (q == 0) g_spre[pix] = t * a * (1.f - a);
   }
 }
-
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // g_ca[b][c] partials go through LDS: a block covers a pixel range of one image
 __global__ __launch_bounds__(256) void fam_ca_bwd_kernel(const float* __restrict__ g_o2, const float* __restrict__ g_m,
@@ -2456,6 +2636,28 @@ __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ a, c
   block_sum_atomic<1>(v, dst);
 }
 
+// the same over two fp16 tensors (the frozen VGG's features under autocast,
+// which exist in fp16 only: the reference's mse_loss promotes them to fp32),
+// 4 elements per thread
+__global__ __launch_bounds__(256) void mse16_kernel(const half_t* __restrict__ a, const half_t* __restrict__ b,
+                                                    long long n4, long long n, double* acc, float* g, float scale) {
+  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+  double v[1] = {0.0};
+  GSTRIDE(i, n4) {
+    const h4 x = *(const h4*)(a + 4 * i), y = *(const h4*)(b + 4 * i);
+    float d[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      d[k] = (float)x[k] - (float)y[k];
+      v[0] += (double)d[k] * d[k];
+    }
+    if (g) *(float4*)(g + 4 * i) = make_float4(scale * 2.f * d[0], scale * 2.f * d[1], scale * 2.f * d[2], scale * 2.f * d[3]);
+  }
+  v[0] /= (double)n;
+  double* dst[1] = {acc};
+  block_sum_atomic<1>(v, dst);
+}
+
 __constant__ float kVggMean[3] = {0.485f, 0.456f, 0.406f};
 __constant__ float kVggStd[3] = {0.229f, 0.224f, 0.225f};
 
@@ -2508,6 +2710,8 @@ __global__ void scale_acc_kernel(const double* __restrict__ acc, int n, float sc
   if (i < n) out[i] = (float)(acc[i] * scale);
 }
 
+static const UprLossParams kLossDefaults = {16, 0.6f, 10.f, 1.f, 0.1f, 1.f, 0.5f, 1, 1};
+
 // ---------------------------------------------------------------------------
 // optimiser
 // ---------------------------------------------------------------------------
@@ -2555,8 +2759,6 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 }  // namespace upr
 
 using namespace upr;
-
-#define ST(s) ((hipStream_t)(s))
 
 extern "C" {
 
@@ -2668,7 +2870,7 @@ int upr_t_conv_mfma(const float* x, int B, int H, int W, int Cin, int x_cs, int 
   if (!x || !wp || !y || B <= 0 || Cin % 32 || N % 32 || Cin <= 0 || N <= 0) return UPR_ERR_ARG;
   if (kh <= 0 || kw <= 0 || stride <= 0 || dil <= 0 || pad < 0) return UPR_ERR_ARG;
   if (x_cs % 4 || x_coff % 4 || y_cs % 4 || y_coff % 4 || (res && res_cs % 4)) return UPR_ERR_ARG;
-  if (store == 1 && ((N / 4) % 32)) return UPR_ERR_SHAPE;
+  if (store == UPR_T_STORE_CONVT2X2 && ((N / 4) % 32)) return UPR_ERR_SHAPE;
   const int Ho = (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1;
   const int Wo = (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
   if (Ho <= 0 || Wo <= 0) return UPR_ERR_SHAPE;
@@ -2680,55 +2882,8 @@ int upr_t_conv_mfma(const float* x, int B, int H, int W, int Cin, int x_cs, int 
   s.kh = kh; s.kw = kw; s.stride = stride; s.pad = pad; s.dil = dil; s.pre = kPreNone; s.kbase = 0;
   c.B = B; c.Ho = Ho; c.Wo = Wo; c.N = N; c.Kpad = kh * kw * Cin;
   c.W = wp; c.bias = bias; c.res1 = res; c.res1_cs = res_cs; c.relu = relu;
-  c.out = y; c.out_cs = y_cs; c.out_coff = y_coff; c.store = store == 1 ? kStoreConvT2x2 : kStoreNHWC;
+  c.out = y; c.out_cs = y_cs; c.out_coff = y_coff; c.store = store == UPR_T_STORE_CONVT2X2 ? kStoreConvT2x2 : kStoreNHWC;
   return launch_conv(c, kF32, ST(stream));
-}
-
-// ---- autocast (AMP) convs: fp16 operands, fp32 accumulate, fp32 activations ----
-// x[m][coff + c] (fp32, pixel stride cs) -> dense fp16 [m][C], 8 channels per thread
-__global__ __launch_bounds__(256) void cast_act_f16_kernel(const float* __restrict__ x, long long M, int C, int cs,
-                                                           int coff, half_t* __restrict__ y) {
-  const int C8 = C / 8;
-  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-  if (256 % C8 == 0) {  // fixed channels per thread, rows by addition (no 64-bit div per element)
-    const int c = (threadIdx.x % C8) * 8, rpb = 256 / C8;
-    for (long long m = (long long)blockIdx.x * rpb + threadIdx.x / C8; m < M; m += (long long)gridDim.x * rpb) {
-      const float4* src = (const float4*)(x + m * cs + coff + c);
-      const float4 a = src[0], b = src[1];
-      *(h8*)(y + m * C + c) =
-          h8{(half_t)a.x, (half_t)a.y, (half_t)a.z, (half_t)a.w, (half_t)b.x, (half_t)b.y, (half_t)b.z, (half_t)b.w};
-    }
-    return;
-  }
-  GSTRIDE(i, M * C8) {
-    const long long m = i / C8;
-    const int c = (int)(i - m * C8) * 8;
-    const float4* src = (const float4*)(x + m * cs + coff + c);
-    const float4 a = src[0], b = src[1];
-    h8 o = {(half_t)a.x, (half_t)a.y, (half_t)a.z, (half_t)a.w, (half_t)b.x, (half_t)b.y, (half_t)b.z, (half_t)b.w};
-    *(h8*)(y + m * C + c) = o;
-  }
-}
-// dense fp16 [m][C] -> y[m][coff + c] (fp32) (+ res[m * res_cs + c], fp32; res may alias y)
-__global__ __launch_bounds__(256) void cast_act_f32_kernel(const half_t* __restrict__ x, long long M, int C,
-                                                           const float* res, int res_cs, float* y, int cs, int coff,
-                                                           int xcs) {
-  const int C4 = C / 4;
-  GSTRIDE(i, M * C4) {
-    const long long m = i / C4;
-    const int c = (int)(i - m * C4) * 4;
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    const h4 v = *(const h4*)(x + m * xcs + c);
-    float4 o = make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-    if (res) {
-      const float4 r = *(const float4*)(res + m * res_cs + c);
-      o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
-    }
-    *(float4*)(y + m * cs + coff + c) = o;
-  }
-}
-__global__ __launch_bounds__(256) void cast_f16_kernel(const float* __restrict__ x, long long n, half_t* __restrict__ y) {
-  GSTRIDE(i, n) y[i] = (half_t)x[i];
 }
 
 int upr_t_cast_f16(const float* x, void* y, size_t n, void* stream) {
@@ -2738,33 +2893,31 @@ int upr_t_cast_f16(const float* x, void* y, size_t n, void* stream) {
   LAUNCH_CHECK();
 }
 
-// UPR_T_OUT32=0: fp16 conv output + separate fp32 cast pass (A/B timing)
-
 int upr_t_conv_mfma16(const float* x, int B, int H, int W, int Cin, int x_cs, int x_coff, const void* wp16,
                       const float* bias, int N, int kh, int kw, int stride, int pad, int dil, const float* res,
                       int res_cs, int relu, float* y, int y_cs, int y_coff, int store, void* x16, int x16_ready,
                       void* y16, int y16_cs, void* stream) {
   if (!x16 || !wp16 || !y || !y16 || B <= 0 || Cin % 32 || N % 32 || Cin <= 0 || N <= 0) return UPR_ERR_ARG;
   if (!x16_ready && !x) return UPR_ERR_ARG;
-  const bool want16 = (store & 2) != 0;  // y16 must end up holding (half)y
-  const bool only16 = want16 && (store & 4) != 0;  // y itself not needed (written only on the fallback path)
+  const bool want16 = (store & UPR_T_STORE_KEEP16) != 0;  // y16 must end up holding (half)y
+  const bool only16 = want16 && (store & UPR_T_STORE_ONLY16) != 0;  // y itself not needed (written only on the fallback path)
   // the 1x1 stride-2 conv's input gradient (y = 2H x 2W, accumulated into at the even pixels)
-  const bool s2 = (store & 8) != 0;
+  const bool s2 = (store & UPR_T_STORE_S2_1X1) != 0;
   // the 3x3 stride-2 pad-1 conv's input gradient from dy itself (x16 = dy over H x W, wp16 the
   // flipped filter, y = 2H x 2W); UPR_ERR_UNSUPPORTED when the kernel does not take the shape
-  const bool s2dg = (store & 16) != 0;
+  const bool s2dg = (store & UPR_T_STORE_S2_3X3_DGRAD) != 0;
   // the ready x16 keeps x's channel stride (a slice of a concat's fp16 copy)
-  const bool x16_strided = (store & 32) != 0;
-  store &= 1;
+  const bool x16_strided = (store & UPR_T_STORE_X16_STRIDED) != 0;
+  store &= UPR_T_STORE_CONVT2X2;
   if (x16_strided && (!x16_ready || x_cs % 8 || x_cs < Cin || (uintptr_t)x16 % 16)) return UPR_ERR_ARG;
   if (s2 && (kh != 1 || kw != 1 || stride != 1 || pad != 0 || dil != 1 || store != 0 || !res || relu)) return UPR_ERR_ARG;
   if (s2dg && (s2 || kh != 3 || kw != 3 || stride != 1 || dil != 1 || store != 0 || relu || bias)) return UPR_ERR_ARG;
-  const int ycs16 = y16_cs > 0 ? y16_cs : (store == 1 ? N / 4 : N);  // y16's channel stride
+  const int ycs16 = y16_cs > 0 ? y16_cs : (store == UPR_T_STORE_CONVT2X2 ? N / 4 : N);  // y16's channel stride
   if (ycs16 % 8 || ((uintptr_t)y16 & 15)) return UPR_ERR_ARG;
   if (kh <= 0 || kw <= 0 || stride <= 0 || dil <= 0 || pad < 0) return UPR_ERR_ARG;
   if (x_cs % 4 || x_coff % 4 || y_cs % 4 || y_coff % 4 || (res && res_cs % 4)) return UPR_ERR_ARG;
   if (res && relu) return UPR_ERR_ARG;  // the residual is added in fp32 after the fp16 GEMM
-  if (store == 1 && ((N / 4) % 32)) return UPR_ERR_SHAPE;
+  if (store == UPR_T_STORE_CONVT2X2 && ((N / 4) % 32)) return UPR_ERR_SHAPE;
   const int Ho = (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1;
   const int Wo = (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
   if (Ho <= 0 || Wo <= 0) return UPR_ERR_SHAPE;
@@ -2778,7 +2931,7 @@ int upr_t_conv_mfma16(const float* x, int B, int H, int W, int Cin, int x_cs, in
   s.kh = kh; s.kw = kw; s.stride = stride; s.pad = pad; s.dil = dil; s.pre = kPreNone; s.kbase = 0;
   c.B = B; c.Ho = Ho; c.Wo = Wo; c.N = N; c.Kpad = kh * kw * Cin;
   c.W = wp16; c.bias = bias; c.relu = relu;
-  c.store = store == 1 ? kStoreConvT2x2 : kStoreNHWC;
+  c.store = store == UPR_T_STORE_CONVT2X2 ? kStoreConvT2x2 : kStoreNHWC;
   // the fp32 output (+ fp32 residual / accumulated gradient) straight from the conv epilogue
   ConvOp c32 = c;
   c32.out32 = y; c32.out32_cs = y_cs; c32.out32_coff = y_coff;
@@ -2820,8 +2973,8 @@ int upr_t_conv_mfma16(const float* x, int B, int H, int W, int Cin, int x_cs, in
   c.out = y16; c.out_cs = ycs16; c.out_coff = 0;
   const int rc = launch_conv(c, kF16, st);
   if (rc != 0) return rc;
-  const long long Mo = store == 1 ? (long long)B * 4 * Ho * Wo : (long long)B * Ho * Wo;
-  const int Co = store == 1 ? N / 4 : N;
+  const long long Mo = store == UPR_T_STORE_CONVT2X2 ? (long long)B * 4 * Ho * Wo : (long long)B * Ho * Wo;
+  const int Co = store == UPR_T_STORE_CONVT2X2 ? N / 4 : N;
   hipLaunchKernelGGL(cast_act_f32_kernel, dim3(grid_for(Mo * (Co / 4))), dim3(256), 0, st, (const half_t*)y16, Mo, Co,
                      res, res_cs, y, y_cs, y_coff, ycs16);
   LAUNCH_CHECK();
@@ -3088,56 +3241,6 @@ int upr_t_bn_stats16(const void* x16, int M, int C, double* acc, void* stream) {
                       0, acc + 2 * C, acc, nullptr, 0, ST(stream));
 }
 
-// chan_fin (mode 0) and bn_finalize in one launch: a block owns 32 channels,
-// lanes 0-31 their sums and 32-63 their sums of squares (the same slot order
-// and partial-sum tree as chan_fin: bit-identical acc), then lanes 0-31
-// finalise their channel as bn_finalize_kernel does
-__global__ __launch_bounds__(256) void chan_fin_bn_kernel(const double* __restrict__ part, int slots, int C,
-                                                          double* __restrict__ acc, int M, float momentum, float eps,
-                                                          float* __restrict__ rm, float* __restrict__ rv,
-                                                          long long* nbt, float* __restrict__ mean,
-                                                          float* __restrict__ invstd) {
-  __shared__ double red[4][64];
-  __shared__ double fin[64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int c = blockIdx.x * 32 + (lane & 31);
-  const bool ok = c < C;
-  const int t = lane < 32 ? c : C + c;
-  double sum = 0.0;  // (chan_fin_kernel's order and batching)
-  if (ok) {
-    for (int k0 = w; k0 < slots; k0 += 64) {
-      double v[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const int k = k0 + 4 * u;
-        v[u] = k < slots ? part[(size_t)k * 2 * C + t] : 0.0;
-      }
-#pragma unroll
-      for (int u = 0; u < 16; ++u) sum += v[u];
-    }
-  }
-  red[w][lane] = sum;
-  __syncthreads();
-  if (w == 0) {
-    const double v = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
-    fin[lane] = v;
-    if (ok) acc[t] = v;
-  }
-  __syncthreads();
-  if (blockIdx.x == 0 && threadIdx.x == 0 && nbt) *nbt += 1;
-  if (w != 0 || lane >= 32 || !ok) return;
-  const double mu = fin[lane] / M;
-  double var = fin[lane + 32] / M - mu * mu;
-  if (var < 0) var = 0;
-  mean[c] = (float)mu;
-  invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-  if (rm) rm[c] = (1.f - momentum) * rm[c] + momentum * (float)mu;
-  if (rv) {
-    const double unb = M > 1 ? var * M / (M - 1) : var;
-    rv[c] = (1.f - momentum) * rv[c] + momentum * (float)unb;
-  }
-}
-
 int upr_t_bn_stats16_fin(const void* x16, int M, int C, double* acc, float momentum, float eps, float* running_mean,
                          float* running_var, int64_t* nbt, float* mean, float* invstd, void* stream) {
   if (!x16 || !acc || !mean || !invstd || M <= 0 || C <= 0) return UPR_ERR_ARG;
@@ -3340,234 +3443,6 @@ int upr_t_maxpool(const UprView* x, int B, int H, int W, int C, int k, int s, in
   return upr_t_maxpool_code(x, B, H, W, C, k, s, p, y, Ho, Wo, nullptr, nullptr, stream);
 }
 
-// Max-pool backward as two deterministic passes (the atomic scatter above --
-// up to k*k fp32 atomics per input element in arbitrary order -- stays behind
-// UPR_MAXPOOL_BWD_SCATTER=1 for A/B timing):
-//  1. per output element the window position of its max, PyTorch's rule
-//     (max_pool2d CPU kernel: the first in-bounds tap, then every tap with
-//     v > max or v NaN), as a byte code ky * k + kx;
-//  2. per input element, in output order, the dy of every window whose code
-//     points at it, added to dx.
-extern "C++" {
-template <int VEC>
-__global__ void maxpool_arg_kernel(V x, int B, int H, int W, int C, int k, int s, int p, int Ho, int Wo,
-                                   unsigned char* __restrict__ code) {
-  const int CV = C / VEC;
-  const long long n = (long long)B * Ho * Wo * CV;
-  GSTRIDE(i, n) {
-    const int c = (int)(i % CV) * VEC;
-    long long r = i / CV;
-    const int ox = (int)(r % Wo); r /= Wo;
-    const int oy = (int)(r % Ho);
-    const int b = (int)(r / Ho);
-    float m[VEC];
-    int best[VEC];
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) { m[v] = -INFINITY; best[v] = -1; }
-    for (int ky = 0; ky < k; ++ky) {
-      const int iy = oy * s - p + ky;
-      if (iy < 0 || iy >= H) continue;
-      for (int kx = 0; kx < k; ++kx) {
-        const int ix = ox * s - p + kx;
-        if (ix < 0 || ix >= W) continue;
-        float val[VEC];
-        if constexpr (VEC == 4) {
-          const float4 q = *(const float4*)(x.d + x.at(b, iy, ix, c));
-          val[0] = q.x; val[1] = q.y; val[2] = q.z; val[3] = q.w;
-        } else {
-          val[0] = x.d[x.at(b, iy, ix, c)];
-        }
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) {
-          if (best[v] < 0) best[v] = ky * k + kx;  // the first in-bounds tap is the default index
-          if (val[v] > m[v] || isnan(val[v])) {
-            m[v] = val[v];
-            best[v] = ky * k + kx;
-          }
-        }
-      }
-    }
-    unsigned char* o = code + (((long long)b * Ho + oy) * Wo + ox) * C + c;
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) o[v] = (unsigned char)(best[v] < 0 ? 255 : best[v]);
-  }
-}
-
-template <int VEC>
-__global__ void maxpool_bwd_gather_kernel(const unsigned char* __restrict__ code, V dy, int B, int H, int W, int C, int k,
-                                          int s, int p, int Ho, int Wo, V dx) {
-  const int CV = C / VEC;
-  const long long n = (long long)B * H * W * CV;
-  GSTRIDE(i, n) {
-    const int c = (int)(i % CV) * VEC;
-    long long r = i / CV;
-    const int ix = (int)(r % W); r /= W;
-    const int iy = (int)(r % H);
-    const int b = (int)(r / H);
-    float* dp = dx.d + dx.at(b, iy, ix, c);
-    float acc[VEC];
-    if constexpr (VEC == 4) {
-      const float4 q = *(const float4*)dp;
-      acc[0] = q.x; acc[1] = q.y; acc[2] = q.z; acc[3] = q.w;
-    } else {
-      acc[0] = *dp;
-    }
-    // windows containing (iy, ix): oy*s - p <= iy <= oy*s - p + k - 1
-    const int oy0 = max(0, (iy + p - k + 1 + s - 1 + s * k) / s - k), oy1 = min(Ho - 1, (iy + p) / s);
-    const int ox0 = max(0, (ix + p - k + 1 + s - 1 + s * k) / s - k), ox1 = min(Wo - 1, (ix + p) / s);
-    for (int oy = oy0; oy <= oy1; ++oy) {
-      const int ty = iy - (oy * s - p);
-      if (ty < 0 || ty >= k) continue;
-      for (int ox = ox0; ox <= ox1; ++ox) {
-        const int tx = ix - (ox * s - p);
-        if (tx < 0 || tx >= k) continue;
-        const unsigned char want = (unsigned char)(ty * k + tx);
-        const unsigned char* cd = code + (((long long)b * Ho + oy) * Wo + ox) * C + c;
-        const float* g = dy.d + dy.at(b, oy, ox, c);
-#pragma unroll
-        for (int v = 0; v < VEC; ++v)
-          if (cd[v] == want) acc[v] += g[v * dy.sc];
-      }
-    }
-    if constexpr (VEC == 4) {
-      *(float4*)dp = make_float4(acc[0], acc[1], acc[2], acc[3]);
-    } else {
-      *dp = acc[0];
-    }
-  }
-}
-
-// Fast paths for the two pools of the training step -- EnhancedFAM's 3x3/1/1
-// (models/model.py:32) and the VGG 2x2/2 (losses/loss.py perceptual
-// features[4], [9], [18]) -- on channel-contiguous views: 4 channels per
-// thread, 32-bit index math (the generic kernels' 64-bit div/mod per element
-// ran at <1 TB/s), compile-time windows.  The forward optionally writes the
-// argmax byte codes (PyTorch's rule, as maxpool_arg_kernel) so the backward
-// is the gather alone.
-// TI = half_t: the input is an activation's compact fp16 copy (the autocast
-// VGG activations live in fp16 only, as the reference's under autocast)
-template <int K, int S, int P, typename TI = float>
-__global__ __launch_bounds__(256) void maxpool4_kernel(const TI* __restrict__ x, int xsb, int xsh, int xsw, int H,
-                                                       int W, int CV, int Ho, int Wo, int n, float* __restrict__ y,
-                                                       int ysb, int ysh, int ysw, unsigned* __restrict__ code,
-                                                       half_t* __restrict__ y16) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int c = (i % CV) * 4;
-  int r = i / CV;
-  const int ox = r % Wo;
-  r /= Wo;
-  const int oy = r % Ho, b = r / Ho;
-  float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-  int best[4] = {-1, -1, -1, -1};
-  const TI* xb = x + b * xsb + c;
-#pragma unroll
-  for (int ky = 0; ky < K; ++ky) {
-    const int iy = oy * S - P + ky;
-    if ((unsigned)iy >= (unsigned)H) continue;
-#pragma unroll
-    for (int kx = 0; kx < K; ++kx) {
-      const int ix = ox * S - P + kx;
-      if ((unsigned)ix >= (unsigned)W) continue;
-      const float4 q = ld4f(xb + iy * xsh + ix * xsw);
-      const float val[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        if (best[v] < 0) best[v] = ky * K + kx;
-        if (val[v] > m[v] || isnan(val[v])) {
-          m[v] = val[v];
-          best[v] = ky * K + kx;
-        }
-      }
-    }
-  }
-  if (y) *(float4*)(y + b * ysb + oy * ysh + ox * ysw + c) = make_float4(m[0], m[1], m[2], m[3]);
-  if (y16) {  // compact [b][oy][ox][C] fp16 copy: element index 4 i
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    *(h4*)(y16 + (size_t)i * 4) = h4{(half_t)m[0], (half_t)m[1], (half_t)m[2], (half_t)m[3]};
-  }
-  if (code) {
-    unsigned w = 0;
-#pragma unroll
-    for (int v = 0; v < 4; ++v) w |= (unsigned)(best[v] < 0 ? 255 : best[v]) << (8 * v);
-    code[i] = w;
-  }
-}
-
-// dx[b][iy][ix][c..c+3] += dy of every window (ascending oy, then ox: the
-// generic gather's order) whose code points at (iy, ix).  O16: the result
-// goes to the compact fp16 g16 instead (element 4 i), masked by the producing
-// ReLU's fp16 output y16 when given -- the frozen VGG's pool backward, whose
-// only reader is the masked fp16 dgrad operand (relu_mask16h fused away)
-template <int K, int S, int P, int O16 = 0>
-__global__ __launch_bounds__(256) void maxpool_gather4_kernel(const unsigned* __restrict__ code,
-                                                              const float* __restrict__ dy, int dsb, int dsh, int dsw,
-                                                              int H, int W, int CV, int Ho, int Wo, int n,
-                                                              float* __restrict__ dx, int xsb, int xsh, int xsw,
-                                                              int accumulate, const half_t* __restrict__ y16 = nullptr,
-                                                              half_t* __restrict__ g16 = nullptr) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int cv = i % CV, c = cv * 4;
-  int r = i / CV;
-  const int ix = r % W;
-  r /= W;
-  const int iy = r % H, b = r / H;
-  float* dp = O16 ? nullptr : dx + b * xsb + iy * xsh + ix * xsw + c;
-  float4 acc = !O16 && accumulate ? *(const float4*)dp : make_float4(0.f, 0.f, 0.f, 0.f);
-  // every window's code word and gradient run is loaded first (independent
-  // loads, one round trip each; a window outside the output reads nothing and
-  // gets the no-hit code 0xffffffff), then the hits are added in the same
-  // window order as before (the 3x3 pool's code -> dy -> next window chain
-  // was 18 dependent round trips per thread: 1.6 TB/s at 512^2)
-  unsigned wv[K * K];
-  float4 gv[K * K];
-#pragma unroll
-  for (int t = 0; t < K; ++t) {
-    const int ky = K - 1 - t, ny = iy + P - ky;  // oy * S
-    const bool oky = ny >= 0 && ny % S == 0 && ny / S < Ho;
-    const int oy = oky ? ny / S : 0;
-#pragma unroll
-    for (int u = 0; u < K; ++u) {
-      const int kx = K - 1 - u, nx = ix + P - kx;
-      const bool ok = oky && nx >= 0 && nx % S == 0 && nx / S < Wo;
-      const int ox = ok ? nx / S : 0;
-      wv[t * K + u] = ok ? code[((b * Ho + oy) * Wo + ox) * CV + cv] : 0xffffffffu;
-      gv[t * K + u] = ok ? *(const float4*)(dy + b * dsb + oy * dsh + ox * dsw + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < K; ++t) {
-    const int ky = K - 1 - t;
-#pragma unroll
-    for (int u = 0; u < K; ++u) {
-      const int kx = K - 1 - u;
-      const unsigned want = (unsigned)(ky * K + kx) * 0x01010101u;
-      const unsigned hit = wv[t * K + u] ^ want;  // a zero byte marks a window whose max sits here
-      const float4 g = gv[t * K + u];
-      if ((hit & 0xffu) == 0) acc.x += g.x;
-      if ((hit & 0xff00u) == 0) acc.y += g.y;
-      if ((hit & 0xff0000u) == 0) acc.z += g.z;
-      if ((hit & 0xff000000u) == 0) acc.w += g.w;
-    }
-  }
-  if (O16) {
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    if (y16) {
-      const h4 y = *(const h4*)(y16 + (size_t)i * 4);
-      if (!(y[0] > (half_t)0)) acc.x = 0.f;
-      if (!(y[1] > (half_t)0)) acc.y = 0.f;
-      if (!(y[2] > (half_t)0)) acc.z = 0.f;
-      if (!(y[3] > (half_t)0)) acc.w = 0.f;
-    }
-    *(h4*)(g16 + (size_t)i * 4) = h4{(half_t)acc.x, (half_t)acc.y, (half_t)acc.z, (half_t)acc.w};
-    return;
-  }
-  *(float4*)dp = acc;
-}
-
-}  // extern "C++"
-
 int upr_t_maxpool_bwd(const UprView* x, const UprView* dy, int B, int H, int W, int C, int k, int s, int p, int Ho,
                       int Wo, const UprView* dx, void* stream) {
   if (!x || !dy || !dx || k <= 0 || s <= 0 || k * k > 255) return UPR_ERR_ARG;
@@ -3593,25 +3468,6 @@ int upr_t_maxpool_bwd(const UprView* x, const UprView* dy, int B, int H, int W, 
   }
   UPR_CHECK_HIP(hipGetLastError());
   return UPR_OK;
-}
-
-__global__ void zero_view_kernel(V v, int B, int H, int W, int C) {
-  const long long n = (long long)B * H * W * C;
-  GSTRIDE(i, n) {
-    const int c = (int)(i % C);
-    long long r = i / C;
-    const int x = (int)(r % W);
-    r /= W;
-    v.d[v.at((int)(r / H), (int)(r % H), x, c)] = 0.f;
-  }
-}
-
-// shape of a fast-path pool: (k, s, p) one of the two instantiated windows,
-// channel-contiguous 16-byte aligned views whose extents fit 32-bit offsets
-static int pool_fast_kind(int k, int s, int p) {
-  if (k == 3 && s == 1 && p == 1) return 1;
-  if (k == 2 && s == 2 && p == 0) return 2;
-  return 0;
 }
 
 int upr_t_maxpool_code(const UprView* x, int B, int H, int W, int C, int k, int s, int p, const UprView* y, int Ho,
@@ -3778,18 +3634,6 @@ int upr_t_bilinear16(const UprView* x, int B, int H, int W, int C, const UprView
   hipLaunchKernelGGL(bilinear4_kernel, dim3((nv + 255) / 256), dim3(256), 0, ST(stream), mkv4(x), H, W, C / 4, mkv4(y),
                      Ho, Wo, (float)H / Ho, (float)W / Wo, nv, accumulate, (half_t*)y16, y16_cs);
   LAUNCH_CHECK();
-}
-
-// out = a + b with its fp16 copy (a residual / skip sum feeding an autocast conv)
-__global__ __launch_bounds__(256) void add16_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                    float* __restrict__ out, half_t* __restrict__ out16, int n4) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  const float4 u = ((const float4*)a)[i], v = ((const float4*)b)[i];
-  const float4 r = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
-  ((float4*)out)[i] = r;
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-  ((h4*)out16)[i] = h4{(half_t)r.x, (half_t)r.y, (half_t)r.z, (half_t)r.w};
 }
 
 int upr_t_add16(const float* a, const float* b, float* out, size_t n, void* out16, void* stream) {
@@ -3968,8 +3812,6 @@ int upr_t_enhance_bwd(const float* e, const float* refl, const float* g_enh, flo
   LAUNCH_CHECK();
 }
 
-static const UprLossParams kLossDefaults = {16, 0.6f, 10.f, 1.f, 0.1f, 1.f, 0.5f, 1, 1};
-
 size_t upr_t_loss_workspace(int B, int H, int W) { return upr_t_loss_workspace_p(B, H, W, 16); }
 
 size_t upr_t_loss_workspace_p(int B, int H, int W, int patch) {
@@ -4063,28 +3905,6 @@ int upr_t_loss_total(float* terms, float w_exp, float w_col, float w_spa, float 
   hipLaunchKernelGGL(loss_total_kernel, dim3(1), dim3(64), 0, ST(stream), terms, w_exp, w_col, w_spa, w_dec, w_per,
                      w_freq);
   LAUNCH_CHECK();
-}
-
-// the same over two fp16 tensors (the frozen VGG's features under autocast,
-// which exist in fp16 only: the reference's mse_loss promotes them to fp32),
-// 4 elements per thread
-__global__ __launch_bounds__(256) void mse16_kernel(const half_t* __restrict__ a, const half_t* __restrict__ b,
-                                                    long long n4, long long n, double* acc, float* g, float scale) {
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-  double v[1] = {0.0};
-  GSTRIDE(i, n4) {
-    const h4 x = *(const h4*)(a + 4 * i), y = *(const h4*)(b + 4 * i);
-    float d[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      d[k] = (float)x[k] - (float)y[k];
-      v[0] += (double)d[k] * d[k];
-    }
-    if (g) *(float4*)(g + 4 * i) = make_float4(scale * 2.f * d[0], scale * 2.f * d[1], scale * 2.f * d[2], scale * 2.f * d[3]);
-  }
-  v[0] /= (double)n;
-  double* dst[1] = {acc};
-  block_sum_atomic<1>(v, dst);
 }
 
 int upr_t_mse16(const void* a16, const void* b16, size_t n, double* acc, float* g, float scale, void* stream) {

@@ -23,29 +23,9 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "upr_common.h"
-#include "../../include/upr.h"
-#include "../../include/upr_train.h"
+#include "train_common.h"
 
 namespace upr {
-
-typedef float f32x4_t2 __attribute__((ext_vector_type(4)));
-typedef float f32x16_t2 __attribute__((ext_vector_type(16)));
-
-struct SV {
-  float* d;
-  long long sb, sh, sw, sc;
-  __device__ __forceinline__ long long at(int b, int y, int x, int c) const {
-    return b * sb + y * sh + x * sw + c * sc;
-  }
-};
-
-static SV mksv(const UprView* u) {
-  SV v;
-  v.d = (float*)u->data;
-  v.sb = u->sb; v.sh = u->sh; v.sw = u->sw; v.sc = u->sc;
-  return v;
-}
 
 // ---------------------------------------------------------------------------
 // forward: 3 -> COUT (32 / 64), 3x3, stride 1, dilation 1, on fp32 MFMA
@@ -60,8 +40,8 @@ static SV mksv(const UprView* u) {
 // 16-byte fp32 / 8-byte fp16 stores from registers.
 // ---------------------------------------------------------------------------
 template <int COUT>
-__global__ __launch_bounds__(256) void c3k3_mfma_kernel(SV x, int B, int H, int W, const float* __restrict__ w,
-                                                       const float* __restrict__ bias, int p, SV y, int Ho, int Wo,
+__global__ __launch_bounds__(256) void c3k3_mfma_kernel(V x, int B, int H, int W, const float* __restrict__ w,
+                                                       const float* __restrict__ bias, int p, V y, int Ho, int Wo,
                                                        int relu, int accum, half_t* __restrict__ y16, int skip32) {
   constexpr int NT = COUT / 16;
   const int lane = threadIdx.x & 63;
@@ -74,7 +54,7 @@ __global__ __launch_bounds__(256) void c3k3_mfma_kernel(SV x, int B, int H, int 
       const int k = kg + 4 * st;
       wa[t][st] = k < 27 ? w[(t * 16 + fr) * 27 + k] : 0.f;
     }
-  f32x4_t2 bv[NT];
+  f32x4 bv[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -115,7 +95,7 @@ __global__ __launch_bounds__(256) void c3k3_mfma_kernel(SV x, int B, int H, int 
     const bool pok = npok;
     const long long pix = g * 16 + fr;
     gather(g + gstride, xn, nb, noy, nox, npok);
-    f32x4_t2 acc[NT];
+    f32x4 acc[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       acc[t] = bv[t];
@@ -126,8 +106,8 @@ __global__ __launch_bounds__(256) void c3k3_mfma_kernel(SV x, int B, int H, int 
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const int co = t * 16 + kg * 4;
-      f32x4_t2 v = acc[t];
-      f32x4_t2* dst = (f32x4_t2*)(y.d + y.at(b, oy, ox, co));
+      f32x4 v = acc[t];
+      f32x4* dst = (f32x4*)(y.d + y.at(b, oy, ox, co));
       if (accum) v += *dst;
       if (relu) {
         v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
@@ -147,9 +127,9 @@ __global__ __launch_bounds__(256) void c3k3_mfma_kernel(SV x, int B, int H, int 
 // (16-byte loads when the input rows are channel-contiguous and aligned)
 // ---------------------------------------------------------------------------
 template <int COUT>
-__global__ __launch_bounds__(256) void small_fwd_kernel(SV x, int B, int H, int W, int Cin,
+__global__ __launch_bounds__(256) void small_fwd_kernel(V x, int B, int H, int W, int Cin,
                                                         const float* __restrict__ w, const float* __restrict__ bias,
-                                                        int kh, int kw, int s, int p, int d, SV y, int Ho, int Wo,
+                                                        int kh, int kw, int s, int p, int d, V y, int Ho, int Wo,
                                                         int relu, int accum, int xvec) {
   extern __shared__ __attribute__((aligned(16))) float smf[];  // [tap][ci][COUT]
   const int taps = kh * kw;
@@ -181,7 +161,7 @@ __global__ __launch_bounds__(256) void small_fwd_kernel(SV x, int B, int H, int 
       int ci = 0;
       if (xvec) {
         for (; ci + 4 <= Cin; ci += 4) {
-          const f32x4_t2 v = *(const f32x4_t2*)(xp + ci);
+          const f32x4 v = *(const f32x4*)(xp + ci);
 #pragma unroll
           for (int e = 0; e < 4; ++e)
 #pragma unroll
@@ -215,8 +195,8 @@ __global__ __launch_bounds__(256) void small_fwd_kernel(SV x, int B, int H, int 
 // them with xor shuffles.
 // ---------------------------------------------------------------------------
 template <int COUT, int LPP>
-__global__ __launch_bounds__(256) void head1x1_kernel(SV x, int P, int Ho, int Wo, const float* __restrict__ w,
-                                                      const float* __restrict__ bias, SV y, int relu, int accum) {
+__global__ __launch_bounds__(256) void head1x1_kernel(V x, int P, int Ho, int Wo, const float* __restrict__ w,
+                                                      const float* __restrict__ bias, V y, int relu, int accum) {
   const int lane = threadIdx.x & 63;
   const long long gw = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int q = lane % LPP;
@@ -231,13 +211,13 @@ __global__ __launch_bounds__(256) void head1x1_kernel(SV x, int P, int Ho, int W
     const long long pix = gw * 64 + (j * 64 + lane) / LPP;
     const bool in = pix < P;
     int b = 0, oy = 0, ox = 0;
-    f32x4_t2 v = f32x4_t2{0.f, 0.f, 0.f, 0.f};
+    f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
     if (in) {
       ox = (int)(pix % Wo);
       const long long r = pix / Wo;
       oy = (int)(r % Ho);
       b = (int)(r / Ho);
-      v = *(const f32x4_t2*)(x.d + x.at(b, oy, ox, q * 4));
+      v = *(const f32x4*)(x.d + x.at(b, oy, ox, q * 4));
     }
     float part[COUT];
 #pragma unroll
@@ -267,8 +247,8 @@ __global__ __launch_bounds__(256) void head1x1_kernel(SV x, int P, int Ho, int W
 // input gradient, stride 1: dx[b,iy,ix,ci] (+)= sum_{ky,kx,co} dy[b,iy+p-ky*d,ix+p-kx*d,co] w[co][ci][ky][kx]
 // ---------------------------------------------------------------------------
 template <int CIN, int COUTT>
-__global__ __launch_bounds__(256) void small_dgrad_kernel(SV dy, int Ho, int Wo, const float* __restrict__ w, int B,
-                                                          int H, int W, int Cout, int kh, int kw, int p, int d, SV dx,
+__global__ __launch_bounds__(256) void small_dgrad_kernel(V dy, int Ho, int Wo, const float* __restrict__ w, int B,
+                                                          int H, int W, int Cout, int kh, int kw, int p, int d, V dx,
                                                           int accum, int vec, int dvec) {
   extern __shared__ __attribute__((aligned(16))) float smd[];  // [tap][co][CIN]
   const int taps = kh * kw;
@@ -299,9 +279,9 @@ __global__ __launch_bounds__(256) void small_dgrad_kernel(SV dy, int Ho, int Wo,
       const float* wt = smd + (ky * kw + kx) * Cout * CIN;
       int co = 0;
       if (COUTT > 0 && dvec) {  // compile-time Cout: the tap's loads all in flight, then the FMAs
-        f32x4_t2 g4[COUTT > 0 ? COUTT / 4 : 1];
+        f32x4 g4[COUTT > 0 ? COUTT / 4 : 1];
 #pragma unroll
-        for (int q = 0; q < COUTT / 4; ++q) g4[q] = *(const f32x4_t2*)(dyp + 4 * q);
+        for (int q = 0; q < COUTT / 4; ++q) g4[q] = *(const f32x4*)(dyp + 4 * q);
 #pragma unroll
         for (int q = 0; q < COUTT / 4; ++q)
 #pragma unroll
@@ -312,7 +292,7 @@ __global__ __launch_bounds__(256) void small_dgrad_kernel(SV dy, int Ho, int Wo,
       }
       if (dvec) {  // channel-contiguous, 16-byte aligned dy rows: 4 channels per load
         for (; co + 4 <= Cout; co += 4) {
-          const f32x4_t2 g4 = *(const f32x4_t2*)(dyp + co);
+          const f32x4 g4 = *(const f32x4*)(dyp + co);
           const float* wc = wt + co * CIN;
 #pragma unroll
           for (int q = 0; q < 4; ++q)
@@ -332,9 +312,9 @@ __global__ __launch_bounds__(256) void small_dgrad_kernel(SV dy, int Ho, int Wo,
   if (CIN % 4 == 0 && vec) {  // channel-contiguous, 16-byte aligned rows (host-checked)
 #pragma unroll
     for (int c = 0; c < CIN; c += 4) {
-      f32x4_t2 v = f32x4_t2{acc[c], acc[c + 1], acc[c + 2], acc[c + 3]};
-      if (accum) v += *(const f32x4_t2*)(xp + c);
-      *(f32x4_t2*)(xp + c) = v;
+      f32x4 v = f32x4{acc[c], acc[c + 1], acc[c + 2], acc[c + 3]};
+      if (accum) v += *(const f32x4*)(xp + c);
+      *(f32x4*)(xp + c) = v;
     }
   } else {
 #pragma unroll
@@ -355,9 +335,9 @@ template <int NT>
 constexpr int sw_unroll() { return NT == 2 ? 16 : 8; }
 
 template <int NT>
-__global__ __launch_bounds__(256) void small_wgrad_mfma_kernel(SV x, SV dy, int B, int H, int W, int Cin, int Ho,
+__global__ __launch_bounds__(256) void small_wgrad_mfma_kernel(V x, V dy, int B, int H, int W, int Cin, int Ho,
                                                                int Wo, int Cout, int kh, int kw, int s, int p, int d,
-                                                               int pairs_per_wave, float* __restrict__ part, SV ym) {
+                                                               int pairs_per_wave, float* __restrict__ part, V ym) {
   // ym.d != nullptr: dy masked by ym > 0 on the fly (the producing ReLU's
   // backward, for a gradient whose only reader is this weight gradient)
   __shared__ __attribute__((aligned(16))) float red[4][NT][16][64];
@@ -383,7 +363,7 @@ __global__ __launch_bounds__(256) void small_wgrad_mfma_kernel(SV x, SV dy, int 
       c_kind[t] = 2;
     }
   }
-  f32x16_t2 acc[NT];
+  f32x16 acc[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -489,7 +469,7 @@ __global__ __launch_bounds__(256) void small_wgrad_fin_kernel(const float* __res
 // ---------------------------------------------------------------------------
 template <int COUT>
 __global__ __launch_bounds__(256) void dgrad_c3_mfma_kernel(const half_t* __restrict__ dy, int B, int H, int W,
-                                                            const float* __restrict__ w, SV dx, int accum) {
+                                                            const float* __restrict__ w, V dx, int accum) {
   typedef _Float16 h8 __attribute__((ext_vector_type(8)));
   typedef float f4 __attribute__((ext_vector_type(4)));
   constexpr int KC = COUT / 32, CH = COUT / 8;  // 32-channel k chunks, 16-byte chunks per pixel
@@ -584,7 +564,7 @@ int small_conv_dgrad_c3_16(const void* dy16, int B, int H, int W, const float* w
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   // resident blocks per CU: 50 KB of LDS each, and (Cout 64) ~248 VGPRs with the prefetch registers
   const int grid = (int)std::min<long long>(ntiles, (long long)cus * (Cout == 64 ? 2 : 3));
-  const SV dx = mksv(dxv);
+  const V dx = mkv(dxv);
   if (Cout == 64)
     hipLaunchKernelGGL(dgrad_c3_mfma_kernel<64>, dim3(grid), dim3(256), 0, st, (const half_t*)dy16, B, H, W, w, dx,
                        accumulate);
@@ -607,7 +587,7 @@ int small_conv_fwd(const UprView* xv, int B, int H, int W, int Cin, const float*
     if ((long long)B * Ho * Wo >= (1ll << 31)) return kErrUnsupported;
     const size_t lds = sizeof(float) * (size_t)Cout * Cin * kh * kw;
     if (lds > 48 * 1024) return kErrUnsupported;
-    const SV x = mksv(xv), y = mksv(yv);
+    const V x = mkv(xv), y = mkv(yv);
     const int xvec = x.sc == 1 && x.sw % 4 == 0 && x.sh % 4 == 0 && x.sb % 4 == 0 && (uintptr_t)x.d % 16 == 0;
     if (xvec && kh == 1 && kw == 1 && stride == 1 && pad == 0 && (Cin == 16 || Cin == 32 || Cin == 64)) {
       const int P = B * Ho * Wo;
@@ -643,7 +623,7 @@ int small_conv_fwd(const UprView* xv, int B, int H, int W, int Cin, const float*
   if (Cout != 32 && Cout != 64) return kErrUnsupported;
   if (yv->sc != 1 || yv->sw % 4 || yv->sh % 4 || yv->sb % 4 || ((uintptr_t)yv->data % 16)) return kErrUnsupported;
   if ((long long)B * Ho * Wo >= (1ll << 31)) return kErrUnsupported;
-  const SV x = mksv(xv), y = mksv(yv);
+  const V x = mkv(xv), y = mkv(yv);
   const int P = B * Ho * Wo;
   {
     // fp32 MFMA form (16-pixel groups, filter in registers); grid sized for ~8 waves per SIMD
@@ -667,7 +647,7 @@ int small_conv_dgrad(const UprView* dyv, int Ho, int Wo, const float* w, int B, 
   if ((long long)B * H * W >= (1ll << 31)) return kErrUnsupported;
   const size_t lds = sizeof(float) * (size_t)Cout * kh * kw * Cin;
   if (lds > 64 * 1024) return kErrUnsupported;
-  const SV dy = mksv(dyv), dx = mksv(dxv);
+  const V dy = mkv(dyv), dx = mkv(dxv);
   const int grid = (B * H * W + 255) / 256;
   const int vec = dx.sc == 1 && dx.sw % 4 == 0 && dx.sh % 4 == 0 && dx.sb % 4 == 0 && (uintptr_t)dx.d % 16 == 0;
   const int dvec = dy.sc == 1 && dy.sw % 4 == 0 && dy.sh % 4 == 0 && dy.sb % 4 == 0 && (uintptr_t)dy.d % 16 == 0;
@@ -701,7 +681,7 @@ int small_conv_dgrad(const UprView* dyv, int Ho, int Wo, const float* w, int B, 
 // ---------------------------------------------------------------------------
 constexpr int SA_TR = 8, SA_TC = 64, SA_K = 7, SA_P = 3;
 
-__global__ __launch_bounds__(256) void sa_wgrad_kernel(SV x, SV dy, int B, int H, int W, int tiles_x, int tiles_y,
+__global__ __launch_bounds__(256) void sa_wgrad_kernel(V x, V dy, int B, int H, int W, int tiles_x, int tiles_y,
                                                        float* __restrict__ part) {
   constexpr int LR = SA_TR + SA_K - 1, LC = SA_TC + SA_K - 1;
   __shared__ float xs[2][LR][LC + 1];
@@ -759,7 +739,7 @@ __global__ __launch_bounds__(256) void sa_wgrad_kernel(SV x, SV dy, int B, int H
 // block owns 4 image rows, reduces per entry over its waves (shuffles, then 4
 // wave partials in order) into part[block][co * (Cin + 1) + k].
 template <int CIN, int COUT>
-__global__ __launch_bounds__(256) void pw_wgrad_kernel(SV x, SV dy, int B, int H, int W, int rows_per_block,
+__global__ __launch_bounds__(256) void pw_wgrad_kernel(V x, V dy, int B, int H, int W, int rows_per_block,
                                                        float* __restrict__ part) {
   constexpr int NE = COUT * (CIN + 1);
   __shared__ float wred[4][NE];
@@ -780,7 +760,7 @@ __global__ __launch_bounds__(256) void pw_wgrad_kernel(SV x, SV dy, int B, int H
       float xv[CIN];
 #pragma unroll
       for (int c = 0; c < CIN; c += 4) {
-        const f32x4_t2 q = *(const f32x4_t2*)(xp + c);
+        const f32x4 q = *(const f32x4*)(xp + c);
         xv[c] = q[0]; xv[c + 1] = q[1]; xv[c + 2] = q[2]; xv[c + 3] = q[3];
       }
 #pragma unroll
@@ -818,7 +798,7 @@ __global__ __launch_bounds__(256) void pw_wgrad_kernel(SV x, SV dy, int B, int H
 // The generic small_wgrad_mfma_kernel gathered every operand with 4-byte loads
 // (0.32 ms per stem at bs 8 512^2, the mask read included).
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void stem_wgrad_relu_kernel(SV x, const float* __restrict__ dy,
+__global__ __launch_bounds__(256) void stem_wgrad_relu_kernel(V x, const float* __restrict__ dy,
                                                               const half_t* __restrict__ y16, int B, int H, int W,
                                                               float* __restrict__ part) {
   constexpr int TR = 4, TC = 64, CO = 32, KC = 27;
@@ -828,7 +808,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_relu_kernel(SV x, const float*
   const int n = lane & 31, kk = lane >> 5;
   // this lane's im2col column n: input channel and tap offsets into the patch
   const int ci = n < KC ? n / 9 : 0, tap = n < KC ? n % 9 : 0, ky = tap / 3, kx = tap % 3;
-  f32x16_t2 acc;
+  f32x16 acc;
 #pragma unroll
   for (int e = 0; e < 16; ++e) acc[e] = 0.f;
   const int ntx = (W + TC - 1) / TC, nty = (H + TR - 1) / TR, ntiles = ntx * nty * B;
@@ -840,17 +820,17 @@ __global__ __launch_bounds__(256) void stem_wgrad_relu_kernel(SV x, const float*
     for (int j = 0; j < (TR * TC * CO / 4) / 256; ++j) {
       const int q = tid + j * 256, px = q >> 3, c4 = (q & 7) * 4;
       const int iy = iy0 + px / TC, ix = ix0 + px % TC;
-      f32x4_t2 v = f32x4_t2{0.f, 0.f, 0.f, 0.f};
+      f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
       if (iy < H && ix < W) {
         const size_t pix = ((size_t)b * H + iy) * W + ix;
-        v = *(const f32x4_t2*)(dy + pix * CO + c4);
+        v = *(const f32x4*)(dy + pix * CO + c4);
         typedef _Float16 h4 __attribute__((ext_vector_type(4)));
         const h4 m = *(const h4*)(y16 + pix * CO + c4);
 #pragma unroll
         for (int e = 0; e < 4; ++e)
           if (!(m[e] > (half_t)0)) v[e] = 0.f;
       }
-      *(f32x4_t2*)&dyl[px][c4] = v;
+      *(f32x4*)&dyl[px][c4] = v;
     }
     for (int q = tid; q < 3 * (TR + 2) * (TC + 2); q += 256) {
       const int c = q / ((TR + 2) * (TC + 2)), r = (q / (TC + 2)) % (TR + 2), col = q % (TC + 2);
@@ -892,7 +872,7 @@ int small_stem_wgrad_relu16(const UprView* xv, const float* dy, const void* y16,
   constexpr int NE = 32 * 28;
   float* part = (float*)scratch(kSlotPart, sizeof(float) * (size_t)grid * NE, st);
   if (!part) return (int)hipErrorOutOfMemory;
-  hipLaunchKernelGGL(stem_wgrad_relu_kernel, dim3(grid), dim3(256), 0, st, mksv(xv), dy, (const half_t*)y16, B, H, W,
+  hipLaunchKernelGGL(stem_wgrad_relu_kernel, dim3(grid), dim3(256), 0, st, mkv(xv), dy, (const half_t*)y16, B, H, W,
                      part);
   hipLaunchKernelGGL(small_wgrad_fin_kernel, dim3(NE), dim3(256), 0, st, (const float*)part, grid, 32, 27, dw, dbias);
   return (int)hipGetLastError();
@@ -902,10 +882,10 @@ int small_conv_wgrad(const UprView* xv, const UprView* dyv, int B, int H, int W,
                      int kh, int kw, int stride, int pad, int dil, float* dw, float* dbias, hipStream_t st,
                      const UprView* ymask) {
   if (Cout > 32) return kErrUnsupported;
-  SV ym{};
-  if (ymask) ym = mksv(ymask);
+  V ym{};
+  if (ymask) ym = mkv(ymask);
   if (!ymask) {
-    const SV x = mksv(xv), dy = mksv(dyv);
+    const V x = mkv(xv), dy = mkv(dyv);
     // the 7x7 spatial-attention conv: LDS-tiled dot products
     if (Cin == 2 && Cout == 1 && kh == SA_K && kw == SA_K && stride == 1 && dil == 1 && pad == SA_P && dbias &&
         Ho == H && Wo == W) {
@@ -949,7 +929,7 @@ int small_conv_wgrad(const UprView* xv, const UprView* dyv, int B, int H, int W,
   if (ppw < unroll) ppw = unroll;
   const long long waves = (pairs + ppw - 1) / ppw;
   const int grid = (int)((waves + 3) / 4);
-  const SV x = mksv(xv), dy = mksv(dyv);
+  const V x = mkv(xv), dy = mkv(dyv);
   const int KC0 = Cin * kh * kw;
   float* part = (float*)scratch(kSlotPart, sizeof(float) * (size_t)grid * Cout * (KC0 + 1), st);
   if (!part) return (int)hipErrorOutOfMemory;

@@ -22,13 +22,10 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "upr_common.h"
-#include "../../include/upr_train.h"
+#include "train_common.h"
 
 namespace upr {
 
-typedef float f32x4_w2 __attribute__((ext_vector_type(4)));
-typedef float f32x16_w2 __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) void* lds_void_ptr_w2;
 
 __device__ __attribute__((aligned(128))) uint4 g_wg_zero[8];
@@ -107,7 +104,7 @@ __global__ __launch_bounds__(256) void wgrad_gemm_kernel(WgArgs a) {
     }
   };
 
-  f32x16_w2 acc0, acc1;
+  f32x16 acc0, acc1;
 #pragma unroll
   for (int e = 0; e < 16; ++e) { acc0[e] = 0.f; acc1[e] = 0.f; }
   const int half = lane >> 5, col = lane & 31;
@@ -149,27 +146,27 @@ __global__ __launch_bounds__(256) void wgrad_gemm_kernel(WgArgs a) {
 __global__ __launch_bounds__(256) void wgrad_slab_reduce_kernel(const float* __restrict__ slab, int splits, int Cout,
                                                                 int KT, int ldn, float* __restrict__ dwp,
                                                                 int torch_ci) {
-  __shared__ f32x4_w2 red[16][16];
+  __shared__ f32x4 red[16][16];
   const int q = threadIdx.x & 15, j = threadIdx.x >> 4;
   const int n4 = Cout * KT / 4;
   const int i = blockIdx.x * 16 + q;
   const int e = i * 4;
   const int co = e / KT, k = e - co * KT;
-  f32x4_w2 s[4] = {};
+  f32x4 s[4] = {};
   if (i < n4) {
     const float* p = slab + (size_t)co * ldn + k;
     const size_t step = (size_t)Cout * ldn;
     int sp = j;
     for (; sp + 48 < splits; sp += 64) {
 #pragma unroll
-      for (int u = 0; u < 4; ++u) s[u] += *(const f32x4_w2*)(p + (size_t)(sp + 16 * u) * step);
+      for (int u = 0; u < 4; ++u) s[u] += *(const f32x4*)(p + (size_t)(sp + 16 * u) * step);
     }
-    for (int u = 0; sp < splits; sp += 16, ++u) s[u & 3] += *(const f32x4_w2*)(p + (size_t)sp * step);
+    for (int u = 0; sp < splits; sp += 16, ++u) s[u & 3] += *(const f32x4*)(p + (size_t)sp * step);
   }
   red[j][q] = (s[0] + s[1]) + (s[2] + s[3]);
   __syncthreads();
   if (j != 0 || i >= n4) return;
-  f32x4_w2 acc = red[0][q];
+  f32x4 acc = red[0][q];
 #pragma unroll
   for (int r = 1; r < 16; ++r) acc += red[r][q];
   if (torch_ci) {
@@ -178,7 +175,7 @@ __global__ __launch_bounds__(256) void wgrad_slab_reduce_kernel(const float* __r
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) o[(size_t)jj * taps] += acc[jj];
   } else {
-    f32x4_w2* o = (f32x4_w2*)(dwp + e);
+    f32x4* o = (f32x4*)(dwp + e);
     *o = *o + acc;
   }
 }
@@ -301,7 +298,7 @@ __global__ __launch_bounds__(256) void wgrad16_kernel(Wg16Args a) {
 
   // A staging: chunk i of this thread = pixel tid / NQA + i * (256 / NQA), quad tid % NQA
   const int qa = tid % NQA;
-  f32x4_w2 areg[AC];
+  f32x4 areg[AC];
   f16x4_w2 hreg[AC];
   const bool a16 = a.dy16 != nullptr;  // uniform
   auto load_a = [&](int u) {
@@ -321,7 +318,7 @@ __global__ __launch_bounds__(256) void wgrad16_kernel(Wg16Args a) {
 #pragma unroll
     for (int i = 0; i < AC; ++i) {
       const int pr = tid / NQA + i * (256 / NQA);
-      areg[i] = *(const f32x4_w2*)(base + (size_t)pr * a.dy_cs);
+      areg[i] = *(const f32x4*)(base + (size_t)pr * a.dy_cs);
     }
   };
   auto store_a = [&]() {
@@ -361,11 +358,11 @@ __global__ __launch_bounds__(256) void wgrad16_kernel(Wg16Args a) {
     }
   };
 
-  f32x4_w2 acc[MT][RPW * 2];
+  f32x4 acc[MT][RPW * 2];
 #pragma unroll
   for (int i = 0; i < MT; ++i)
 #pragma unroll
-    for (int j = 0; j < RPW * 2; ++j) acc[i][j] = f32x4_w2{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < RPW * 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int fg = lane >> 4, l16 = lane & 15, tq = l16 >> 2, tp = l16 & 3;
 
   if (u0 < u1) {
@@ -597,7 +594,7 @@ __global__ __launch_bounds__(256) void wgrad16h_kernel(Wg16hArgs a) {
   // dy of step s -> registers (quad i of this thread: q = i * 256 + tid -> pixel q / (COUT/4), quad q % (COUT/4))
   // A16: dy's fp16 copy is read (a compile-time choice: a runtime one put each load in
   // its own branch, and hipcc waited for every load at the join)
-  f32x4_w2 areg[A16 ? 1 : AQ];
+  f32x4 areg[A16 ? 1 : AQ];
   f16x4_w2 hreg[A16 ? AQ : 1];
   auto load_dy = [&](int s) {
     const size_t pix0 = (size_t)(b * a.H + s * TR) * a.W + ox0;
@@ -609,7 +606,7 @@ __global__ __launch_bounds__(256) void wgrad16h_kernel(Wg16hArgs a) {
       if constexpr (A16)
         hreg[i] = *(const f16x4_w2*)(a.dy16 + pix * a.dy_cs + a.dy_coff + cq * 4);
       else
-        areg[i] = *(const f32x4_w2*)(a.dy + pix * a.dy_cs + a.dy_coff + cq * 4);
+        areg[i] = *(const f32x4*)(a.dy + pix * a.dy_cs + a.dy_coff + cq * 4);
     }
   };
   auto store_dy = [&](auto STG_) {
@@ -629,11 +626,11 @@ __global__ __launch_bounds__(256) void wgrad16h_kernel(Wg16hArgs a) {
     }
   };
 
-  f32x4_w2 acc[MT][NKT];
+  f32x4 acc[MT][NKT];
 #pragma unroll
   for (int m = 0; m < MT; ++m)
 #pragma unroll
-    for (int k = 0; k < NKT; ++k) acc[m][k] = f32x4_w2{0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < NKT; ++k) acc[m][k] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int fg = lane >> 4, l16 = lane & 15, tq = l16 >> 2, tp = l16 & 3;
 
   auto compute = [&](auto STG_) {
@@ -714,20 +711,20 @@ __global__ __launch_bounds__(256) void wgrad16h_kernel(Wg16hArgs a) {
   constexpr int NPASS = C::NPASS, NKP = NKT / NPASS;
   constexpr int WSTRIDE = MT * NKP * 64;  // f32x4 chunks per wave per pass
   // waves 0, 1 park in stage 0, waves 2, 3 in stage 1
-  f32x4_w2* red0 = (f32x4_w2*)stg0;
-  f32x4_w2* red1 = (f32x4_w2*)stg1;
+  f32x4* red0 = (f32x4*)stg0;
+  f32x4* red1 = (f32x4*)stg1;
   float* sl = a.slab + (size_t)split * COUT * a.ldn + (size_t)tg * NTAP * CIN;
 #pragma unroll
   for (int ps = 0; ps < NPASS; ++ps) {
     if (ps) __syncthreads();  // the previous pass's sums are read
-    f32x4_w2* mine = (wave < 2 ? red0 : red1) + (wave & 1) * WSTRIDE;
+    f32x4* mine = (wave < 2 ? red0 : red1) + (wave & 1) * WSTRIDE;
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
       for (int k = 0; k < NKP; ++k) mine[(m * NKP + k) * 64 + lane] = acc[m][ps * NKP + k];
     __syncthreads();
     for (int c = tid; c < WSTRIDE; c += 256) {
-      const f32x4_w2 v = red0[c] + red0[WSTRIDE + c] + red1[c] + red1[WSTRIDE + c];
+      const f32x4 v = red0[c] + red0[WSTRIDE + c] + red1[c] + red1[WSTRIDE + c];
       const int ln = c & 63, mk = c >> 6, m = mk / NKP, k = ps * NKP + mk % NKP;
 #pragma unroll
       for (int i = 0; i < 4; ++i) sl[(size_t)(m * 16 + (ln >> 4) * 4 + i) * a.ldn + k * 16 + (ln & 15)] = v[i];

@@ -108,6 +108,14 @@ class UprPackJob(ctypes.Structure):
                 ("n", ctypes.c_int)]
 
 
+# include/upr_train.h UPR_T_STORE_*: bits of upr_t_conv_mfma / upr_t_conv_mfma16's `store`
+UPR_T_STORE_CONVT2X2 = 1
+UPR_T_STORE_KEEP16 = 2
+UPR_T_STORE_ONLY16 = 4
+UPR_T_STORE_S2_1X1 = 8
+UPR_T_STORE_S2_3X3_DGRAD = 16
+UPR_T_STORE_X16_STRIDED = 32
+
 _vp = ctypes.POINTER(UprView)
 c_u64, c_i64p = ctypes.c_uint64, ctypes.c_void_p
 _i, _p, _f = c_int, c_void_p, c_float

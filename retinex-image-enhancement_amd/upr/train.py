@@ -339,7 +339,7 @@ class Conv:
         # x16_strided: x16 is the shared fp16 copy of the concat x is a slice of (channel stride cs)
         x16p = ctypes.c_void_p(x16.data_ptr() + 2 * coff) if x16_strided else _p(x16)
         if x16_strided:
-            store |= 32
+            store |= L.UPR_T_STORE_X16_STRIDED
         if out16 is not None:
             t16, c16, cs16 = out16
             y16p, y16cs = ctypes.c_void_p(t16.data_ptr() + 2 * c16), cs16
@@ -349,15 +349,15 @@ class Conv:
         _chk(L.lib().upr_t_conv_mfma16(_fp(x, 0), B, H, W, C, cs, coff, _p(w16), _p(bias), N, kh, kw, s, p, d,
                                        res.ptr() if res is not None else None, res.cs if res is not None else 0,
                                        int(relu), _fp(out.t), out.cs, out.coff,
-                                       store | (2 if keep16 and res is None else 0) |
-                                       (4 if only16 and keep16 and res is None else 0),
+                                       store | (L.UPR_T_STORE_KEEP16 if keep16 and res is None else 0) |
+                                       (L.UPR_T_STORE_ONLY16 if only16 and keep16 and res is None else 0),
                                        x16p, int(ready), y16p, y16cs, _stream()), "conv_mfma16")
         if out16 is not None:
             out.t16 = None
             return x16
         # forward activations (keep16): without a residual y16 is (half)out exactly, and the next
         # autocast conv reading out takes it (Act.t16); forward activations are not modified in place
-        whole = out.coff == 0 and out.cs == out.C == (N // 4 if store == 1 else N)
+        whole = out.coff == 0 and out.cs == out.C == (N // 4 if store == L.UPR_T_STORE_CONVT2X2 else N)
         out.t16 = y16 if keep16 and res is None and whole else None
         out.stale32 = bool(only16 and out.t16 is not None)
         return x16
@@ -458,17 +458,17 @@ class Conv:
     def _dgrad_s2_1x1(self, gy, src16, B, Ho, Wo, gx):
         """Input gradient of a 1x1 stride-2 conv (the projecting shortcut,
         model.py:119-122) accumulated into gx: dx(2i, 2j) += W^T dy(i, j) on the
-        streaming 1x1 kernel (upr_t_conv_mfma16 store | 8), with no zero-upsampled
+        streaming 1x1 kernel (upr_t_conv_mfma16 store S2_1X1), with no zero-upsampled
         operand.  False when the shape is not one that kernel takes."""
         if gy.stale32 and src16 is None:
             return False
         lib = L.lib()
         x16 = src16 if src16 is not None else _h16(B * Ho * Wo * self.Cout, gy.t.device)
-        y16 = _h16(16, gy.t.device)  # not written (store has no | 2)
+        y16 = _h16(16, gy.t.device)  # not written (store has no KEEP16)
         rc = lib.upr_t_conv_mfma16(None if src16 is not None else _fp(gy.t, 0), B, Ho, Wo, self.Cout,
                                    gy.cs, gy.coff, _p(self.wt16), None, self.Cin, 1, 1, 1, 0, 1, gx.ptr(), gx.cs, 0,
-                                   _fp(gx.t), gx.cs, gx.coff, 8, _p(x16), int(src16 is not None), _p(y16), 0,
-                                   _stream())
+                                   _fp(gx.t), gx.cs, gx.coff, L.UPR_T_STORE_S2_1X1, _p(x16), int(src16 is not None),
+                                   _p(y16), 0, _stream())
         if rc == L.UPR_ERR_UNSUPPORTED:
             return False
         _chk(rc, "conv_dgrad_s2_1x1")
@@ -478,7 +478,7 @@ class Conv:
     def _dgrad_s2_3x3(self, gy, src16, B, Ho, Wo, gx, acc, o16):
         """Input gradient of a 3x3 stride-2 pad-1 conv (enc1.conv1, model.py:100-178)
         straight from dy: the four output phases as small convs over dy (upr_t_conv_mfma16
-        store | 16), no zero-upsampled operand.  False when the kernel does not take
+        store S2_3X3_DGRAD), no zero-upsampled operand.  False when the kernel does not take
         the shape (the caller then zero-upsamples)."""
         if gy.stale32 and src16 is None:
             return False
@@ -489,7 +489,9 @@ class Conv:
         y16 = _h16(B * 4 * Ho * Wo * self.Cin if keep else 16, dev)  # written only with keep
         rc = lib.upr_t_conv_mfma16(None if ready else _fp(gy.t, 0), B, Ho, Wo, self.Cout, gy.cs, gy.coff,
                                    _p(self.wt16), None, self.Cin, 3, 3, 1, 1, 1, gx.ptr() if acc else None,
-                                   gx.cs if acc else 0, 0, _fp(gx.t), gx.cs, gx.coff, 16 | (6 if keep else 0),
+                                   gx.cs if acc else 0, 0, _fp(gx.t), gx.cs, gx.coff,
+                                   L.UPR_T_STORE_S2_3X3_DGRAD |
+                                   (L.UPR_T_STORE_KEEP16 | L.UPR_T_STORE_ONLY16 if keep else 0),
                                    _p(x16), int(ready), _p(y16), 0, _stream())
         if rc == L.UPR_ERR_UNSUPPORTED:
             return False
@@ -739,12 +741,12 @@ class ConvT:
         with _timed("mfma16" if self.amp else "mfma32", "fwd", self.flops(x)):
             if self.amp:
                 Conv._mfma16(self, x.t, x.B, x.H, x.W, self.Cin, x.cs, x.coff, self.wp16, self.b4, 4 * self.Cout, 1, 1,
-                             1, 0, 1, None, False, out, store=1, x16=x.t16 if x.coff == 0 and x.cs == x.C == self.Cin
-                             else None, keep16=True)
+                             1, 0, 1, None, False, out, store=L.UPR_T_STORE_CONVT2X2,
+                             x16=x.t16 if x.coff == 0 and x.cs == x.C == self.Cin else None, keep16=True)
             else:
                 _chk(L.lib().upr_t_conv_mfma(x.ptr(), x.B, x.H, x.W, self.Cin, x.cs, 0, _p(self.wp), _p(self.b4),
-                                             4 * self.Cout, 1, 1, 1, 0, 1, None, 0, 0, _fp(out.t), out.cs, 0, 1,
-                                             _stream()), "convT")
+                                             4 * self.Cout, 1, 1, 1, 0, 1, None, 0, 0, _fp(out.t), out.cs, 0,
+                                             L.UPR_T_STORE_CONVT2X2, _stream()), "convT")
         return out
 
     def flops(self, x):

@@ -561,7 +561,8 @@ def test_conv_mfma16_1x1_streaming(cin, cout, bias, relu, resid):
     bd = b.to(DEV) if bias else None
     rc = lib.upr_t_conv_mfma16(xd.data_ptr(), B, H, W, cin, cin, 0, wd16.data_ptr(), bd.data_ptr() if bias else None,
                                cout, 1, 1, 1, 0, 1, y.data_ptr() if resid else None, cout if resid else 0, int(relu),
-                               y.data_ptr(), cout, 0, 0 if resid else 2, x16.data_ptr(), 0, y16.data_ptr(), 0, st)
+                               y.data_ptr(), cout, 0, 0 if resid else L.UPR_T_STORE_KEEP16, x16.data_ptr(), 0,
+                               y16.data_ptr(), 0, st)
     assert rc == 0, rc
     torch.cuda.synchronize()
     _close(y, ref, 1e-3, "1x1 fp32 out")
@@ -625,8 +626,8 @@ def test_dgrad_1x1_stride2_scatter(cin, cout):
     y16 = torch.empty(16, dtype=torch.float16, device=DEV)
     gx = base.to(DEV)
     rc = lib.upr_t_conv_mfma16(dyd.data_ptr(), B, Ho, Wo, cout, cout, 0, wt16.data_ptr(), None, cin, 1, 1, 1, 0, 1,
-                               gx.data_ptr(), cin, 0, gx.data_ptr(), cin, 0, 8, x16.data_ptr(), 0, y16.data_ptr(), 0,
-                               st)
+                               gx.data_ptr(), cin, 0, gx.data_ptr(), cin, 0, L.UPR_T_STORE_S2_1X1, x16.data_ptr(), 0,
+                               y16.data_ptr(), 0, st)
     assert rc == 0, rc
     torch.cuda.synchronize()
     _close(gx, ref, 1e-3, "1x1 s2 dgrad")
@@ -635,7 +636,8 @@ def test_dgrad_1x1_stride2_scatter(cin, cout):
     assert torch.equal(gx.cpu()[:, odd], base[:, odd])
     # the flag is refused on anything but a 1x1 accumulate
     assert lib.upr_t_conv_mfma16(dyd.data_ptr(), B, Ho, Wo, cout, cout, 0, wt16.data_ptr(), None, cin, 1, 1, 1, 0, 1,
-                                 None, 0, 0, gx.data_ptr(), cin, 0, 8, x16.data_ptr(), 0, y16.data_ptr(), 0, st) != 0
+                                 None, 0, 0, gx.data_ptr(), cin, 0, L.UPR_T_STORE_S2_1X1, x16.data_ptr(), 0,
+                                 y16.data_ptr(), 0, st) != 0
 
 
 @pytest.mark.parametrize("cin,cout", [(32, 64), (64, 128), (128, 256)])
@@ -666,7 +668,7 @@ def test_dgrad_3x3_stride2_phases(acc, keep16, cin, cout):
     x16 = torch.empty(B * Ho * Wo * cout, dtype=torch.float16, device=DEV)
     y16 = torch.zeros(B * 4 * Ho * Wo * cin, dtype=torch.float16, device=DEV)
     gx = base.to(DEV) if acc else torch.full((B, 2 * Ho, 2 * Wo, cin), 7.0, device=DEV)
-    store = 16 | (6 if keep16 else 0)
+    store = L.UPR_T_STORE_S2_3X3_DGRAD | (L.UPR_T_STORE_KEEP16 | L.UPR_T_STORE_ONLY16 if keep16 else 0)
     rc = lib.upr_t_conv_mfma16(dyd.data_ptr(), B, Ho, Wo, cout, cout, 0, wt16.data_ptr(), None, cin, 3, 3, 1, 1, 1,
                                gx.data_ptr() if acc else None, cin if acc else 0, 0, gx.data_ptr(), cin, 0, store,
                                x16.data_ptr(), 0, y16.data_ptr(), 0, st)
@@ -701,8 +703,8 @@ def test_shared_concat_fp16_slices():
         y16 = torch.empty(B * H * W * N, dtype=torch.float16, device=DEV)
         if strided:
             rc = lib.upr_t_conv_mfma16(None, B, H, W, C, 4 * C, k0, wt16.data_ptr(), None, N, 3, 3, 1, 1, 1, None, 0,
-                                       0, y.data_ptr(), N, 0, 32, ctypes.c_void_p(cat16.data_ptr() + 2 * k0), 1,
-                                       y16.data_ptr(), 0, st)
+                                       0, y.data_ptr(), N, 0, L.UPR_T_STORE_X16_STRIDED,
+                                       ctypes.c_void_p(cat16.data_ptr() + 2 * k0), 1, y16.data_ptr(), 0, st)
         else:
             rc = lib.upr_t_conv_mfma16(None, B, H, W, C, C, 0, wt16.data_ptr(), None, N, 3, 3, 1, 1, 1, None, 0, 0,
                                        y.data_ptr(), N, 0, 0, sl16.data_ptr(), 1, y16.data_ptr(), 0, st)
