@@ -34,7 +34,9 @@
 extern "C" {
 #endif
 
-enum { UPR_F32 = 0, UPR_F16 = 1 };
+/* UPR_F32_SPLIT: upr_conv2d_nhwc only -- an fp32 conv computed from split-fp16
+ * operands (see upr_split_f32) */
+enum { UPR_F32 = 0, UPR_F16 = 1, UPR_F32_SPLIT = 2 };
 
 enum {
   UPR_OK = 0,
@@ -97,6 +99,16 @@ void upr_model_destroy(UprModel* model);
  * reference counterpart: lets a caller report which executor actually ran. */
 long long upr_model_forks(const UprModel* model);
 
+/* An fp32 model without PreAct / ASPP runs the convs of its 128- and
+ * 256-channel levels (enc2 .. dec3) on the fp16 MFMA unit from split-fp16
+ * operands with fp32 accumulation (about fp32 accuracy; env UPR_FP32_SPLIT=0,
+ * read by upr_model_create, keeps the fp32 MFMA kernels).  Those activations
+ * must stay within the fp16 range (65504): a forward that leaves it sets a
+ * flag, and from the next forward on the handle runs the fp32 kernels for good
+ * (one line on stderr).  Returns 0: off, 1: active, 2: disabled after an
+ * overflow.  No reference counterpart. */
+int upr_model_split_state(const UprModel* model);
+
 /* Per-op profiling of upr_model_forward (no reference counterpart: the
  * reference only brackets whole calls with time.time(), simple_enhance.py:165-179).
  * enable != 0 records a hipEvent pair around every op of every later forward
@@ -137,6 +149,20 @@ int upr_retinex_decompose_bwd(const void* x, const void* illu, const void* g, vo
 int upr_conv2d_nhwc(const void* x, int B, int H, int W, int Cin, const void* w, const float* bias, int Cout, int kh,
                     int kw, int stride, int pad, int dil, const void* residual, int relu, void* y, int dtype,
                     void* stream);
+
+/* Split-fp16 tensors: C fp32 channels of an NHWC pixel stored as 2C fp16,
+ * [hi(C) | lo(C)], hi = (half)v, lo = (half)((v - hi) * 2^11); v = hi + lo *
+ * 2^-11 to about 2^-22 relative.  upr_split_f32: x fp32 [npix][C] -> y fp16
+ * [npix][2C] (C % 8 == 0, 16-byte aligned); `overflow` (device word, nullable)
+ * is set to 1 when a |v| > 65504 or non-finite value is met (never cleared).
+ * upr_unsplit_f32 is the inverse.  upr_pack_split_f32 (host only): conv weight
+ * w fp32 [Cout][Cin][kh][kw] (Cin % 64 == 0) -> the blob upr_conv2d_nhwc takes
+ * as `w` with dtype UPR_F32_SPLIT (x, residual and y split tensors, Cout % 128
+ * == 0); returns the blob's bytes (0: bad arguments) and fills `out` when
+ * out_bytes suffices.  No reference counterpart. */
+int upr_split_f32(const float* x, void* y, size_t npix, int C, unsigned* overflow, void* stream);
+int upr_unsplit_f32(const void* x, float* y, size_t npix, int C, void* stream);
+size_t upr_pack_split_f32(const float* w, int Cout, int Cin, int kh, int kw, void* out, size_t out_bytes);
 
 /* float -> uint8 exactly as `(x * 255).astype(np.uint8)` on float32
  * (enhancers/adaptive_params.py:142, letterbox.py:93): truncation, wrap mod

@@ -386,7 +386,6 @@ static int launch_t(const ConvOp& op, hipStream_t stream) {
 }
 
 int launch_conv_halo(const ConvOp& op, int dtype, hipStream_t st);
-int launch_conv_wide(const ConvOp& op, hipStream_t st);
 int launch_conv_ring(const ConvOp& op, hipStream_t st);
 int launch_conv_ring32(const ConvOp& op, hipStream_t st);
 int launch_conv_wide32(const ConvOp& op, hipStream_t st);

@@ -36,6 +36,11 @@
 //
 // Segments must be plain (no pre-activation / max-pool prologue: those need
 // register staging and stay on conv.hip / conv_halo.hip), C % 64 == 0.
+//
+// The gathered kernel also computes fp32 convs from split-fp16 operands
+// (ConvOp::split_out, upr_common.h; weights and K-segments from pack_split in
+// model.hip): same main loop over 3x the K, and SPLIT instances of the two
+// epilogues that keep every value in fp32 until it is stored as hi / lo halves.
 #include <cstdlib>
 #include <cstring>
 #include <utility>
@@ -118,7 +123,8 @@ struct SegCursor {
 // before the accumulators are parked -- one batch of independent loads
 // instead of one exposed HBM round trip per 16-byte store (a residual cost
 // the bottleneck / dec3 convs 10-25% of their time)
-template <int BN, int WM, int WN, int WAVES_M, int BM = WBM, bool RPF = false, int QW = 0>
+// SPLIT: an fp32 conv from split-fp16 operands (ConvOp::split_out), see direct_epilogue
+template <int BN, int WM, int WN, int WAVES_M, int BM = WBM, bool RPF = false, int QW = 0, bool SPLIT = false>
 __device__ __forceinline__ void wide_epilogue(const ConvOp& op, f32x4_w (&acc)[WM][WN], unsigned char* smem, int m0,
                                               int n0, int M, int HW) {
   const int tid = threadIdx.x;
@@ -170,7 +176,7 @@ __device__ __forceinline__ void wide_epilogue(const ConvOp& op, f32x4_w (&acc)[W
   const half_t* rpf = (const half_t*)(op.res1 ? op.res1 : op.res2);
   const int rpf_cs = op.res1 ? op.res1_cs : op.res2_cs;
   f16x8_w rv[NQ];
-  if (RPF && rpf) {
+  if (RPF && rpf && !SPLIT) {
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
       const int m = m0 + tid / CPR + q * RPI;
@@ -242,7 +248,9 @@ __device__ __forceinline__ void wide_epilogue(const ConvOp& op, f32x4_w (&acc)[W
           for (int e = 0; e < 8; ++e) v[e] += op.img_bias[img * op.N + nch + e];
         }
         const int q = RPF ? p * (64 / RPI) + it : 0;
-        if (op.res1) {
+        if (SPLIT) {
+          if (op.res1) split_res_add(v, (const half_t*)op.res1 + (size_t)m * op.res1_cs + nch, op.N);
+        } else if (op.res1) {
           const f16x8_w r = RPF ? rv[q] : *(const f16x8_w*)((const half_t*)op.res1 + (size_t)m * op.res1_cs + nch);
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] += (float)r[e];
@@ -251,10 +259,29 @@ __device__ __forceinline__ void wide_epilogue(const ConvOp& op, f32x4_w (&acc)[W
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
         }
-        if (op.res2) {
+        if (SPLIT) {
+          if (op.res2) split_res_add(v, (const half_t*)op.res2 + (size_t)m * op.res2_cs + nch, op.N);
+        } else if (op.res2) {
           const f16x8_w r = RPF && !op.res1 ? rv[q] : *(const f16x8_w*)((const half_t*)op.res2 + (size_t)m * op.res2_cs + nch);
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] += (float)r[e];
+        }
+        if constexpr (SPLIT) {
+          // the unrounded fp32 value: as hi / lo halves, or plain fp32 at the region's exit
+          size_t pix = (size_t)m;
+          int ch = nch;
+          if (convt) {
+            pix = ((size_t)img * 2 * op.Ho + 2 * py + (cq >> 1)) * (2 * op.Wo) + 2 * px + (cq & 1);
+            ch = cco;
+          }
+          if (op.split_out) {
+            if (split_store((half_t*)op.split_out + pix * op.split_cs + ch, op.split_lo, v) && op.ovf) *op.ovf = 1u;
+          } else {
+            float* d = op.out_f32 + pix * op.out_f32_cs + ch;
+            *(f32x4_w*)d = f32x4_w{v[0], v[1], v[2], v[3]};
+            *(f32x4_w*)(d + 4) = f32x4_w{v[4], v[5], v[6], v[7]};
+          }
+          continue;
         }
         f16x8_w o;
 #pragma unroll
@@ -339,7 +366,8 @@ __device__ __forceinline__ void wide_epilogue(const ConvOp& op, f32x4_w (&acc)[W
 // block on the CU overlapping)
 // DS: operand-swapped MFMAs, B rows DMA'd in hw4_perm32 order and the
 // direct-store epilogue (wide_ds_ok decides per op)
-template <int BN, bool PIPE, int MINW = 2, int SCHED = 0, bool DS = false>
+// SPLIT: the fp32-from-split-fp16 epilogues (same main loop)
+template <int BN, bool PIPE, int MINW = 2, int SCHED = 0, bool DS = false, bool SPLIT = false>
 __global__ __launch_bounds__(512, MINW) void conv_wide_kernel(ConvOp op) {
   constexpr bool ONE = MINW >= 4;
   using C = WideCfg<BN>;
@@ -532,10 +560,10 @@ __global__ __launch_bounds__(512, MINW) void conv_wide_kernel(ConvOp op) {
     // (no pool in this form: the LDS is not reused, no barrier)
     f16x8_w rv0[C::WM];
     const int mb = m0 + wm * C::WM * 16 + (lane & 15);
-    direct_epilogue<BN, C::WM, C::WN, C::WAVES_M, false>(
+    direct_epilogue<BN, C::WM, C::WN, C::WAVES_M, false, SPLIT>(
         op, acc, n0, wm, wn, lane, rv0, smem, [&](int a) { return mb + a * 16; }, M, HW, -1);
   } else {
-    wide_epilogue<BN, C::WM, C::WN, C::WAVES_M, WBM, !ONE>(op, acc, smem, m0, n0, M, HW);
+    wide_epilogue<BN, C::WM, C::WN, C::WAVES_M, WBM, !ONE, 0, SPLIT>(op, acc, smem, m0, n0, M, HW);
   }
 }
 
@@ -1702,23 +1730,28 @@ static int halo_route(const ConvOp& op, hipStream_t st) {
 // per-image pool (its tiles may straddle images)
 static bool wide_ds_ok(const ConvOp& op) { return !op.pool && hw4_ds_ok(op); }
 
-template <int BN, bool PIPE, int SCHED, bool DS>
+static bool wide_split(const ConvOp& op) { return op.split_out || op.out_f32; }
+
+template <int BN, bool PIPE, int SCHED, bool DS, bool SPLIT = false>
 static int launch_wide_bn_k(const ConvOp& op, hipStream_t st) {
   using C = WideCfg<BN>;
   static bool attr_set = false;
   if (!attr_set) {
-    const hipError_t e = hipFuncSetAttribute((const void*)conv_wide_kernel<BN, PIPE, 2, SCHED, DS>,
+    const hipError_t e = hipFuncSetAttribute((const void*)conv_wide_kernel<BN, PIPE, 2, SCHED, DS, SPLIT>,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
     if (e != hipSuccess) return (int)e;
     attr_set = true;
   }
   const int M = op.B * op.Ho * op.Wo;
   const int grid = ((M + WBM - 1) / WBM) * (op.N / BN);
-  hipLaunchKernelGGL((conv_wide_kernel<BN, PIPE, 2, SCHED, DS>), dim3(grid), dim3(512), C::LDS, st, op);
+  hipLaunchKernelGGL((conv_wide_kernel<BN, PIPE, 2, SCHED, DS, SPLIT>), dim3(grid), dim3(512), C::LDS, st, op);
   return (int)hipGetLastError();
 }
 template <int BN, bool PIPE, int SCHED>
 static int launch_wide_bn_s(const ConvOp& op, hipStream_t st) {
+  if (wide_split(op))
+    return wide_ds_ok(op) ? launch_wide_bn_k<BN, PIPE, SCHED, true, true>(op, st)
+                          : launch_wide_bn_k<BN, PIPE, SCHED, false, true>(op, st);
   return wide_ds_ok(op) ? launch_wide_bn_k<BN, PIPE, SCHED, true>(op, st) : launch_wide_bn_k<BN, PIPE, SCHED, false>(op, st);
 }
 
@@ -1764,7 +1797,12 @@ static int launch_wide_onestep128(const ConvOp& op, hipStream_t st) {
   constexpr int LDS1 = C::STAGE > EPI ? C::STAGE : EPI;
   const int M = op.B * op.Ho * op.Wo;
   const int grid = ((M + WBM - 1) / WBM) * (op.N / 128);
-  if (wide_ds_ok(op))
+  if (wide_split(op)) {
+    if (wide_ds_ok(op))
+      hipLaunchKernelGGL((conv_wide_kernel<128, false, 4, 0, true, true>), dim3(grid), dim3(512), LDS1, st, op);
+    else
+      hipLaunchKernelGGL((conv_wide_kernel<128, false, 4, 0, false, true>), dim3(grid), dim3(512), LDS1, st, op);
+  } else if (wide_ds_ok(op))
     hipLaunchKernelGGL((conv_wide_kernel<128, false, 4, 0, true>), dim3(grid), dim3(512), LDS1, st, op);
   else
     hipLaunchKernelGGL((conv_wide_kernel<128, false, 4>), dim3(grid), dim3(512), LDS1, st, op);
@@ -1772,7 +1810,24 @@ static int launch_wide_onestep128(const ConvOp& op, hipStream_t st) {
 }
 
 // fp16 only; returns kErrUnsupported for shapes this kernel does not take
-int launch_conv_wide(const ConvOp& op, hipStream_t st) {
+// probe: launch nothing, only answer whether the gathered kernel takes the op
+// (kOk / kErrUnsupported); ops only a halo-tiled form would take answer
+// kErrUnsupported to a probe
+int launch_conv_wide(const ConvOp& op, hipStream_t st, bool probe) {
+  const bool split = op.split_out || op.out_f32 || op.split_res;
+  if (split) {
+    // fp32 conv from split-fp16 operands: one output form, at most one
+    // (split) residual, 16-byte stores
+    if ((op.split_out != nullptr) == (op.out_f32 != nullptr) || op.out32 || op.out2 || op.pool || op.img_bias) return kErrUnsupported;
+    if (op.split_out && ((uintptr_t)op.split_out % 16 || op.split_cs % 8 || op.split_lo % 8)) return kErrUnsupported;
+    if (op.out_f32 && ((uintptr_t)op.out_f32 % 16 || op.out_f32_cs % 4 || op.store != kStoreNHWC)) return kErrUnsupported;
+    if (op.split_res && (op.res1 != nullptr) == (op.res2 != nullptr)) return kErrUnsupported;
+    if (!op.split_res && (op.res1 || op.res2)) return kErrUnsupported;
+    if (op.store == kStoreConvT2x2 && (op.N % 32 || op.res1 || op.res2)) return kErrUnsupported;
+    if ((op.res1 && ((uintptr_t)op.res1 % 16 || op.res1_cs % 8)) || (op.res2 && ((uintptr_t)op.res2 % 16 || op.res2_cs % 8)))
+      return kErrUnsupported;
+    if (((uintptr_t)op.scale | (uintptr_t)op.bias) % 16 || op.N % 8) return kErrUnsupported;
+  }
   if (op.out2 && ((uintptr_t)op.out2 % 16 || op.store != kStoreNHWC)) return kErrUnsupported;
   if (op.out32 && ((uintptr_t)op.out32 % 16 || op.out32_cs % 4 || op.out32_coff % 4)) return kErrUnsupported;
   if (op.res32 && ((uintptr_t)op.res32 % 16 || op.res32_cs % 4)) return kErrUnsupported;
@@ -1785,11 +1840,12 @@ int launch_conv_wide(const ConvOp& op, hipStream_t st) {
   }
   // UPR_HALO=0: skip the halo-tiled forms (A/B against the gathered kernel, tools/convbench.py)
   static const bool halo_off = [] { const char* e = getenv("UPR_HALO"); return e && atoi(e) == 0; }();
-  if (!halo_off) {
+  if (!halo_off && !split && !probe) {
     const int rc = halo_route(op, st);
     if (rc != kErrUnsupported) return rc;
   }
   if (op.N % 128) return kErrUnsupported;  // (64-wide: only the halo route above)
+  if (probe) return kOk;
   if (op.N % 256 == 0) return launch_wide_any<256>(op, st);
   // (128-channel stride-1 3x3 convs: faster here than on the old halo kernel,
   // dec3.conv.0 0.264 -> 0.191 ms, conv.3 0.276 -> 0.217)

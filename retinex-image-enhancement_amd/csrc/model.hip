@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -135,6 +136,7 @@ struct GemmLayer {
   int N = 0, Kpad = 0;
   size_t w = 0;                 // bytes offset of [N][Kpad] T
   size_t bias = SIZE_MAX;       // float [N]
+  size_t scale = SIZE_MAX;      // float [N] (split-fp16 layers: 1 / s_n, pack_split)
   std::vector<SegSpec> segs;
 };
 
@@ -192,6 +194,79 @@ static GemmLayer pack_gemm(Blob& blob, int dtype, int N, std::vector<SegWeights>
   L.w = blob.add_t(W, dtype);
   if (!bias.empty()) L.bias = blob.add_f32(bias);
   return L;
+}
+
+// ---------------------------------------------------------------------------
+// Split-fp16 form of an fp32 GEMM (the fp16 wide-tile kernel computing an fp32
+// conv, ConvOp::split_out).  Activations: v = hi + lo * 2^-11, both fp16.
+// Weights, per output channel n: a power of two s_n puts max|w| in [2^14,
+// 2^15) (exact), W_hi = fp16(w s), W_lo = fp16(w s - W_hi).  Then
+//   x w s ~= hi W_hi + lo (W_hi 2^-11) + hi W_lo        (fp32 accumulate)
+// and the dropped lo W_lo term is ~2^-22 relative.  Each logical segment (src,
+// C, taps) becomes two K-segments over the same [hi | lo] source of pixel
+// stride 2C: A reads all 2C channels against [W_hi | W_hi 2^-11] per tap, B
+// reads the C hi channels against W_lo.  scale[n] = 1 / s_n (the epilogue
+// applies it before the bias).  Scaling the weights up keeps W_lo and the lo
+// products clear of the fp16 subnormal range; storing lo scaled by 2^11 does
+// the same for the activations.
+// ---------------------------------------------------------------------------
+struct SplitPack {
+  int N = 0, Kpad = 0;
+  std::vector<_Float16> W;     // [N][Kpad]
+  std::vector<float> scale;    // [N]
+  std::vector<SegSpec> segs;   // 2 per logical segment
+};
+
+// segs: plain segments (coff 0, cs == C, C % 64 == 0, no prologue); false otherwise
+static bool pack_split(int N, const std::vector<SegWeights>& segs, SplitPack& out) {
+  if (segs.empty() || segs.size() > 2) return false;
+  out = SplitPack();
+  out.N = N;
+  int K = 0;
+  for (const auto& s : segs) {
+    const SegSpec& sp = s.spec;
+    if (sp.coff != 0 || sp.cs != sp.C || sp.C % 64 || sp.pre != kPreNone) return false;
+    const int taps = sp.kh * sp.kw;
+    SegSpec a = sp, b = sp;
+    a.C = 2 * sp.C; a.cs = 2 * sp.C; a.kbase = K;
+    K += taps * 2 * sp.C;
+    b.C = sp.C; b.cs = 2 * sp.C; b.kbase = K;
+    K += taps * sp.C;
+    out.segs.push_back(a);
+    out.segs.push_back(b);
+  }
+  out.Kpad = (int)align_up(K, 32);
+  out.W.assign((size_t)N * out.Kpad, (_Float16)0.f);
+  out.scale.assign(N, 1.f);
+  for (int n = 0; n < N; ++n) {
+    double mx = 0.0;
+    for (const auto& s : segs) {
+      const size_t per = (size_t)s.spec.C * s.spec.kh * s.spec.kw;
+      for (size_t i = 0; i < per; ++i) mx = std::max(mx, std::fabs(s.w[n * per + i]));
+    }
+    int e = 15;  // mx = f 2^e, f in [0.5, 1): mx 2^(15 - e) is in [2^14, 2^15)
+    if (mx > 0.0 && std::isfinite(mx)) (void)std::frexp(mx, &e);
+    const int sh = std::min(std::max(15 - e, -100), 100);
+    const double sc = std::ldexp(1.0, sh);
+    out.scale[n] = (float)std::ldexp(1.0, -sh);
+    for (size_t si = 0; si < segs.size(); ++si) {
+      const SegSpec& sp = segs[si].spec;
+      const int C = sp.C, kh = sp.kh, kw = sp.kw;
+      _Float16* rowA = out.W.data() + (size_t)n * out.Kpad + out.segs[2 * si].kbase;
+      _Float16* rowB = out.W.data() + (size_t)n * out.Kpad + out.segs[2 * si + 1].kbase;
+      for (int c = 0; c < C; ++c)
+        for (int r = 0; r < kh; ++r)
+          for (int q = 0; q < kw; ++q) {
+            const double w = segs[si].w[(((size_t)n * C + c) * kh + r) * kw + q] * sc;
+            const _Float16 hi = (_Float16)w;
+            const int t = r * kw + q;
+            rowA[t * 2 * C + c] = hi;
+            rowA[t * 2 * C + C + c] = (_Float16)((double)hi * (1.0 / 2048.0));
+            rowB[t * C + c] = (_Float16)(w - (double)hi);
+          }
+    }
+  }
+  return true;
 }
 
 // Conv weight [N][C][kh][kw] from a HostTensor, rows scaled by mul (optional).
@@ -265,7 +340,7 @@ static std::vector<double> conv3_kmajor(const std::vector<double>& w) {
   return t;
 }
 
-enum OpKind { OP_GEMM, OP_CONV3, OP_PREP, OP_FAM_CA, OP_FAM_MIX, OP_FAM_SA, OP_ASPP_G, OP_TAIL, OP_PREACT };
+enum OpKind { OP_GEMM, OP_CONV3, OP_PREP, OP_FAM_CA, OP_FAM_MIX, OP_FAM_SA, OP_ASPP_G, OP_TAIL, OP_PREACT, OP_SPLIT };
 
 struct Op {
   OpKind kind;
@@ -277,6 +352,9 @@ struct Op {
   int res1 = -1, res1_cs = 0, res2 = -1, res2_cs = 0;
   int relu = 0, store = kStoreNHWC;
   int pool_slot = -1;   // index into pool buffer (units of B*256 16-byte entries)
+  // split-fp16 region (fp32 plain models): the op's second layer (pack_split),
+  // -1 outside the region; split_exit: the op writes plain fp32 (region exit)
+  int split_layer = -1, split_exit = 0;
   int img_bias = 0;
   size_t head_w = 0; float head_b = 0.f;
   // conv3 / fam
@@ -329,6 +407,14 @@ struct UprModel {
   unsigned long long side_clock = 0;
   std::mutex sides_mu;
   std::atomic<long long> forks{0};  // forwards that ran the two-stream schedule (upr_model_forks)
+  // Split-fp16 region of the plain fp32 graph (env UPR_FP32_SPLIT, read at
+  // creation): 0 off, 1 active, 2 disabled for good after a region activation
+  // left the fp16 range.  ovf_dev: the sticky device word the split epilogues
+  // set; copied (asynchronously) into the pinned ovf_host at the end of every
+  // split forward and looked at when the next forward starts.
+  std::atomic<int> split_state{0};
+  unsigned* ovf_dev = nullptr;
+  volatile unsigned* ovf_host = nullptr;
 };
 
 namespace upr {
@@ -446,9 +532,38 @@ struct Builder {
     const HostTensor* t = T(k);
     return t ? t->v : std::vector<double>();
   }
+  // the double weights of every GEMM layer, kept for make_split (split-capable models only)
+  std::map<int, std::vector<SegWeights>> kept;
   int add_layer(int N, std::vector<SegWeights>& segs, const std::vector<double>& bias) {
     m->layers.push_back(pack_gemm(blob, dt, N, segs, bias));
+    if (m->split_state.load() == 1) kept[(int)m->layers.size() - 1] = segs;
     return (int)m->layers.size() - 1;
+  }
+  // Gives the region's ops (name prefixes `first` .. `last`, in graph order)
+  // their split-fp16 layers; the last one writes plain fp32.  B_X2, which dec2
+  // also needs as fp32, is read from its split copy in B_U2 (OP_SPLIT; B_U2 is
+  // idle until dec2.up).  False when an op does not fit: the model stays exact.
+  bool make_split(const std::vector<std::string>& names) {
+    for (size_t i = 0; i < names.size(); ++i) {
+      Op* o = nullptr;
+      for (auto& q : m->ops)
+        if (q.kind == OP_GEMM && q.name == names[i]) o = &q;
+      if (!o || !kept.count(o->layer) || o->pool_slot >= 0 || o->img_bias) return false;
+      SplitPack sp;
+      if (!pack_split(m->layers[o->layer].N, kept[o->layer], sp)) return false;
+      GemmLayer L;
+      L.N = sp.N; L.Kpad = sp.Kpad;
+      L.w = blob.add(sp.W.data(), sp.W.size() * 2);
+      L.scale = blob.add(sp.scale.data(), sp.scale.size() * 4);
+      L.bias = m->layers[o->layer].bias;
+      L.segs = sp.segs;
+      for (auto& s : L.segs)
+        if (s.src == B_X2) s.src = B_U2;
+      m->layers.push_back(L);
+      o->split_layer = (int)m->layers.size() - 1;
+      o->split_exit = i + 1 == names.size();
+    }
+    return true;
   }
   void gemm(const std::string& name, int layer, int level, int out, int out_cs, int relu, int res1 = -1,
             int res1_cs = 0, int res2 = -1, int res2_cs = 0, int store = kStoreNHWC, int out_coff = 0,
@@ -741,6 +856,12 @@ static int build_model(UprModel* m, ParamSet& P) {
   (void)pre;
   if (!head_only) {
   bd.block(ie + ".enc1", B_X1, B_E1T, B_X2, 32, 64, 2, 0);
+  if (m->split_state.load() == 1) {
+    // region entry: the split-fp16 copy of enc1's output (a no-op on forwards that run exact)
+    Op o;
+    o.kind = OP_SPLIT; o.name = ie + ".enc2.split_in"; o.in = B_X2; o.out = B_U2; o.level = 1;
+    m->ops.push_back(o);
+  }
   bd.block(ie + ".enc2", B_X2, B_E2T, B_X3, 64, 128, 2, 1);
   bd.block(ie + ".enc3", B_X3, B_E3T, B_X4, 128, 256, 2, 2);
   if (m->use_aspp) {
@@ -753,6 +874,18 @@ static int build_model(UprModel* m, ParamSet& P) {
   }
   if (!bd.ok) return P.missing.empty() ? kErrShape : kErrMissingParam;
   bd.upblock(ie + ".dec3", B_X5, B_U3, B_V3, B_D3, 256, 128, 3, B_X3);
+  if (m->split_state.load() == 1) {
+    std::vector<std::string> region;
+    for (const char* n : {".enc2.conv1", ".enc2.conv2", ".enc3.conv1", ".enc3.conv2", ".bottleneck.0.conv1",
+                          ".bottleneck.0.conv2", ".bottleneck.1.conv1", ".bottleneck.1.conv2", ".dec3.up",
+                          ".dec3.conv.0", ".dec3.conv.3"})
+      region.push_back(ie + n);
+    if (!bd.ok || !bd.make_split(region)) {
+      for (auto& o : m->ops) o.split_layer = -1;
+      m->split_state.store(0);
+    }
+    bd.kept.clear();
+  }
   bd.upblock(ie + ".dec2", B_D3, B_U2, B_V2, B_D2, 128, 64, 2, B_X2);
   bd.upblock(ie + ".dec1", B_D2, B_U1, B_V1, B_D1, 64, 32, 1, B_X1);
   // residual head + illumination (models/model.py:324-328, :351-358)
@@ -908,6 +1041,56 @@ static int run_forward(UprModel* m, const void* x, int B, int H, int W, void* en
     m->cur_bytes.assign(nops, 0.0);
   }
   const double elt = dt == kF16 ? 2.0 : 4.0;
+  // The split-fp16 form of a region op (Op::split_layer): its K-segments over the
+  // [hi | lo] tensors, residuals in split form, output split or (exit) plain fp32
+  auto split_op = [&](const Op& o, int ho, int wo) {
+    const GemmLayer& L = m->layers[o.split_layer];
+    ConvOp c;
+    memset(&c, 0, sizeof(c));
+    c.nseg = (int)L.segs.size();
+    for (int i = 0; i < c.nseg; ++i) {
+      const SegSpec& s = L.segs[i];
+      ConvSeg& cs = c.seg[i];
+      cs.src = buf(s.src);
+      cs.C = s.C; cs.cs = s.cs; cs.coff = s.coff;
+      cs.Hin = ho * s.stride; cs.Win = wo * s.stride;
+      cs.kh = s.kh; cs.kw = s.kw; cs.stride = s.stride; cs.pad = s.pad; cs.dil = s.dil;
+      cs.pre = kPreNone; cs.kbase = s.kbase;
+    }
+    c.B = B; c.Ho = ho; c.Wo = wo; c.N = L.N; c.Kpad = L.Kpad;
+    c.W = blob + L.w;
+    c.scale = fptr(L.scale);
+    c.bias = L.bias != SIZE_MAX ? fptr(L.bias) : nullptr;
+    c.res1 = o.res1 >= 0 ? buf(o.res1) : nullptr; c.res1_cs = 2 * o.res1_cs;
+    c.res2 = o.res2 >= 0 ? buf(o.res2) : nullptr; c.res2_cs = 2 * o.res2_cs;
+    c.split_res = c.res1 || c.res2;
+    c.relu = o.relu;
+    c.store = o.store;
+    if (o.split_exit) { c.out_f32 = (float*)buf(o.out); c.out_f32_cs = o.out_cs; }
+    else { c.split_out = buf(o.out); c.split_cs = 2 * o.out_cs; c.split_lo = o.out_cs; }
+    c.ovf = m->ovf_dev;
+    return c;
+  };
+  // This forward runs the region split only if the handle is still in state 1
+  // (a range overflow seen by an earlier forward switches it to the exact plan
+  // for good) and the wide kernel takes every op of it at this (B, H, W)
+  bool split_now = false;
+  if (m->split_state.load() == 1) {
+    int one = 1;
+    if (m->ovf_host && *m->ovf_host) {
+      if (m->split_state.compare_exchange_strong(one, 2))
+        fprintf(stderr, "upr: an fp32 activation left the fp16 range; this model now runs its exact fp32 plan "
+                      "(UPR_FP32_SPLIT=0 selects it from the start)\n");
+    } else {
+      split_now = true;
+      for (const Op& o : m->ops)
+        if (o.kind == OP_GEMM && o.split_layer >= 0) {
+          int ho, wo;
+          lvl_dims(o.level, ho, wo);
+          if (launch_conv_wide(split_op(o, ho, wo), st, /*probe=*/true) != kOk) split_now = false;
+        }
+    }
+  }
   // launch op oi on stream st (the caller's stream or the multi-scale side stream)
   auto run_op = [&](size_t oi, hipStream_t st) -> int {
     const Op& o = m->ops[oi];
@@ -968,7 +1151,8 @@ static int run_forward(UprModel* m, const void* x, int B, int H, int W, void* en
           c.out2 = buf(o.out2); c.out2_cs = L.N;
           c.pre2_scale = fptr(o.ps); c.pre2_shift = fptr(o.ph);
         }
-        rc = launch_conv(c, dt, st);
+        if (split_now && o.split_layer >= 0) rc = launch_conv_wide(split_op(o, ho, wo), st);
+        else rc = launch_conv(c, dt, st);
         if (m->prof) {
           // GEMM work of this launch: 2*M*N*K; algorithmic bytes: every source read once,
           // weights once, residuals once, output written once
@@ -994,6 +1178,15 @@ static int run_forward(UprModel* m, const void* x, int B, int H, int W, void* en
         const int C = buf_geom(o.out, m->use_aspp).C;
         rc = launch_preact_f16(buf(o.in), fptr(o.w), fptr(o.b), buf(o.out), (size_t)B * h * w, C, st);
         if (m->prof) m->cur_bytes[oi] = 2.0 * B * h * w * C * elt;
+        break;
+      }
+      case OP_SPLIT: {
+        if (!split_now) break;
+        int h, w;
+        lvl_dims(o.level, h, w);
+        const int C = buf_geom(o.in, m->use_aspp).C;
+        rc = launch_split_f32((const float*)buf(o.in), buf(o.out), (size_t)B * h * w, C, m->ovf_dev, st);
+        if (m->prof) m->cur_bytes[oi] = 2.0 * B * h * w * C * 4.0;
         break;
       }
       case OP_ASPP_G: {
@@ -1087,6 +1280,8 @@ static int run_forward(UprModel* m, const void* x, int B, int H, int W, void* en
     }
     for (size_t i = 0; i < nops; ++i) { m->st_flops[i] += m->cur_flops[i]; m->st_bytes[i] += m->cur_bytes[i]; }
   }
+  if (split_now)  // range guard: looked at when the next forward starts, no wait here
+    UPR_CHECK_HIP(hipMemcpyAsync((void*)m->ovf_host, m->ovf_dev, sizeof(unsigned), hipMemcpyDeviceToHost, st));
   if (dt == kF16 && !(m->flags & UPR_MODEL_HEAD_ONLY)) {
     // illumination in the model dtype
     extern int launch_cast_f32_to_f16(const float*, void*, size_t, hipStream_t);
@@ -1102,6 +1297,66 @@ __global__ void cast_f32_f16_kernel(const float* __restrict__ a, half_t* __restr
 }
 int launch_cast_f32_to_f16(const float* a, void* b, size_t n, hipStream_t st) {
   hipLaunchKernelGGL(cast_f32_f16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, (half_t*)b, n);
+  return (int)hipGetLastError();
+}
+
+// fp32 NHWC <-> split fp16 ([hi(C) | lo(C)] per pixel, ConvOp::split_out):
+// one thread per 8 channels of a pixel, 16-byte accesses
+__global__ void split_f32_kernel(const float* __restrict__ x, half_t* __restrict__ y, size_t n8, int C8,
+                                 unsigned* __restrict__ ovf) {
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n8) return;
+  const size_t pix = i / C8;
+  const int c = (int)(i - pix * C8) * 8;
+  const f4 a = *(const f4*)(x + i * 8), b = *(const f4*)(x + i * 8 + 4);
+  const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+  h8 h, l;
+  bool bad = false;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    h[e] = (half_t)v[e];
+    l[e] = (half_t)((v[e] - (float)h[e]) * kSplitLoScale);
+    bad = bad || !(__builtin_fabsf(v[e]) <= 65504.f);
+  }
+  half_t* d = y + pix * (size_t)(16 * C8) + c;
+  *(h8*)d = h;
+  *(h8*)(d + 8 * C8) = l;
+  if (bad && ovf) *ovf = 1u;
+}
+__global__ void unsplit_f32_kernel(const half_t* __restrict__ x, float* __restrict__ y, size_t n8, int C8) {
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n8) return;
+  const size_t pix = i / C8;
+  const int c = (int)(i - pix * C8) * 8;
+  const half_t* sp = x + pix * (size_t)(16 * C8) + c;
+  const h8 h = *(const h8*)sp, l = *(const h8*)(sp + 8 * C8);
+  f4 a, b;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    a[e] = (float)h[e] + (float)l[e] * kSplitLoInv;
+    b[e] = (float)h[e + 4] + (float)l[e + 4] * kSplitLoInv;
+  }
+  *(f4*)(y + i * 8) = a;
+  *(f4*)(y + i * 8 + 4) = b;
+}
+int launch_split_f32(const float* x, void* y, size_t npix, int C, unsigned* ovf, hipStream_t st) {
+  if (C <= 0 || C % 8 || ((uintptr_t)x | (uintptr_t)y) % 16) return kErrArg;
+  const size_t n8 = npix * (size_t)(C / 8);
+  if (n8 == 0) return kOk;
+  if ((n8 + 255) / 256 > 0x7fffffffull) return kErrShape;
+  hipLaunchKernelGGL(split_f32_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, x, (half_t*)y, n8, C / 8, ovf);
+  return (int)hipGetLastError();
+}
+int launch_unsplit_f32(const void* x, float* y, size_t npix, int C, hipStream_t st) {
+  if (C <= 0 || C % 8 || ((uintptr_t)x | (uintptr_t)y) % 16) return kErrArg;
+  const size_t n8 = npix * (size_t)(C / 8);
+  if (n8 == 0) return kOk;
+  if ((n8 + 255) / 256 > 0x7fffffffull) return kErrShape;
+  hipLaunchKernelGGL(unsplit_f32_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, (const half_t*)x, y, n8, C / 8);
   return (int)hipGetLastError();
 }
 
@@ -1135,9 +1390,24 @@ int upr_model_create(const UprTensorDesc* params, int n_params, int use_preact, 
   }
   std::unique_ptr<UprModel> m(new UprModel());
   m->dtype = dtype; m->use_preact = use_preact ? 1 : 0; m->use_aspp = use_aspp ? 1 : 0; m->flags = flags;
+  // the split-fp16 region exists in the plain fp32 IENet only; UPR_FP32_SPLIT=0
+  // (read here, per handle) keeps the fp32 MFMA kernels everywhere
+  const char* se = getenv("UPR_FP32_SPLIT");
+  const bool split_env = !(se && *se && atoi(se) == 0);
+  if (split_env && dtype == UPR_F32 && !m->use_preact && !m->use_aspp && !(flags & UPR_MODEL_HEAD_ONLY))
+    m->split_state.store(1);
   int rc = build_model(m.get(), P);
+  if (rc == kOk && m->split_state.load() == 1) {
+    hipError_t e = hipMalloc((void**)&m->ovf_dev, 256);
+    if (e == hipSuccess) e = hipMemset(m->ovf_dev, 0, 256);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&m->ovf_host, sizeof(unsigned), hipHostMallocDefault);
+    if (e == hipSuccess) *m->ovf_host = 0u;
+    else rc = (int)e;
+  }
   if (rc != kOk) {
     if (m->dev_blob) (void)hipFree(m->dev_blob);
+    if (m->ovf_dev) (void)hipFree(m->ovf_dev);
+    if (m->ovf_host) (void)hipHostFree((void*)m->ovf_host);
     return rc;
   }
   *out = m.release();
@@ -1205,12 +1475,16 @@ int upr_model_profile_read(UprModel* model, UprOpStat* out, int max_ops, int* n_
 
 long long upr_model_forks(const UprModel* model) { return model ? model->forks.load() : -1; }
 
+int upr_model_split_state(const UprModel* model) { return model ? model->split_state.load() : 0; }
+
 void upr_model_destroy(UprModel* model) {
   if (!model) return;
   upr_model_profile(model, 0);
   for (auto e : model->ev_free) (void)hipEventDestroy(e);
   model->sides.clear();  // ~Side: synchronise, destroy
   if (model->dev_blob) (void)hipFree(model->dev_blob);
+  if (model->ovf_dev) (void)hipFree(model->ovf_dev);
+  if (model->ovf_host) (void)hipHostFree((void*)model->ovf_host);
   delete model;
 }
 
@@ -1231,12 +1505,34 @@ int upr_conv2d_nhwc(const void* x, int B, int H, int W, int Cin, const void* w, 
                     void* stream) {
   if (!x || !w || !y || B <= 0 || H <= 0 || W <= 0 || Cin % 32 || Cout % 32 || Cin <= 0 || Cout <= 0) return UPR_ERR_ARG;
   if (kh <= 0 || kw <= 0 || stride <= 0 || dil <= 0 || pad < 0) return UPR_ERR_ARG;
-  if (dtype != UPR_F32 && dtype != UPR_F16) return UPR_ERR_ARG;
+  if (dtype != UPR_F32 && dtype != UPR_F16 && dtype != UPR_F32_SPLIT) return UPR_ERR_ARG;
   const int Ho = (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1;
   const int Wo = (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
   if (Ho <= 0 || Wo <= 0) return UPR_ERR_SHAPE;
   ConvOp c;
   memset(&c, 0, sizeof(c));
+  if (dtype == UPR_F32_SPLIT) {
+    // x / residual / y are split tensors, w is upr_pack_split_f32's blob: the
+    // two K-segments of pack_split over x, then the per-channel scale
+    if (Cin % 64 || Cout % 128) return UPR_ERR_UNSUPPORTED;
+    const int taps = kh * kw;
+    c.nseg = 2;
+    for (int i = 0; i < 2; ++i) {
+      ConvSeg& s = c.seg[i];
+      s.src = x; s.C = i == 0 ? 2 * Cin : Cin; s.cs = 2 * Cin; s.coff = 0; s.Hin = H; s.Win = W;
+      s.kh = kh; s.kw = kw; s.stride = stride; s.pad = pad; s.dil = dil; s.pre = kPreNone;
+      s.kbase = i == 0 ? 0 : taps * 2 * Cin;
+    }
+    c.B = B; c.Ho = Ho; c.Wo = Wo; c.N = Cout; c.Kpad = (int)align_up((size_t)3 * taps * Cin, 32);
+    c.W = w;
+    c.scale = (const float*)((const uint8_t*)w + align_up((size_t)Cout * c.Kpad * 2, 256));
+    c.bias = bias; c.relu = relu;
+    if (relu) { c.res1 = residual; c.res1_cs = 2 * Cout; }
+    else { c.res2 = residual; c.res2_cs = 2 * Cout; }
+    c.split_res = residual != nullptr;
+    c.split_out = y; c.split_cs = 2 * Cout; c.split_lo = Cout; c.store = kStoreNHWC;
+    return launch_conv_wide(c, (hipStream_t)stream);
+  }
   c.nseg = 1;
   ConvSeg& s = c.seg[0];
   s.src = x; s.C = Cin; s.cs = Cin; s.coff = 0; s.Hin = H; s.Win = W;
@@ -1249,6 +1545,33 @@ int upr_conv2d_nhwc(const void* x, int B, int H, int W, int Cin, const void* w, 
   else { c.res2 = residual; c.res2_cs = Cout; }
   c.out = y; c.out_cs = Cout; c.out_coff = 0; c.store = kStoreNHWC;
   return launch_conv(c, dtype, (hipStream_t)stream);
+}
+
+size_t upr_pack_split_f32(const float* w, int Cout, int Cin, int kh, int kw, void* out, size_t out_bytes) {
+  if (!w || Cout <= 0 || Cin <= 0 || Cin % 64 || kh <= 0 || kw <= 0) return 0;
+  std::vector<SegWeights> segs(1);
+  segs[0].spec = seg(/*src=*/0, Cin, Cin, 0, kh, 1, 0, 1);
+  segs[0].spec.kw = kw;
+  segs[0].w.assign(w, w + (size_t)Cout * Cin * kh * kw);
+  SplitPack sp;
+  if (!pack_split(Cout, segs, sp)) return 0;
+  const size_t wbytes = align_up(sp.W.size() * 2, 256), need = wbytes + sp.scale.size() * 4;
+  if (out && out_bytes >= need) {
+    memset(out, 0, need);
+    memcpy(out, sp.W.data(), sp.W.size() * 2);
+    memcpy((uint8_t*)out + wbytes, sp.scale.data(), sp.scale.size() * 4);
+  }
+  return need;
+}
+
+int upr_split_f32(const float* x, void* y, size_t npix, int C, unsigned* overflow, void* stream) {
+  if (!x || !y) return UPR_ERR_ARG;
+  return launch_split_f32(x, y, npix, C, overflow, (hipStream_t)stream);
+}
+
+int upr_unsplit_f32(const void* x, float* y, size_t npix, int C, void* stream) {
+  if (!x || !y) return UPR_ERR_ARG;
+  return launch_unsplit_f32(x, y, npix, C, (hipStream_t)stream);
 }
 
 }  // extern "C"

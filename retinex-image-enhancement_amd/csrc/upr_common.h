@@ -115,7 +115,30 @@ struct ConvOp {
   // hwide4 pointwise form (set by its dispatcher, 0 elsewhere): each tile walks
   // its K chunks starting at chunk mtile % NCH instead of 0
   int krot;
+  // Split-fp16 form of an fp32 conv (launch_conv_wide only).  A split tensor
+  // stores C fp32 channels per pixel as 2C fp16: [hi(C) | lo(C)], hi = (half)v,
+  // lo = (half)((v - hi) * 2^11), v = hi + lo * 2^-11.  The segments and packed
+  // weights carry the split operands (model.hip pack_split); here only the
+  // epilogue differs: every value is taken from the fp32 accumulator, never
+  // from its fp16 rounding.
+  // split_out (nullable): hi at split_out[pix * split_cs + ch], lo split_lo
+  // halfs further (NHWC: split_lo = N, ConvT pixel shuffle: N / 4); `out` is
+  // not written.  out_f32 (nullable): the plain fp32 value instead (NHWC).
+  // split_res: res1 / res2 are split tensors (lo at + N).  ovf (nullable): set
+  // to 1 with a plain store when a stored |v| > 65504 or v is not finite.
+  void* split_out; int split_cs, split_lo;
+  float* out_f32; int out_f32_cs;
+  int split_res;
+  unsigned* ovf;
 };
+
+// 2^11 / 2^-11: the scale of the lo half of a split-fp16 value (ConvOp::split_out)
+constexpr float kSplitLoScale = 2048.f;
+constexpr float kSplitLoInv = 1.f / 2048.f;
+
+// fp32 NHWC [npix][C] <-> split fp16 [npix][2C] (C % 8 == 0; model.hip)
+int launch_split_f32(const float* x, void* y, size_t npix, int C, unsigned* ovf, hipStream_t st);
+int launch_unsplit_f32(const void* x, float* y, size_t npix, int C, hipStream_t st);
 
 // fp16 convs with an fp32 output (ConvOp::out32): the wide-tile and row-ring
 // kernels; kErrUnsupported when neither takes the op
@@ -127,6 +150,9 @@ int launch_conv_s2dg(const ConvOp& op, hipStream_t stream, bool probe = false);
 int launch_conv_pw(const ConvOp& op, hipStream_t stream, bool probe = false);
 
 int launch_conv(const ConvOp& op, int dtype, hipStream_t stream);
+// fp16 wide-tile convs (conv_wide.hip), also the split-fp16 form of fp32 convs
+// (ConvOp::split_out); probe: only answer kOk / kErrUnsupported
+int launch_conv_wide(const ConvOp& op, hipStream_t st, bool probe = false);
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 

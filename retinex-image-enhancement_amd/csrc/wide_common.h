@@ -43,6 +43,29 @@ __device__ __forceinline__ void glds16_s(const void* ubase, unsigned voff, unsig
 }
 
 
+// Split-fp16 tensors (ConvOp::split_out): 8 channels of one pixel, hi at p, lo
+// lo_off halfs further.  split_res_add: v += hi + lo * 2^-11 in fp32.
+// split_store: writes both halves of the unrounded v (two 16-byte stores);
+// returns true when a value is outside the fp16 range (|v| > 65504, inf, NaN).
+__device__ __forceinline__ void split_res_add(float (&v)[8], const half_t* p, int lo_off) {
+  const f16x8_w h = *(const f16x8_w*)p, l = *(const f16x8_w*)(p + lo_off);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] += (float)h[e] + (float)l[e] * kSplitLoInv;
+}
+__device__ __forceinline__ bool split_store(half_t* p, int lo_off, const float (&v)[8]) {
+  f16x8_w h, l;
+  bool bad = false;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    h[e] = (half_t)v[e];
+    l[e] = (half_t)((v[e] - (float)h[e]) * kSplitLoScale);
+    bad = bad || !(__builtin_fabsf(v[e]) <= 65504.f);
+  }
+  *(f16x8_w*)p = h;
+  *(f16x8_w*)(p + lo_off) = l;
+  return bad;
+}
+
 template <typename F, int... S>
 __device__ __forceinline__ void static_steps(F&& f, std::integer_sequence<int, S...>) {
   (f(std::integral_constant<int, S>{}), ...);
@@ -70,8 +93,10 @@ __device__ __forceinline__ int hw4_perm32(int r) {
 // pixel (GEMM row) of the lane's fragment a, valid while < M; IMG >= 0: every
 // pixel of the block is in image IMG (required for op.pool), else the image is
 // divided out per fragment (only for the per-image bias).  PRE: the caller
-// preloaded pair 0's residual rows into rv0 (hw4_res_load).
-template <int BN, int WM, int WN, int WAVES_M, bool PRE, typename PixF>
+// preloaded pair 0's residual rows into rv0 (hw4_res_load).  SPLIT: the op is
+// an fp32 conv from split-fp16 operands (ConvOp::split_out / out_f32 /
+// split_res); a kernel instance of its own, so the fp16 forms carry none of it.
+template <int BN, int WM, int WN, int WAVES_M, bool PRE, bool SPLIT = false, typename PixF>
 __device__ __forceinline__ void direct_epilogue(const ConvOp& op, f32x4_w (&acc)[WM][WN], int n0, int wm, int wn,
                                                 int lane, const f16x8_w (&rv0)[WM], unsigned char* smem, PixF pix,
                                                 int M, int HW, int IMG) {
@@ -137,6 +162,22 @@ __device__ __forceinline__ void direct_epilogue(const ConvOp& op, f32x4_w (&acc)
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += op.img_bias[im * op.N + c + e];
       }
+      if (SPLIT && op.split_res) {
+        // split residual (one of res1 / res2): hi was prefetched into rv, lo is read here
+        const f16x8_w l = *(const f16x8_w*)(rpf + m * rcs + op.N + c);
+        if (op.res1) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[e] += (float)rv[p][a][e] + (float)l[e] * kSplitLoInv;
+        }
+        if (op.relu) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+        }
+        if (!op.res1) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[e] += (float)rv[p][a][e] + (float)l[e] * kSplitLoInv;
+        }
+      } else {
       if (op.res1) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += (float)rv[p][a][e];
@@ -149,6 +190,18 @@ __device__ __forceinline__ void direct_epilogue(const ConvOp& op, f32x4_w (&acc)
         const f16x8_w r = op.res1 ? *(const f16x8_w*)((const half_t*)op.res2 + m * op.res2_cs + c) : rv[p][a];
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += (float)r[e];
+      }
+      }
+      if constexpr (SPLIT) {
+        // the unrounded fp32 value: as hi / lo halves, or plain fp32 at the region's exit
+        if (op.split_out) {
+          if (split_store((half_t*)op.split_out + m * op.split_cs + c, op.split_lo, v) && op.ovf) *op.ovf = 1u;
+        } else {
+          float* d = op.out_f32 + m * op.out_f32_cs + c;
+          *(f32x4_w*)d = f32x4_w{v[0], v[1], v[2], v[3]};
+          *(f32x4_w*)(d + 4) = f32x4_w{v[4], v[5], v[6], v[7]};
+        }
+        continue;
       }
       f16x8_w o;
 #pragma unroll

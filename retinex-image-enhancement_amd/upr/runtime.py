@@ -122,6 +122,10 @@ class ModelHandle:
         """Forwards so far that ran the two-stream (multi-scale side stream) schedule."""
         return int(self._lib.upr_model_forks(self._h))
 
+    def split_state(self):
+        """Split-fp16 region of an fp32 model: 0 off, 1 active, 2 disabled after a range overflow."""
+        return int(self._lib.upr_model_split_state(self._h))
+
     def profile_read(self):
         """Per-op stats (launch order): list of dicts name/kind/calls/ms/flops/bytes."""
         n = ctypes.c_int(0)
@@ -307,6 +311,70 @@ def conv2d_nhwc(x, w_packed, bias, kh, kw, stride=1, pad=0, dil=1, residual=None
                                      stride, pad, dil, _ptr(residual), int(bool(relu)), _ptr(y),
                                      dtype_code(x.dtype), _stream(x.device))
     L.check(rc, "upr_conv2d_nhwc")
+    return y
+
+
+def split_f32(x, overflow=None):
+    """fp32 NHWC [..., C] -> split fp16 [..., 2C] = [hi | lo] (hi + lo * 2^-11 = x to ~2^-22).
+
+    overflow: optional int32 device tensor of one element, set to 1 when a
+    value is outside the fp16 range."""
+    _require_device(x)
+    if x.dtype != torch.float32 or x.shape[-1] % 8:
+        raise ValueError("split_f32 expects float32 with a channel count that is a multiple of 8")
+    x = x.contiguous()
+    C = x.shape[-1]
+    y = torch.empty(x.shape[:-1] + (2 * C,), dtype=torch.float16, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = L.lib().upr_split_f32(_ptr(x), _ptr(y), x.numel() // C, C, _ptr(overflow), _stream(x.device))
+    L.check(rc, "upr_split_f32")
+    return y
+
+
+def unsplit_f32(y):
+    """Inverse of split_f32: split fp16 [..., 2C] -> fp32 [..., C]."""
+    _require_device(y)
+    if y.dtype != torch.float16 or y.shape[-1] % 16:
+        raise ValueError("unsplit_f32 expects a float16 split tensor")
+    y = y.contiguous()
+    C = y.shape[-1] // 2
+    x = torch.empty(y.shape[:-1] + (C,), dtype=torch.float32, device=y.device)
+    with torch.cuda.device(y.device):
+        rc = L.lib().upr_unsplit_f32(_ptr(y), _ptr(x), y.numel() // (2 * C), C, _stream(y.device))
+    L.check(rc, "upr_unsplit_f32")
+    return x
+
+
+def pack_split_weight(w):
+    """torch conv weight [Cout, Cin, kh, kw] (fp32, host packing) -> the uint8 blob
+    conv2d_split takes: split-fp16 K-segments [W_hi | W_hi 2^-11], W_lo and the per-channel scale."""
+    wc = w.detach().to("cpu", torch.float32).contiguous()
+    co, ci, kh, kw = wc.shape
+    lib = L.lib()
+    need = lib.upr_pack_split_f32(ctypes.c_void_p(wc.data_ptr()), co, ci, kh, kw, None, 0)
+    if need == 0:
+        raise ValueError(f"pack_split_weight: unsupported weight shape {tuple(wc.shape)} (Cin % 64 == 0)")
+    blob = torch.empty(need, dtype=torch.uint8)
+    lib.upr_pack_split_f32(ctypes.c_void_p(wc.data_ptr()), co, ci, kh, kw, ctypes.c_void_p(blob.data_ptr()), need)
+    return blob
+
+
+def conv2d_split(x, w_blob, cout, bias, kh, kw, stride=1, pad=0, dil=1, residual=None, relu=False):
+    """conv2d_nhwc on split tensors: x [B,H,W,2Cin] and residual [B,Ho,Wo,2Cout] fp16
+    split, w_blob from pack_split_weight (on the device) -> y [B,Ho,Wo,2Cout] split."""
+    _require_device(x)
+    x = x.contiguous()
+    B, H, W, C2 = x.shape
+    Ho = (H + 2 * pad - dil * (kh - 1) - 1) // stride + 1
+    Wo = (W + 2 * pad - dil * (kw - 1) - 1) // stride + 1
+    y = torch.empty((B, Ho, Wo, 2 * cout), dtype=torch.float16, device=x.device)
+    if residual is not None:
+        residual = residual.contiguous()
+    with torch.cuda.device(x.device):
+        rc = L.lib().upr_conv2d_nhwc(_ptr(x), B, H, W, C2 // 2, _ptr(w_blob), _ptr(bias), cout, kh, kw, stride, pad,
+                                     dil, _ptr(residual), int(bool(relu)), _ptr(y), L.UPR_F32_SPLIT,
+                                     _stream(x.device))
+    L.check(rc, "upr_conv2d_nhwc(split)")
     return y
 
 
