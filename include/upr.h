@@ -34,9 +34,11 @@
 extern "C" {
 #endif
 
-/* UPR_F32_SPLIT: upr_conv2d_nhwc only -- an fp32 conv computed from split-fp16
- * operands (see upr_split_f32) */
-enum { UPR_F32 = 0, UPR_F16 = 1, UPR_F32_SPLIT = 2 };
+/* upr_conv2d_nhwc only: UPR_F32_SPLIT -- an fp32 conv computed from split-fp16
+ * operands (see upr_split_f32); UPR_F32_SPLIT_REGS -- an fp32 conv over plain
+ * fp32 tensors whose fragments are split into fp16 (hi, lo) pairs in registers
+ * (see upr_conv2d_nhwc_regs) */
+enum { UPR_F32 = 0, UPR_F16 = 1, UPR_F32_SPLIT = 2, UPR_F32_SPLIT_REGS = 3 };
 
 enum {
   UPR_OK = 0,
@@ -99,15 +101,33 @@ void upr_model_destroy(UprModel* model);
  * reference counterpart: lets a caller report which executor actually ran. */
 long long upr_model_forks(const UprModel* model);
 
-/* An fp32 model without PreAct / ASPP runs the convs of its 128- and
- * 256-channel levels (enc2 .. dec3) on the fp16 MFMA unit from split-fp16
- * operands with fp32 accumulation (about fp32 accuracy; env UPR_FP32_SPLIT=0,
- * read by upr_model_create, keeps the fp32 MFMA kernels).  Those activations
- * must stay within the fp16 range (65504): a forward that leaves it sets a
- * flag, and from the next forward on the handle runs the fp32 kernels for good
- * (one line on stderr).  Returns 0: off, 1: active, 2: disabled after an
- * overflow.  No reference counterpart. */
+/* An fp32 model without PreAct / ASPP runs its convs on the fp16 MFMA unit
+ * with fp32 accumulation (about fp32 accuracy), in two ways.  "Split tensors":
+ * the convs of the 128- and 256-channel levels (enc2 .. dec3) read and write
+ * split-fp16 tensors.  "Split in registers": the 32-channel stride-1 3x3 convs
+ * of the row-ring kernel (dec1, the residual head, the EnhancedFAM branch3/4
+ * first convs and fusion parts) keep fp32 tensors and split each 8-channel
+ * fragment into (hi, lo) fp16 after reading it.  Env UPR_FP32_SPLIT=0, read by
+ * upr_model_create, keeps the fp32 MFMA kernels everywhere; UPR_FP32_SPLIT_REGS=0
+ * keeps them for the split-in-registers ops only.  The activations these
+ * convs read must stay within the fp16 range (65504): a forward that leaves it
+ * sets a flag, and from the next forward on the handle runs the fp32 kernels
+ * for good (one line on stderr).  A UPR_MODEL_HEAD_ONLY handle of such a model
+ * has no split-tensor op but runs its EnhancedFAM convs split in registers in
+ * state 1, as the full model does.  Returns 0: off, 1: active, 2: disabled
+ * after an overflow.  No reference counterpart. */
 int upr_model_split_state(const UprModel* model);
+
+/* The form every op of the handle's most recent forward ran in, in launch
+ * order: 0 = the model dtype's own (exact) kernels, 1 = split tensors, 2 =
+ * split in registers.  Fills names[i] (64 bytes each, nullable) and forms[i]
+ * for i < max_ops and returns the number of ops (0 before the first forward,
+ * -1 for NULL).  No reference counterpart. */
+typedef struct {
+  char name[64];
+  int form;
+} UprOpForm;
+int upr_model_op_forms(const UprModel* model, UprOpForm* out, int max_ops);
 
 /* Per-op profiling of upr_model_forward (no reference counterpart: the
  * reference only brackets whole calls with time.time(), simple_enhance.py:165-179).
@@ -149,6 +169,18 @@ int upr_retinex_decompose_bwd(const void* x, const void* illu, const void* g, vo
 int upr_conv2d_nhwc(const void* x, int B, int H, int W, int Cin, const void* w, const float* bias, int Cout, int kh,
                     int kw, int stride, int pad, int dil, const void* residual, int relu, void* y, int dtype,
                     void* stream);
+
+/* upr_conv2d_nhwc with dtype UPR_F32_SPLIT_REGS runs this with overflow NULL.
+ * Arguments as for UPR_F32 (fp32 NHWC x / residual / y, the same packed fp32
+ * weights; the weight scales are derived from w).  Only the shapes the
+ * split-in-registers kernels take: 3x3, stride 1, pad 1, Cin 32, Cout 32
+ * (residual allowed) or 64 (no residual), Ho >= 4, Wo >= 16; anything else
+ * returns UPR_ERR_UNSUPPORTED (never another kernel).  `overflow` (device
+ * word, nullable) is set to 1 when an input left the fp16 range (|v| >= 65520
+ * or non-finite: the outputs are then void); never cleared. */
+int upr_conv2d_nhwc_regs(const void* x, int B, int H, int W, int Cin, const void* w, const float* bias, int Cout,
+                         int kh, int kw, int stride, int pad, int dil, const void* residual, int relu, void* y,
+                         unsigned* overflow, void* stream);
 
 /* Split-fp16 tensors: C fp32 channels of an NHWC pixel stored as 2C fp16,
  * [hi(C) | lo(C)], hi = (half)v, lo = (half)((v - hi) * 2^11); v = hi + lo *

@@ -418,7 +418,20 @@ int launch_conv_out32(const ConvOp& op, hipStream_t stream) {
   return launch_conv_halo(op, kF16, stream);
 }
 
+static thread_local int t_last_form = 0;
+int conv_last_form() { return t_last_form; }
+void conv_set_last_form(int form) { t_last_form = form; }
+
+int launch_conv_regs(const ConvOp& op, hipStream_t stream) {
+  t_last_form = 0;
+  if (op.nseg != 1 || op.B <= 0 || op.Ho <= 0 || op.Wo <= 0 || op.out32 || op.out2 || !op.seg[0].src) return kErrArg;
+  ConvOp c = op;
+  c.mma16 = 2;
+  return launch_conv_ring32(c, stream);
+}
+
 int launch_conv(const ConvOp& op, int dtype, hipStream_t stream) {
+  t_last_form = 0;
   if (op.nseg < 1 || op.nseg > 4 || op.B <= 0 || op.Ho <= 0 || op.Wo <= 0) return kErrArg;
   if (op.out32 || op.out_s2) return kErrArg;  // launch_conv_out32
   if (op.out2) {

@@ -90,7 +90,10 @@ enum RingFlags : int {
   kRingDil2 = 128, kRingResPre = 256, kRingPool = 512, kRingXPool = 1024, kRingR32 = 2048,
   // timing ablations only (results garbage; UPR_RING_ABL, tools/convbench.py):
   // no ring DMA after the first two steps / no MFMAs / no output stores
-  kRingAblDma = 4096, kRingAblMma = 8192, kRingAblSt = 16384
+  kRingAblDma = 4096, kRingAblMma = 8192, kRingAblSt = 16384,
+  // fp32 ring only: split in registers (ConvOp::mma16) -- the fragments are
+  // split into fp16 (hi, lo) after the LDS read and run on v_mfma_f32_16x16x32_f16
+  kRingMma16 = 32768
 };
 // kRingXPool (fp32 ring): two more K slices after the 3x3 segment, a 1x1 over
 // x and a 1x1 over maxpool3x3(x) (EnhancedFAM branch1 / branch2 composed with
@@ -924,7 +927,16 @@ struct Ring32Cfg {
   // VGPRs (one wave per SIMD: 32 -> 64 fits in 504 registers without spills;
   // the residual variant does not)
   static constexpr bool WREG = NT == 2 || (NT == 4 && !RES);
-  static constexpr int WBYTES = WREG ? 0 : 9 * NB * 32 * 4;  // [tap][n][32 k] fp32
+  // split in registers: the filter registers hold (W_hi, W_lo) fp16 fragments
+  // (the same 8 VGPRs per (slice, tile)), two accumulators per tile
+  static constexpr bool M16 = (FL & kRingMma16) != 0;
+  static_assert(!M16 || WREG, "split in registers: register-resident filters only");
+  // ... 32 -> 64: W_hi (144 registers) stays resident; the 144 of W_lo, the two
+  // accumulator sets and the fragments being split do not fit beside it, so
+  // W_lo lives in LDS as lane-linear fragments [tap][tile][lane] (16 bytes
+  // each) and is read one tap ahead
+  static constexpr bool TAPCH = M16 && NT == 4;
+  static constexpr int WBYTES = TAPCH ? 9 * NT * 1024 : WREG ? 0 : 9 * NB * 32 * 4;  // else [tap][n][32 k] fp32
   static constexpr int EW = RES ? 32 * NB * 4 : HEAD ? 512 : 0;
   static constexpr int E = RES ? NB / 8 : HEAD ? 1 : 0;
   static constexpr int LDS = WBYTES + RA::BYTES + (XP ? RB::BYTES : 0) + 4 * EW;
@@ -962,8 +974,43 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
   const int KT = nu * a.steps;
 
   // filter: lane (fr = n within tile, fg) holds W[nt*16 + fr][tap*32 + fg*8 .. +7]
-  f32x4 wr[K::WREG ? K::NSL : 1][NT][2];
-  if constexpr (K::WREG) {
+  constexpr bool M16 = K::M16;
+  f32x4 wr[K::WREG && !M16 ? K::NSL : 1][NT][2];
+  // split in registers: (W_hi, W_lo) of w s_n, s_n from the row's largest
+  // magnitude (the row is read twice: once for the maximum, once to split);
+  // wsh = log2 s_n of the lane's filter row nt*16 + fr
+  f16x8_t wh[M16 ? K::NSL : 1][NT], wl[M16 && !K::TAPCH ? K::NSL : 1][NT];
+  int wsh[NT];
+  if constexpr (M16) {
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      const float* row = (const float*)op.W + (size_t)(nt * 16 + fr) * op.Kpad + fg * 8;
+      float mx = 0.f;
+#pragma unroll
+      for (int t = 0; t < K::NSL; ++t) {
+        const f32x4 w0 = *(const f32x4*)(row + t * 32), w1 = *(const f32x4*)(row + t * 32 + 4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) mx = fmaxf(mx, fmaxf(__builtin_fabsf(w0[i]), __builtin_fabsf(w1[i])));
+      }
+      mx = fmaxf(mx, __shfl_xor(mx, 16));
+      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      wsh[nt] = split_row_shift(mx);
+      const float wsn = __builtin_ldexpf(1.f, wsh[nt]);
+#pragma unroll
+      for (int t = 0; t < K::NSL; ++t) {
+        const f32x4 w0 = *(const f32x4*)(row + t * 32), w1 = *(const f32x4*)(row + t * 32 + 4);
+        const float v[8] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
+        if constexpr (K::TAPCH) {
+          // (every wave holds the same fragments: wave 0 parks W_lo in LDS)
+          f16x8_t lo;
+          split_w_f32x8(v, wsn, wh[t][nt], lo);
+          if (wave == 0) *(f16x8_t*)(Wl + (t * NT + nt) * 1024 + lane * 16) = lo;
+        } else {
+          split_w_f32x8(v, wsn, wh[t][nt], wl[t][nt]);
+        }
+      }
+    }
+  } else if constexpr (K::WREG) {
 #pragma unroll
     for (int t = 0; t < K::NSL; ++t)
 #pragma unroll
@@ -1029,6 +1076,24 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
   for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
     for (int i = 0; i < 4; ++i) bv[nt][i] = op.bias ? op.bias[nt * 16 + fg * 4 + i] : 0.f;
+  // split in registers: log2 s_n of the lane's accumulator rows (channel nt*16 +
+  // fg*4 + i, held by the lanes with fr = fg*4 + i), four signed bytes per
+  // tile (the 32 -> 64 program has no registers to spare for 16 floats); the
+  // bias enters as bias s_n
+  int esh[M16 ? NT : 1];
+  if constexpr (M16) {
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      esh[nt] = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int sh = __shfl(wsh[nt], fg * 4 + i);
+        esh[nt] |= (sh & 255) << (8 * i);
+        bv[nt][i] = __builtin_ldexpf(bv[nt][i], sh);
+      }
+    }
+  }
+  float bad = 0.f;  // NaN once an accumulator was not finite (ConvOp::ovf, stored after the loop)
   float hw2[NT][4];
   if constexpr (HEAD) {
 #pragma unroll
@@ -1094,6 +1159,26 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
       for (int g = 0; g < NG; ++g) acc[nt][g] = f32x4{bv[nt][0], bv[nt][1], bv[nt][2], bv[nt][3]};
+    // split in registers: acc = hi W_hi + hi W_lo, acc2 = lo W_hi (folded in with 2^-11 below)
+    f32x4 acc2[M16 ? NT : 1][NG];
+    if constexpr (M16) {
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int g = 0; g < NG; ++g) acc2[nt][g] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    // one 32-channel K slice of pixel group g against filter slice t
+    auto mm16 = [&](int t, int g, const f32x4& x0, const f32x4& x1, const f16x8_t (&wlo)[NT]) {
+      const float v[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+      f16x8_t xh, xl;
+      split_f32x8(v, xh, xl);
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        acc[nt][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t][nt], xh, acc[nt][g], 0, 0, 0);
+        acc[nt][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wlo[nt], xh, acc[nt][g], 0, 0, 0);
+        acc2[nt][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t][nt], xl, acc2[nt][g], 0, 0, 0);
+      }
+    };
 #define RING_FENCE __builtin_amdgcn_sched_barrier(0)
 #define RING_LDS_DONE                                                               \
   do {                                                                              \
@@ -1101,7 +1186,44 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
     __builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0); vmcnt / expcnt untouched */ \
     RING_FENCE;                                                                     \
   } while (0)
-    if (s >= 0) {
+    // split in registers, 32 -> 64: the chunk is one fragment (tap c >> 1, pixel
+    // group c & 1: 2 halves, 8 registers, + the tap's W_lo fragments with its
+    // first group; the 12 MFMAs of 16 cycles of a chunk cover the next one's
+    // read latency) instead of a tap row's six
+    constexpr bool TAPCH = K::TAPCH;
+    if constexpr (TAPCH) {
+      if (s >= 0) {
+        static_assert(NG == 2, "chunk index: tap * 2 + group");
+        f32x4 tx[2][2];
+        f16x8_t wlt[2][NT];  // W_lo of tap t in wlt[t & 1] (read with chunk 2t, used by chunks 2t and 2t + 1)
+        auto ldt = [&](int c, f32x4 (&x)[2]) {
+          const int r = (c >> 1) / 3, sc = (c >> 1) % 3, g = c & 1;
+          const unsigned char* xr = ringA + abase + ((4 * kk + 4 + wave - HA + (r - 1) * DIL) & 15) * (RA::RW * 16) +
+                                    (g * 16 + HA + (sc - 1) * DIL) * 16;
+#pragma unroll
+          for (int h = 0; h < 2; ++h) x[h] = *(const f32x4*)(xr + h * RA::PLANE);
+          if (g == 0) {
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+              wlt[(c >> 1) & 1][nt] = *(const f16x8_t*)(Wl + ((c >> 1) * NT + nt) * 1024 + lane * 16);
+          }
+        };
+        auto mmt = [&](int c, const f32x4 (&x)[2]) { mm16(c >> 1, c & 1, x[0], x[1], wlt[(c >> 1) & 1]); };
+        ldt(0, tx[0]);
+        ldt(1, tx[1]);
+        RING_LDS_DONE;
+        mmt(0, tx[0]);
+#pragma unroll
+        for (int c = 1; c < 18; ++c) {
+          RING_FENCE;
+          if (c + 1 < 18) ldt(c + 1, tx[(c + 1) & 1]);
+          RING_FENCE;
+          mmt(c, tx[c & 1]);
+          RING_LDS_DONE;
+        }
+      }
+    }
+    if (s >= 0 && !TAPCH) {
       // chunk = one tap row r: 3 taps x 2 groups x 2 halves of X (+ 3 x NT x 2 of W from LDS)
       // ring row of tap row r (input row y + (r - 1) * DIL); ring column of tap sc below
       auto rowA = [&](int r) { return ((4 * kk + 4 + wave - HA + (r - 1) * DIL) & 15) * (RA::RW * 16); };
@@ -1127,6 +1249,13 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
         }
       };
       auto mm = [&](int r, const f32x4 (&x)[3][NG][2], const f32x4 (&w)[NW][NT][2]) {
+        if constexpr (M16) {
+#pragma unroll
+          for (int sc = 0; sc < 3; ++sc)
+#pragma unroll
+            for (int g = 0; g < NG; ++g) mm16(r * 3 + sc, g, x[sc][g][0], x[sc][g][1], wl[r * 3 + sc]);
+          return;
+        }
 #pragma unroll
         for (int sc = 0; sc < 3; ++sc)
 #pragma unroll
@@ -1188,6 +1317,14 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
               if (dr == 1) ctr[g][h] = xr3[1][g][h];
             }
         }
+        if constexpr (M16) {
+          // the 3x3 max is taken in fp32 as in the exact form, then split
+#pragma unroll
+          for (int g = 0; g < NG; ++g) {
+            mm16(9, g, ctr[g][0], ctr[g][1], wl[K::XP ? 9 : 0]);
+            mm16(10, g, mx[g][0], mx[g][1], wl[K::XP ? 10 : 0]);
+          }
+        } else {
 #pragma unroll
         for (int j = 0; j < 8; ++j)
 #pragma unroll
@@ -1199,6 +1336,7 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
               acc[nt][g] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[10][nt][j >> 2][j & 3], mx[g][j >> 2][j & 3],
                                                                 acc[nt][g], 0, 0, 0);
             }
+        }
       } else {
         mm(2, bx[0], bw[0]);
       }
@@ -1207,6 +1345,21 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
 #undef RING_FENCE
 
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K::G) : "memory");
+    if constexpr (M16) {
+      // accumulator finish: (acc + acc2 2^-11) / s_n.  The range guard looks at
+      // the unscaled sum (v * 0 is NaN exactly when v is not finite), before
+      // the residual and the ReLU, which would hide a NaN or a -inf
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float v = __builtin_fmaf(acc2[nt][g][i], kSplitLoInv, acc[nt][g][i]);
+            bad = __builtin_fmaf(ovalid[g] ? v : 0.f, 0.f, bad);  // stored outputs only
+            acc[nt][g][i] = __builtin_ldexpf(v, -(int)(signed char)(esh[nt] >> (8 * i)));
+          }
+    }
     if constexpr (HEAD) {
 #pragma unroll
       for (int g = 0; g < NG; ++g) {
@@ -1282,6 +1435,10 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
     advance(cc);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if constexpr (M16) {
+    // one plain store after the last step (the steps' vmcnt waits count every memory instruction)
+    if (bad != bad && op.ovf) *op.ovf = 1u;
+  }
 }
 
 static int ring_cus() {
@@ -1467,9 +1624,24 @@ int launch_conv_ring(const ConvOp& op, hipStream_t st) {
   return kErrUnsupported;
 }
 
+// ConvOp::mma16: the split-in-registers program of the same configuration
+// where its filter is register resident, else the exact fp32 program
+template <int MODE, int NB, int FL>
+static int ring32_form(const ConvOp& op, hipStream_t st) {
+  if constexpr (Ring32Cfg<MODE, NB, FL>::WREG) {
+    if (op.mma16) {
+      const int rc = launch_ring32_cfg<MODE, NB, FL | kRingMma16>(op, st);
+      if (rc == kOk) conv_set_last_form(2);
+      return rc;
+    }
+  }
+  if (op.mma16 == 2) return kErrUnsupported;  // that form or nothing
+  return launch_ring32_cfg<MODE, NB, FL>(op, st);
+}
+
 template <int MODE, int NB, int FL>
 static int ring32_relu(const ConvOp& op, hipStream_t st) {
-  return op.relu ? launch_ring32_cfg<MODE, NB, FL | kRingRelu>(op, st) : launch_ring32_cfg<MODE, NB, FL>(op, st);
+  return op.relu ? ring32_form<MODE, NB, FL | kRingRelu>(op, st) : ring32_form<MODE, NB, FL>(op, st);
 }
 
 // fp32: stride-1 3x3 over 32 channels (-> 32 / 64, head), and the split
@@ -1494,7 +1666,7 @@ int launch_conv_ring32(const ConvOp& op, hipStream_t st) {
     if (x1.pre != kPreNone || x2.pre != kPreMaxPool3 || x1.kbase != 288 || x2.kbase != 320 || x1.cs % 4 ||
         x1.coff % 4 || (uintptr_t)x1.src % 16)
       return kErrUnsupported;
-    return launch_ring32_cfg<kRingConv, 32, kRingXPool>(op, st);
+    return ring32_form<kRingConv, 32, kRingXPool>(op, st);
   }
   if (op.nseg != 1) return kErrUnsupported;
   if (op.img_bias || op.scale || op.Kpad != 288 || (op.res1 && op.res2)) return kErrUnsupported;
@@ -1505,8 +1677,8 @@ int launch_conv_ring32(const ConvOp& op, hipStream_t st) {
     if (op.store != kStoreNHWC || op.N != 32 || op.res2 || !op.res1 || !op.relu || op.res1_cs % 4 || op.out_cs % 4 ||
         op.out_coff % 4)
       return kErrUnsupported;
-    return op.pool ? launch_ring32_cfg<kRingConv, 32, kRingDil2 | kRingRes | kRingResPre | kRingRelu | kRingPool>(op, st)
-                   : launch_ring32_cfg<kRingConv, 32, kRingDil2 | kRingRes | kRingResPre | kRingRelu>(op, st);
+    return op.pool ? ring32_form<kRingConv, 32, kRingDil2 | kRingRes | kRingResPre | kRingRelu | kRingPool>(op, st)
+                   : ring32_form<kRingConv, 32, kRingDil2 | kRingRes | kRingResPre | kRingRelu>(op, st);
   }
   if (!ring_seg_ok(s)) return kErrUnsupported;
   if (op.res1) {
@@ -1518,7 +1690,7 @@ int launch_conv_ring32(const ConvOp& op, hipStream_t st) {
   if (op.pool) return kErrUnsupported;
   if (op.store == kStoreHeadIllu) {
     if (op.N != 32 || op.res2 || op.illu_f16 || op.Wo % 8) return kErrUnsupported;
-    return launch_ring32_cfg<kRingHead, 32, 0>(op, st);
+    return ring32_form<kRingHead, 32, 0>(op, st);
   }
   if (op.store != kStoreNHWC || op.out_cs % 4 || op.out_coff % 4) return kErrUnsupported;
   if (op.res2 && op.res2_cs % 4) return kErrUnsupported;

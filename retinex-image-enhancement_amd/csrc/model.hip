@@ -415,6 +415,14 @@ struct UprModel {
   std::atomic<int> split_state{0};
   unsigned* ovf_dev = nullptr;
   volatile unsigned* ovf_host = nullptr;
+  // Split in registers (ConvOp::mma16; env UPR_FP32_SPLIT_REGS, read at
+  // creation): in state 1 every fp32 conv outside the region is offered to its
+  // kernel in that form (the 32-channel row-ring programs take it), guarded by
+  // the same ovf word.  op_forms: the form each op of the latest forward ran in
+  // (upr_model_op_forms)
+  int split_regs = 0;
+  std::vector<int> op_forms;
+  std::mutex forms_mu;
 };
 
 namespace upr {
@@ -1091,6 +1099,10 @@ static int run_forward(UprModel* m, const void* x, int B, int H, int W, void* en
         }
     }
   }
+  // split in registers: decided per forward from the handle's state alone (not
+  // from the region's probe); state 2 and UPR_FP32_SPLIT=0 run every op exact
+  const bool regs_now = m->split_regs && m->ovf_dev && m->split_state.load() == 1 && !(m->ovf_host && *m->ovf_host);
+  std::vector<int> forms(nops, 0);
   // launch op oi on stream st (the caller's stream or the multi-scale side stream)
   auto run_op = [&](size_t oi, hipStream_t st) -> int {
     const Op& o = m->ops[oi];
@@ -1151,8 +1163,14 @@ static int run_forward(UprModel* m, const void* x, int B, int H, int W, void* en
           c.out2 = buf(o.out2); c.out2_cs = L.N;
           c.pre2_scale = fptr(o.ps); c.pre2_shift = fptr(o.ph);
         }
-        if (split_now && o.split_layer >= 0) rc = launch_conv_wide(split_op(o, ho, wo), st);
-        else rc = launch_conv(c, dt, st);
+        if (split_now && o.split_layer >= 0) {
+          rc = launch_conv_wide(split_op(o, ho, wo), st);
+          forms[oi] = 1;
+        } else {
+          if (regs_now && dt == kF32) { c.mma16 = 1; c.ovf = m->ovf_dev; }
+          rc = launch_conv(c, dt, st);
+          forms[oi] = conv_last_form();
+        }
         if (m->prof) {
           // GEMM work of this launch: 2*M*N*K; algorithmic bytes: every source read once,
           // weights once, residuals once, output written once
@@ -1186,6 +1204,7 @@ static int run_forward(UprModel* m, const void* x, int B, int H, int W, void* en
         lvl_dims(o.level, h, w);
         const int C = buf_geom(o.in, m->use_aspp).C;
         rc = launch_split_f32((const float*)buf(o.in), buf(o.out), (size_t)B * h * w, C, m->ovf_dev, st);
+        forms[oi] = 1;
         if (m->prof) m->cur_bytes[oi] = 2.0 * B * h * w * C * 4.0;
         break;
       }
@@ -1280,7 +1299,11 @@ static int run_forward(UprModel* m, const void* x, int B, int H, int W, void* en
     }
     for (size_t i = 0; i < nops; ++i) { m->st_flops[i] += m->cur_flops[i]; m->st_bytes[i] += m->cur_bytes[i]; }
   }
-  if (split_now)  // range guard: looked at when the next forward starts, no wait here
+  {
+    std::lock_guard<std::mutex> lk(m->forms_mu);
+    m->op_forms = forms;
+  }
+  if (split_now || regs_now)  // range guard: looked at when the next forward starts, no wait here
     UPR_CHECK_HIP(hipMemcpyAsync((void*)m->ovf_host, m->ovf_dev, sizeof(unsigned), hipMemcpyDeviceToHost, st));
   if (dt == kF16 && !(m->flags & UPR_MODEL_HEAD_ONLY)) {
     // illumination in the model dtype
@@ -1394,8 +1417,14 @@ int upr_model_create(const UprTensorDesc* params, int n_params, int use_preact, 
   // (read here, per handle) keeps the fp32 MFMA kernels everywhere
   const char* se = getenv("UPR_FP32_SPLIT");
   const bool split_env = !(se && *se && atoi(se) == 0);
-  if (split_env && dtype == UPR_F32 && !m->use_preact && !m->use_aspp && !(flags & UPR_MODEL_HEAD_ONLY))
-    m->split_state.store(1);
+  // (a head-only handle has no region op, but its FAM convs run split in
+  // registers in state 1, as the full model's do: multi_scale_enhance stays
+  // bit-equal to the fused forward)
+  if (split_env && dtype == UPR_F32 && !m->use_preact && !m->use_aspp) m->split_state.store(1);
+  // UPR_FP32_SPLIT_REGS=0 keeps the split-in-registers ops on the fp32 MFMA
+  // kernels while the region stays split
+  const char* sr = getenv("UPR_FP32_SPLIT_REGS");
+  m->split_regs = !(sr && *sr && atoi(sr) == 0);
   int rc = build_model(m.get(), P);
   if (rc == kOk && m->split_state.load() == 1) {
     hipError_t e = hipMalloc((void**)&m->ovf_dev, 256);
@@ -1477,6 +1506,19 @@ long long upr_model_forks(const UprModel* model) { return model ? model->forks.l
 
 int upr_model_split_state(const UprModel* model) { return model ? model->split_state.load() : 0; }
 
+int upr_model_op_forms(const UprModel* model, UprOpForm* out, int max_ops) {
+  if (!model) return -1;
+  UprModel* m = const_cast<UprModel*>(model);
+  std::lock_guard<std::mutex> lk(m->forms_mu);
+  const size_t n = m->op_forms.size();
+  for (size_t i = 0; out && i < n && (int)i < max_ops; ++i) {
+    memset(&out[i], 0, sizeof(out[i]));
+    strncpy(out[i].name, m->ops[i].name.c_str(), sizeof(out[i].name) - 1);
+    out[i].form = m->op_forms[i];
+  }
+  return (int)n;
+}
+
 void upr_model_destroy(UprModel* model) {
   if (!model) return;
   upr_model_profile(model, 0);
@@ -1505,6 +1547,9 @@ int upr_conv2d_nhwc(const void* x, int B, int H, int W, int Cin, const void* w, 
                     void* stream) {
   if (!x || !w || !y || B <= 0 || H <= 0 || W <= 0 || Cin % 32 || Cout % 32 || Cin <= 0 || Cout <= 0) return UPR_ERR_ARG;
   if (kh <= 0 || kw <= 0 || stride <= 0 || dil <= 0 || pad < 0) return UPR_ERR_ARG;
+  if (dtype == UPR_F32_SPLIT_REGS)
+    return upr_conv2d_nhwc_regs(x, B, H, W, Cin, w, bias, Cout, kh, kw, stride, pad, dil, residual, relu, y, nullptr,
+                                stream);
   if (dtype != UPR_F32 && dtype != UPR_F16 && dtype != UPR_F32_SPLIT) return UPR_ERR_ARG;
   const int Ho = (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1;
   const int Wo = (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
@@ -1545,6 +1590,33 @@ int upr_conv2d_nhwc(const void* x, int B, int H, int W, int Cin, const void* w, 
   else { c.res2 = residual; c.res2_cs = Cout; }
   c.out = y; c.out_cs = Cout; c.out_coff = 0; c.store = kStoreNHWC;
   return launch_conv(c, dtype, (hipStream_t)stream);
+}
+
+int upr_conv2d_nhwc_regs(const void* x, int B, int H, int W, int Cin, const void* w, const float* bias, int Cout,
+                         int kh, int kw, int stride, int pad, int dil, const void* residual, int relu, void* y,
+                         unsigned* overflow, void* stream) {
+  if (!x || !w || !y || B <= 0 || H <= 0 || W <= 0 || Cin % 32 || Cout % 32 || Cin <= 0 || Cout <= 0) return UPR_ERR_ARG;
+  if (kh <= 0 || kw <= 0 || stride <= 0 || dil <= 0 || pad < 0) return UPR_ERR_ARG;
+  const int Ho = (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1;
+  const int Wo = (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
+  if (Ho <= 0 || Wo <= 0) return UPR_ERR_SHAPE;
+  // the UPR_F32 op of upr_conv2d_nhwc, offered in the split-in-registers form to
+  // the kernels that have it and to nothing else
+  ConvOp c;
+  memset(&c, 0, sizeof(c));
+  c.nseg = 1;
+  ConvSeg& s = c.seg[0];
+  s.src = x; s.C = Cin; s.cs = Cin; s.coff = 0; s.Hin = H; s.Win = W;
+  s.kh = kh; s.kw = kw; s.stride = stride; s.pad = pad; s.dil = dil; s.pre = kPreNone; s.kbase = 0;
+  c.B = B; c.Ho = Ho; c.Wo = Wo; c.N = Cout; c.Kpad = kh * kw * Cin;
+  c.W = w; c.bias = bias; c.relu = relu;
+  // (the row ring adds its residual after the ReLU; with a ReLU its pre-ReLU
+  // residual program is the dilation-2 FAM part, which this entry does not offer)
+  if (relu && residual) return UPR_ERR_UNSUPPORTED;
+  c.res2 = residual; c.res2_cs = Cout;
+  c.out = y; c.out_cs = Cout; c.out_coff = 0; c.store = kStoreNHWC;
+  c.mma16 = 1; c.ovf = overflow;
+  return launch_conv_regs(c, (hipStream_t)stream);
 }
 
 size_t upr_pack_split_f32(const float* w, int Cout, int Cin, int kh, int kw, void* out, size_t out_bytes) {

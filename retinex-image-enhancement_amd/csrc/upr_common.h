@@ -129,12 +129,61 @@ struct ConvOp {
   void* split_out; int split_cs, split_lo;
   float* out_f32; int out_f32_cs;
   int split_res;
+  // Split in registers (fp32 row ring only; 0 elsewhere):
+  // tensors, DMA and LDS stay fp32, each 8-channel fragment is split into (hi,
+  // lo) fp16 after its LDS read (split_f32x8) and the products run on the fp16
+  // MFMA unit as hi W_hi + hi W_lo + (lo W_hi) 2^-11 with per-output-channel
+  // power-of-two weight scales.  1: a kernel that does not take the op in this
+  // form runs its exact fp32 form (conv_last_form tells which ran); 2: it
+  // answers kErrUnsupported instead (launch_conv_regs).  ovf as above: set
+  // when an accumulator is not finite (an input left the fp16 range).
+  // (placed in the padding before ovf: the struct, and with it every kernel
+  // argument block, keeps its layout)
+  int mma16;
   unsigned* ovf;
 };
 
 // 2^11 / 2^-11: the scale of the lo half of a split-fp16 value (ConvOp::split_out)
 constexpr float kSplitLoScale = 2048.f;
 constexpr float kSplitLoInv = 1.f / 2048.f;
+
+#ifdef __HIPCC__
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
+// 8 fp32 values -> split fp16: hi = (half)v, lo = (half)((v - hi) 2^11),
+// plain round-to-nearest casts (fp16 subnormals kept).  |v| >= 65520 gives
+// hi = +-inf and a non-finite lo: the caller's accumulators go non-finite.
+__device__ __forceinline__ void split_f32x8(const float (&v)[8], f16x8_t& hi, f16x8_t& lo) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const half_t h = (half_t)v[i];
+    hi[i] = h;
+    lo[i] = (half_t)__builtin_fmaf((float)h, -kSplitLoScale, v[i] * kSplitLoScale);
+  }
+}
+// weights: w s_n -> W_hi = (half)(w s), W_lo = (half)(w s - W_hi)
+__device__ __forceinline__ void split_w_f32x8(const float (&v)[8], float s, f16x8_t& hi, f16x8_t& lo) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const float w = v[i] * s;
+    const half_t h = (half_t)w;
+    hi[i] = h;
+    lo[i] = (half_t)(w - (float)h);
+  }
+}
+#endif
+// The exponent sh of the power of two s = 2^sh with max|w| s in [2^14, 2^15)
+// for a weight row of largest magnitude mx (pack_split's rule: 0 for a zero or
+// non-finite row, clamped to +-100); host and device
+__host__ __device__ inline int split_row_shift(float mx) {
+  int sh = 0;
+  if (mx > 0.f && mx < __builtin_inff()) {
+    int e;
+    (void)__builtin_frexpf(mx, &e);
+    sh = 15 - e;
+    sh = sh < -100 ? -100 : sh > 100 ? 100 : sh;
+  }
+  return sh;
+}
 
 // fp32 NHWC [npix][C] <-> split fp16 [npix][2C] (C % 8 == 0; model.hip)
 int launch_split_f32(const float* x, void* y, size_t npix, int C, unsigned* ovf, hipStream_t st);
@@ -150,6 +199,15 @@ int launch_conv_s2dg(const ConvOp& op, hipStream_t stream, bool probe = false);
 int launch_conv_pw(const ConvOp& op, hipStream_t stream, bool probe = false);
 
 int launch_conv(const ConvOp& op, int dtype, hipStream_t stream);
+// the form the calling thread's latest launch_conv ran in: 0 = the dtype's own
+// kernels, 2 = split in registers (ConvOp::mma16)
+int conv_last_form();
+void conv_set_last_form(int form);
+// an fp32 op in the split-in-registers form only (sets mma16 = 2): kOk, or
+// kErrUnsupported when no kernel takes it in that form
+int launch_conv_regs(const ConvOp& op, hipStream_t stream);
+
+int launch_conv_ring32(const ConvOp& op, hipStream_t st);
 // fp16 wide-tile convs (conv_wide.hip), also the split-fp16 form of fp32 convs
 // (ConvOp::split_out); probe: only answer kOk / kErrUnsupported
 int launch_conv_wide(const ConvOp& op, hipStream_t st, bool probe = false);

@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("UPR_LIB", os.path.join(os.path.dirname(_HERE), "lib",
 UPR_F32 = 0
 UPR_F16 = 1
 UPR_F32_SPLIT = 2
+UPR_F32_SPLIT_REGS = 3
 UPR_MODEL_IENET_ONLY = 1
 UPR_MODEL_HEAD_ONLY = 2
 
@@ -39,6 +40,11 @@ class UprOpStat(ctypes.Structure):
                 ("bytes", ctypes.c_double)]
 
 
+class UprOpForm(ctypes.Structure):
+    _fields_ = [("name", ctypes.c_char * 64),
+                ("form", ctypes.c_int)]
+
+
 UPR_OP_CONV_IGEMM = 0
 UPR_OP_OTHER = 1
 UPR_CALIB_MFMA_F16 = 0
@@ -57,11 +63,14 @@ SIGNATURES = {
     "upr_model_destroy": (None, [c_void_p]),
     "upr_model_forks": (ctypes.c_longlong, [c_void_p]),
     "upr_model_split_state": (c_int, [c_void_p]),
+    "upr_model_op_forms": (c_int, [c_void_p, ctypes.POINTER(UprOpForm), c_int]),
     "upr_model_profile": (c_int, [c_void_p, c_int]),
     "upr_model_profile_read": (c_int, [c_void_p, ctypes.POINTER(UprOpStat), c_int, ctypes.POINTER(c_int)]),
     "upr_status_string": (ctypes.c_char_p, [c_int]),
     "upr_conv2d_nhwc": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                 c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "upr_conv2d_nhwc_regs": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                     c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "upr_split_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p]),
     "upr_unsplit_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "upr_pack_split_f32": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),

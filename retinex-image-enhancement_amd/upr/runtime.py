@@ -126,6 +126,14 @@ class ModelHandle:
         """Split-fp16 region of an fp32 model: 0 off, 1 active, 2 disabled after a range overflow."""
         return int(self._lib.upr_model_split_state(self._h))
 
+    def op_forms(self):
+        """(name, form) per op of the most recent forward, in launch order: 0 the
+        model dtype's own kernels, 1 split-fp16 tensors, 2 split in registers."""
+        n = int(self._lib.upr_model_op_forms(self._h, None, 0))
+        arr = (L.UprOpForm * max(n, 1))()
+        n = int(self._lib.upr_model_op_forms(self._h, arr, n))
+        return [(a.name.decode(), int(a.form)) for a in arr[:n]]
+
     def profile_read(self):
         """Per-op stats (launch order): list of dicts name/kind/calls/ms/flops/bytes."""
         n = ctypes.c_int(0)
@@ -311,6 +319,32 @@ def conv2d_nhwc(x, w_packed, bias, kh, kw, stride=1, pad=0, dil=1, residual=None
                                      stride, pad, dil, _ptr(residual), int(bool(relu)), _ptr(y),
                                      dtype_code(x.dtype), _stream(x.device))
     L.check(rc, "upr_conv2d_nhwc")
+    return y
+
+
+def conv2d_nhwc_regs(x, w_packed, bias, kh, kw, stride=1, pad=0, dil=1, residual=None, relu=False, overflow=None):
+    """conv2d_nhwc for fp32 tensors in the split-in-registers form (fp16 MFMAs on
+    fragments split after the LDS read), and in no other: shapes its kernels do
+    not take raise UprError (UPR_ERR_UNSUPPORTED).
+
+    overflow: optional int32 device tensor of one element, set to 1 when an
+    input was outside the fp16 range (the output is then void)."""
+    _require_device(x)
+    if x.dtype != torch.float32:
+        raise ValueError("conv2d_nhwc_regs expects float32 tensors")
+    x = x.contiguous()
+    B, H, W, Cin = x.shape
+    Cout = w_packed.shape[0]
+    Ho = (H + 2 * pad - dil * (kh - 1) - 1) // stride + 1
+    Wo = (W + 2 * pad - dil * (kw - 1) - 1) // stride + 1
+    y = torch.empty((B, Ho, Wo, Cout), dtype=x.dtype, device=x.device)
+    if residual is not None:
+        residual = residual.contiguous()
+    with torch.cuda.device(x.device):
+        rc = L.lib().upr_conv2d_nhwc_regs(_ptr(x), B, H, W, Cin, _ptr(w_packed.contiguous()), _ptr(bias), Cout, kh, kw,
+                                          stride, pad, dil, _ptr(residual), int(bool(relu)), _ptr(y), _ptr(overflow),
+                                          _stream(x.device))
+    L.check(rc, "upr_conv2d_nhwc_regs")
     return y
 
 

@@ -5,6 +5,9 @@ Times the conv kernels on the UP-Retinex layer shapes in isolation (HIP events
 on the current stream), for tuning and for per-kernel rocprofv3 --pmc passes:
 
   python tools/convbench.py --dtype fp16 --shapes dec1,bneck --iters 20
+
+--dtype fp32regs: fp32 tensors in the split-in-registers form
+(upr_conv2d_nhwc_regs; only the shapes its kernels take: dec1, dec1p, fam_h).
 """
 import argparse
 import os
@@ -54,7 +57,7 @@ SHAPES = {
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--dtype", choices=["fp32", "fp16"], default="fp16")
+    ap.add_argument("--dtype", choices=["fp32", "fp16", "fp32regs"], default="fp16")
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--bufs", type=int, default=1,
@@ -74,13 +77,14 @@ def main():
         Wo = (W + 2 * p - d * (k - 1) - 1) // s + 1
         r = torch.randn(B, Ho, Wo, Co, device=dev, generator=g).to(dt) if res else None
         relu = r is None  # residual shapes: plain conv + skip add (the UpBlock epilogue)
+        conv = runtime.conv2d_nhwc_regs if args.dtype == "fp32regs" else runtime.conv2d_nhwc
         for _ in range(3):
-            runtime.conv2d_nhwc(x, w, b, k, k, s, p, d, residual=r, relu=relu)
+            conv(x, w, b, k, k, s, p, d, residual=r, relu=relu)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for i in range(args.iters):
-            runtime.conv2d_nhwc(xs[i % args.bufs], w, b, k, k, s, p, d, residual=r, relu=relu)
+            conv(xs[i % args.bufs], w, b, k, k, s, p, d, residual=r, relu=relu)
         e1.record()
         torch.cuda.synchronize()
         ms = e0.elapsed_time(e1) / args.iters
