@@ -1,5 +1,6 @@
-// Shared by the training units (train.hip, train_small.hip, train_wgrad.hip):
-// the strided-view kernel arguments, launch helpers, vector typedefs and the
+// Shared by the training units (train.hip, train_fam.hip, train_optim.hip,
+// train_small.hip, train_wgrad.hip): the strided-view kernel arguments, launch
+// helpers, vector typedefs, the device helpers two units use, and the
 // prototypes of every function one training unit calls in another.
 //
 // Layout: activations are addressed through UprView strides (NCHW inputs,
@@ -80,6 +81,27 @@ static inline int grid_for(long long n, int per = 256, int cap = 65536) {
 #define ST(s) ((hipStream_t)(s))
 
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+template <int NV>
+__device__ __forceinline__ void block_sum_atomic(double (&v)[NV], double* dst[NV]) {
+  __shared__ double sm[NV][256];
+#pragma unroll
+  for (int k = 0; k < NV; ++k) sm[k][threadIdx.x] = v[k];
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) {
+#pragma unroll
+      for (int k = 0; k < NV; ++k) sm[k][threadIdx.x] += sm[k][threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+      if (dst[k]) atomicAdd(dst[k], sm[k][0]);
+  }
+  __syncthreads();
+}
 
 // train_small.hip: pixel-tiled / MFMA forms of the small-channel convs
 int small_conv_fwd(const UprView* xv, int B, int H, int W, int Cin, const float* w, const float* bias, int Cout,
