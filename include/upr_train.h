@@ -200,6 +200,12 @@ int upr_t_unpack_grad(const float* gp, float* g, int Co, int Ci, int kh, int kw,
  * a stride-2 conv as a stride-1 conv over z). */
 int upr_t_zero_upsample(const float* dy, int B, int Ho, int Wo, int C, int dy_cs, int dy_coff, float* z,
                         void* stream);
+/* upr_t_zero_upsample16 from the gradient's compact fp16 copy dy16. */
+int upr_t_zero_upsample16h(const void* dy16, int B, int Ho, int Wo, int C, void* z16, void* stream);
+/* upr_t_zero_upsample with an fp16 result z16 [B,2Ho,2Wo,C] (dy rounded to
+ * fp16: the autocast stride-2 input-gradient conv's operand); C % 8 == 0. */
+int upr_t_zero_upsample16(const float* dy, int B, int Ho, int Wo, int C, int dy_cs, int dy_coff, void* z16,
+                          void* stream);
 
 /* ---- BatchNorm2d, training mode (nn.BatchNorm2d, model.py:106-162,196-229) -- */
 /* acc[2C] = (sum x, sum x^2) per channel of x[M][cs], overwritten (acc:
@@ -281,12 +287,6 @@ int upr_t_chan_sum16(const void* g16, int M, int C, float* out, int accumulate, 
 /* upr_t_chan_sum16 over a channel slice of a wider fp16 copy: g16 points at the
  * slice's first channel, cs is the copy's channel stride. */
 int upr_t_chan_sum16s(const void* g16, int M, int C, int cs, float* out, int accumulate, double* ws, void* stream);
-/* upr_t_zero_upsample16 from the gradient's compact fp16 copy dy16. */
-int upr_t_zero_upsample16h(const void* dy16, int B, int Ho, int Wo, int C, void* z16, void* stream);
-/* upr_t_zero_upsample with an fp16 result z16 [B,2Ho,2Wo,C] (dy rounded to
- * fp16: the autocast stride-2 input-gradient conv's operand); C % 8 == 0. */
-int upr_t_zero_upsample16(const float* dy, int B, int Ho, int Wo, int C, int dy_cs, int dy_coff, void* z16,
-                          void* stream);
 /* Doubles of `acc` that upr_t_bn_stats / upr_t_bn_bwd_reduce / upr_t_bn_bwd_fused
  * need (and of `ws` for upr_t_chan_sum_ws): acc[0, 2C) receives the per-channel
  * sums, the rest holds the per-block partial sums of the two-stage reduction
@@ -315,6 +315,14 @@ int upr_t_relu_mask16h(float* g, int g_cs, int g_coff, const void* y16, int y16_
                        int write32, void* stream);
 /* dst (+)= src, any layouts (NCHW <-> NHWC, concat slices). */
 int upr_t_copy(const UprView* src, const UprView* dst, int B, int H, int W, int C, int accumulate, void* stream);
+/* upr_t_copy also writing the fp16 copy of the result at
+ * dst16[pixel * dst16_cs + c] (dst16 points at the slice's first channel of
+ * a [B][H][W][dst16_cs] fp16 concat): 4-channel views only, else
+ * UPR_ERR_UNSUPPORTED (nothing launched).  accumulate 2: the fp16 copy only
+ * (dst's fp32 untouched) -- for a concat whose every reader takes its fp16
+ * copy. */
+int upr_t_copy16(const UprView* src, const UprView* dst, int B, int H, int W, int C, int accumulate, void* dst16,
+                 int dst16_cs, void* stream);
 /* n contiguous elements.  op 0: out = sigmoid(a); op 1: out = a*b*(1-b)
  * (sigmoid backward, b = sigmoid output); op 2: out = a*mask/(1-p) with
  * mask_out[i] = hash(seed, i) >= p (nn.Dropout(p) train); op 3: out =
@@ -323,6 +331,9 @@ int upr_t_copy(const UprView* src, const UprView* dst, int B, int H, int W, int 
  * out may alias a. */
 int upr_t_pointwise(const float* a, const float* b, float* out, size_t n, int op, const uint8_t* mask_in,
                     uint8_t* mask_out, float p, uint64_t seed, void* stream);
+/* out = a + b (n floats) and out16 = (half)out; n % 4 == 0, 16-byte aligned
+ * fp32 / 8-byte aligned fp16, else UPR_ERR_UNSUPPORTED. */
+int upr_t_add16(const float* a, const float* b, float* out, size_t n, void* out16, void* stream);
 
 /* ---- pooling / resampling ---------------------------------------------- */
 /* nn.MaxPool2d(k, s, p) forward / backward (backward recomputes the argmax
@@ -357,25 +368,20 @@ int upr_t_maxpool_bwd_code16(const unsigned char* code, const UprView* dy, int B
 /* upr_t_maxpool16_code: y->data NULL writes the fp16 copy y16 only (the pooled values are fp16 values). */
 int upr_t_maxpool16_code(const void* x16, int B, int H, int W, int C, int k, int s, int p, const UprView* y, int Ho,
                          int Wo, unsigned char* code, void* y16, void* stream);
-/* upr_t_copy / upr_t_bilinear also writing the fp16 copy of the result at
- * dst16[pixel * dst16_cs + c] (dst16 points at the slice's first channel of
- * a [B][H][W][dst16_cs] fp16 concat): 4-channel views only, else
- * UPR_ERR_UNSUPPORTED (nothing launched).  accumulate 2: the fp16 copy only
- * (dst's fp32 untouched) -- for a concat whose every reader takes its fp16
- * copy. */
-int upr_t_copy16(const UprView* src, const UprView* dst, int B, int H, int W, int C, int accumulate, void* dst16,
-                 int dst16_cs, void* stream);
-int upr_t_bilinear16(const UprView* x, int B, int H, int W, int C, const UprView* y, int Ho, int Wo, int accumulate,
-                     void* y16, int y16_cs, void* stream);
-/* out = a + b (n floats) and out16 = (half)out; n % 4 == 0, 16-byte aligned
- * fp32 / 8-byte aligned fp16, else UPR_ERR_UNSUPPORTED. */
-int upr_t_add16(const float* a, const float* b, float* out, size_t n, void* out16, void* stream);
 /* F.interpolate(mode='bilinear', align_corners=False) H x W -> Ho x Wo
  * (scale = in/out per axis) and its backward (dx accumulated, atomics). */
 int upr_t_bilinear(const UprView* x, int B, int H, int W, int C, const UprView* y, int Ho, int Wo, int accumulate,
                    void* stream);
 int upr_t_bilinear_bwd(const UprView* dy, int B, int H, int W, int C, int Ho, int Wo, const UprView* dx,
                        void* stream);
+/* upr_t_bilinear also writing the fp16 copy of the result at
+ * y16[pixel * y16_cs + c] (y16 points at the slice's first channel of a
+ * [B][Ho][Wo][y16_cs] fp16 concat): 4-channel views only, else
+ * UPR_ERR_UNSUPPORTED (nothing launched).  accumulate 2: the fp16 copy only
+ * (y's fp32 untouched) -- for a concat whose every reader takes its fp16
+ * copy. */
+int upr_t_bilinear16(const UprView* x, int B, int H, int W, int C, const UprView* y, int Ho, int Wo, int accumulate,
+                     void* y16, int y16_cs, void* stream);
 /* out[B][C] (+)= scale * sum over pixels (AdaptiveAvgPool2d(1) with scale = 1/HW). */
 int upr_t_pixel_sum(const float* x, int B, int HW, int C, int cs, int coff, float scale, float* out, int accumulate,
                     void* stream);

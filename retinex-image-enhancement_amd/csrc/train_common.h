@@ -1,7 +1,9 @@
-// Shared by the training units (train.hip, train_fam.hip, train_optim.hip,
-// train_small.hip, train_wgrad.hip): the strided-view kernel arguments, launch
-// helpers, vector typedefs, the device helpers two units use, and the
-// prototypes of every function one training unit calls in another.
+// Shared by the training units (train_conv.hip, train_bn.hip,
+// train_pointwise.hip, train_resample.hip, train_loss.hip, train_fam.hip,
+// train_optim.hip, train_small.hip, train_wgrad.hip): the strided-view kernel
+// arguments, launch helpers, vector typedefs, the device helpers two units
+// use, and the prototypes of every function one training unit calls in
+// another.
 //
 // Layout: activations are addressed through UprView strides (NCHW inputs,
 // NHWC activations, channel slices of concat buffers).  Everything computes in
@@ -60,6 +62,22 @@ __device__ __forceinline__ float4 ld4f(const half_t* p) {
   return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
 }
 
+// thread i of a V4 kernel over [B][H][W][CV * 4] -> pixel (b, y, x) and the first of its 4 channels
+__device__ __forceinline__ void dec4(int i, int CV, int W, int H, int& b, int& y, int& x, int& c) {
+  c = (i % CV) * 4;
+  int r = i / CV;
+  x = r % W;
+  r /= W;
+  y = r % H;
+  b = r / H;
+}
+
+// d16 (nullable): fp16 copy of the result at d16[pixel * cs16 + c] (pixel = (b*H + y)*W + x)
+__device__ __forceinline__ void store16(half_t* d16, int cs16, int pix, int c, float4 v) {
+  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+  *(h4*)(d16 + (size_t)pix * cs16 + c) = h4{(half_t)v.x, (half_t)v.y, (half_t)v.z, (half_t)v.w};
+}
+
 static V4 mkv4(const UprView* u) {
   V4 v;
   v.d = (float*)u->data;
@@ -116,7 +134,7 @@ int small_conv_dgrad_c3_16(const void* dy16, int B, int H, int W, const float* w
 int small_conv_wgrad(const UprView* xv, const UprView* dyv, int B, int H, int W, int Cin, int Ho, int Wo, int Cout,
                      int kh, int kw, int stride, int pad, int dil, float* dw, float* dbias, hipStream_t st,
                      const UprView* ymask = nullptr);
-// train_wgrad.hip: split-K GEMM weight gradient (train.hip's conv_wgrad_kernel takes the shapes it does not)
+// train_wgrad.hip: split-K GEMM weight gradient (train_conv.hip's conv_wgrad_kernel takes the shapes it does not)
 int wgrad_gemm(const float* x, int B, int H, int W, int Cin, int x_cs, int x_coff, const float* dy, int Ho, int Wo,
                int Cout, int dy_cs, int dy_coff, int kh, int kw, int stride, int pad, int dil, float* dwp,
                hipStream_t st, int torch_ci = 0);

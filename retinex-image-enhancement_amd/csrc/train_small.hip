@@ -575,7 +575,7 @@ int small_conv_dgrad_c3_16(const void* dy16, int B, int H, int W, const float* w
 }
 
 // ---------------------------------------------------------------------------
-// host entries (called from train.hip's upr_t_conv_direct*; kErrUnsupported
+// host entries (called from train_conv.hip's upr_t_conv_direct*; kErrUnsupported
 // sends the caller to the generic kernels)
 // ---------------------------------------------------------------------------
 int small_conv_fwd(const UprView* xv, int B, int H, int W, int Cin, const float* w, const float* bias, int Cout,

@@ -820,7 +820,7 @@ int wgrad16_gemm(const void* x16, int B, int H, int W, int Cin, const float* dy,
   return wgrad16_nr<32>(a, dwp, st, torch_ci);
 }
 
-// Entry from train.hip's upr_t_conv_wgrad (same contract: dwp += ...).
+// Entry from train_conv.hip's upr_t_conv_wgrad (same contract: dwp += ...).
 int wgrad_gemm(const float* x, int B, int H, int W, int Cin, int x_cs, int x_coff, const float* dy, int Ho, int Wo,
                int Cout, int dy_cs, int dy_coff, int kh, int kw, int stride, int pad, int dil, float* dwp,
                hipStream_t st, int torch_ci) {
