@@ -245,9 +245,9 @@ int upr_t_bn_bwd_apply(const float* g, int g_cs, int g_coff, const float* x, int
  * consumer ReLU of a relu(bn(x)) folded in: g counts only where bn(x) > 0,
  * recomputed from x with the forward's expression (so no separate ReLU-mask
  * pass), and (dx16 non-NULL) a compact [M][C] fp16 copy of dx for the
- * autocast input-gradient conv that consumes it.  acc: 2C doubles of scratch
- * (zeroed here).  Needs C % 4 == 0, C <= 1024, 16-byte aligned rows;
- * UPR_ERR_UNSUPPORTED otherwise (the caller takes the separate kernels). */
+ * autocast input-gradient conv that consumes it.  acc: scratch of
+ * upr_t_reduce_acc_doubles(C) doubles (overwritten here).  Needs C % 4 == 0,
+ * C <= 1024, 16-byte aligned rows; UPR_ERR_UNSUPPORTED otherwise (the caller takes the separate kernels). */
 int upr_t_bn_bwd_fused(const float* g, int g_cs, int g_coff, const float* x, int x_cs, const float* mean,
                        const float* invstd, const float* gamma, const float* beta, int relu, int M, int C,
                        double* acc, float* dgamma, float* dbeta, float* dx, int dx_cs, int dx_coff, int accumulate,
@@ -521,9 +521,11 @@ int upr_t_sqsum(const float* g, size_t n, double* acc, void* stream);
 /* One Adam step over a flat parameter buffer with the clip_grad_norm_(max_norm)
  * coefficient computed on the device from sqsum: g' = g*min(1, max_norm/(sqrt(sqsum)+1e-6))
  * + wd*p; m,v moments; bias-corrected update (train.py:84-103, Adam L2 decay).
- * norm_out (nullable) receives sqrt(sqsum). */
+ * norm_out (nullable) receives sqrt(sqsum).  beta1 / beta2 are doubles, as
+ * torch's are: 1 - beta and the bias corrections 1 - beta^step are formed in
+ * double and rounded once (in fp32, 1 - 0.999f is 1.3e-5 off 0.001). */
 int upr_t_adam(float* p, const float* g, float* m, float* v, size_t n, const double* sqsum, float max_norm, float lr,
-               float beta1, float beta2, float eps, float weight_decay, int step, float* norm_out, void* stream);
+               double beta1, double beta2, float eps, float weight_decay, int step, float* norm_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -33,18 +33,17 @@ __global__ __launch_bounds__(256) void unscale_kernel(float* __restrict__ g, lon
 
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, long long n, const double* __restrict__ sq, float max_norm,
-                            float lr, float b1, float b2, float eps, float wd, float bc1, float bc2s,
-                            float* norm_out) {
+                            float step, float b1, float b2, float omb1, float omb2, float eps, float wd,
+                            float bc2s, float* norm_out) {
   const float norm = (float)sqrt(*sq);
   float coef = 1.f;
   if (max_norm > 0.f) coef = fminf(max_norm / (norm + 1e-6f), 1.f);
   if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) *norm_out = norm;
-  const float step = lr / bc1;
   GSTRIDE(i, n) {
     const float pv = p[i];
     const float gv = g[i] * coef + wd * pv;
-    const float mv = b1 * m[i] + (1.f - b1) * gv;
-    const float vv = b2 * v[i] + (1.f - b2) * gv * gv;
+    const float mv = b1 * m[i] + omb1 * gv;
+    const float vv = b2 * v[i] + omb2 * gv * gv;
     m[i] = mv;
     v[i] = vv;
     p[i] = pv - step * mv / (sqrtf(vv) / bc2s + eps);
@@ -72,12 +71,16 @@ int upr_t_unscale(float* g, size_t n, const float* scale, float* found_inf, void
 }
 
 int upr_t_adam(float* p, const float* g, float* m, float* v, size_t n, const double* sqsum, float max_norm, float lr,
-               float beta1, float beta2, float eps, float weight_decay, int step, float* norm_out, void* stream) {
+               double beta1, double beta2, float eps, float weight_decay, int step, float* norm_out, void* stream) {
   if (!p || !g || !m || !v || !sqsum || step <= 0) return UPR_ERR_ARG;
-  const float bc1 = 1.f - powf(beta1, (float)step);
-  const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
+  // torch.optim.Adam keeps the betas, 1 - beta and the bias corrections in
+  // double and rounds each once: 1.f - (float)0.999 is 1.3e-5 off 0.001, and
+  // so was every v
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2s = sqrt(1.0 - pow(beta2, (double)step));
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for((long long)n)), dim3(256), 0, ST(stream), p, g, m, v, (long long)n,
-                     sqsum, max_norm, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, norm_out);
+                     sqsum, max_norm, (float)((double)lr / bc1), (float)beta1, (float)beta2, (float)(1.0 - beta1),
+                     (float)(1.0 - beta2), eps, weight_decay, (float)bc2s, norm_out);
   LAUNCH_CHECK();
 }
 

@@ -132,7 +132,7 @@ UPR_T_STORE_X16_STRIDED = 32
 
 _vp = ctypes.POINTER(UprView)
 c_u64, c_i64p = ctypes.c_uint64, ctypes.c_void_p
-_i, _p, _f = c_int, c_void_p, c_float
+_i, _p, _f, _d = c_int, c_void_p, c_float, ctypes.c_double
 
 # mirrors include/upr_train.h exactly
 SIGNATURES.update({
@@ -232,7 +232,7 @@ SIGNATURES.update({
     "upr_t_loss_total": (_i, [_p, _f, _f, _f, _f, _f, _f, _p]),
     "upr_t_sqsum": (_i, [_p, c_size_t, _p, _p]),
     "upr_t_unscale": (_i, [_p, c_size_t, _p, _p, _p]),
-    "upr_t_adam": (_i, [_p, _p, _p, _p, c_size_t, _p, _f, _f, _f, _f, _f, _f, _i, _p, _p]),
+    "upr_t_adam": (_i, [_p, _p, _p, _p, c_size_t, _p, _f, _f, _d, _d, _f, _f, _i, _p, _p]),
 })
 
 _lib = None

@@ -90,8 +90,8 @@ class Adam:
             sq, max_norm, norm_out = self._sq, 0.0, None
         b1, b2 = g["betas"]
         _chk(L.lib().upr_t_adam(_p(self.flat.flat), _p(self.flat.grad), _p(self.m), _p(self.v), self.flat.numel,
-                                _p(sq), ctypes.c_float(max_norm), ctypes.c_float(g["lr"]), ctypes.c_float(b1),
-                                ctypes.c_float(b2), ctypes.c_float(g["eps"]), ctypes.c_float(g["weight_decay"]),
+                                _p(sq), ctypes.c_float(max_norm), ctypes.c_float(g["lr"]), ctypes.c_double(b1),
+                                ctypes.c_double(b2), ctypes.c_float(g["eps"]), ctypes.c_float(g["weight_decay"]),
                                 self.step_count, _p(norm_out), _stream()), "adam")
         bump_weights_epoch()
 
