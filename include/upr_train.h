@@ -527,6 +527,51 @@ int upr_t_sqsum(const float* g, size_t n, double* acc, void* stream);
 int upr_t_adam(float* p, const float* g, float* m, float* v, size_t n, const double* sqsum, float max_norm, float lr,
                double beta1, double beta2, float eps, float weight_decay, int step, float* norm_out, void* stream);
 
+/* ---- data augmentation (datasets/dataset.py:101-183) --------------------- */
+/* One sample's augmentation record.  flags: UPR_AUG_HFLIP (torch.flip dims=[2]),
+ * UPR_AUG_VFLIP (dims=[1]), rot90 k in bits 2-3 (applied after the flips, as
+ * the reference does), then one bit per photometric stage; a stage whose bit
+ * is clear is skipped, its value ignored.  sample_id keys the noise generator. */
+#define UPR_AUG_HFLIP 1u
+#define UPR_AUG_VFLIP 2u
+#define UPR_AUG_ROT_SHIFT 2
+#define UPR_AUG_GAMMA 16u
+#define UPR_AUG_CONTRAST 32u
+#define UPR_AUG_BRIGHTNESS 64u
+#define UPR_AUG_NOISE 128u
+#define UPR_AUG_SATURATION 256u
+#define UPR_AUG_SHIFT 512u
+typedef struct {
+  uint32_t flags;
+  float gamma;       /* pow(clamp(x, min=1e-8), gamma) */
+  float contrast;    /* clamp((v - mean_c) * contrast + mean_c, 0, 1) */
+  float brightness;  /* clamp(v + brightness, 0, 1) */
+  float noise_level; /* clamp(v + n * noise_level, 0, 1), n ~ N(0, 1) */
+  float saturation;  /* clamp(gray + saturation * (v - gray), 0, 1) */
+  float shift;       /* clamp(v + shift, 0, 1) */
+  uint32_t reserved;
+  uint64_t sample_id;
+} UprAugParams;
+
+/* Workspace bytes of upr_augment (the statistics pass's fp64 partials and the
+ * per-(image, channel) means); 0 for a shape the entry refuses. */
+size_t upr_augment_workspace(int B, int H, int W);
+/* LowLightDataset.__getitem__ after the letterbox, for a batch: x [B,3,H,W]
+ * -> y [B,3,Ho,Wo] (Ho, Wo = W, H for odd k), y != x.  params: B records on the
+ * device; params_host: the same records in host memory, read before anything
+ * is launched to pick the kernels and to refuse (UPR_ERR_SHAPE, y untouched) a
+ * batch whose images would differ in output shape.  Noise is Philox4x32-10
+ * keyed by seed, counter (sample_id, ((c*Ho + y)*Wo + x) / 4), four Box-Muller
+ * normals per counter; noise != NULL ([B,3,Ho,Wo]) replaces the generator.
+ * 16-byte aligned x / y / noise with W % 4 == 0 take the vector path, anything
+ * else the scalar one, with the same result. */
+int upr_augment(const float* x, float* y, int B, int H, int W, const UprAugParams* params,
+                const UprAugParams* params_host, uint64_t seed, const float* noise, void* ws, size_t ws_bytes,
+                void* stream);
+/* The generator alone: out [B,3,Ho,Wo] = the normals upr_augment would add
+ * (before the noise level) for params[b].sample_id; params on the device. */
+int upr_augment_normals(float* out, int B, int Ho, int Wo, const UprAugParams* params, uint64_t seed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,11 +7,12 @@ never seeds its random init, main.py:229) and --precision {fp32,fp16}.
 Intentional divergences (reference bugs): a single-file --mode enhance works
 (reference main.py:240-249 raises TypeError); --mode predict unpacks the
 model's 3-tuple (reference predict.py:163 raises ValueError).
---mode train: the training STEP runs on the HIP path through the drop-in
-trainers/train.py (train_step / train_one_epoch, losses/loss.py TotalLoss);
-the reference's epoch driver around it (datasets, augmentation, schedulers,
-TensorBoard, checkpoint files; reference trainers/train.py:134-330) is outside
-this build's scope, so the CLI mode exits with that message.
+--mode train runs trainers.train.train(args): images of --train_dir are decoded
+on host threads, letterboxed and augmented on the device (datasets/dataset.py),
+and every step runs on the HIP path (train_step, losses/loss.py TotalLoss,
+upr.optim.Adam); schedulers, early stopping, latest_model.pth / best_model.pth
+and results.csv follow the reference (trainers/train.py:189-396).  --seed also
+seeds the shuffle, the augmentation draws and the noise generator.
 """
 import argparse
 import os
@@ -112,9 +113,9 @@ def main(argv=None):
     print(f"使用设备: {args.device}")
     print(f"运行模式: {args.mode}")
     if args.mode == 'train':
-        raise SystemExit("--mode train: the reference's epoch driver (datasets, augmentation, schedulers, "
-                         "checkpoint files) is outside this build; the HIP training step itself is the drop-in "
-                         "trainers.train.train_step / train_one_epoch with losses.loss.TotalLoss")
+        from trainers.train import train
+        train(args)
+        return
     if args.mode == 'predict':
         if not os.path.exists(args.checkpoint):
             print(f"错误: 找不到模型检查点文件 '{args.checkpoint}'")

@@ -1,4 +1,6 @@
-"""UP-Retinex training step (drop-in for the reference trainers/train.py:27-131).
+"""UP-Retinex training (drop-in for the reference trainers/train.py): the step
+(:27-131) and, below it, the epoch driver train(args) with its schedulers,
+checkpoint files, early stopping and results.csv (:134-396, :520-600).
 
 `train_one_epoch` keeps the reference's signature and step order
 (zero_grad -> forward -> TotalLoss -> backward -> clip_grad_norm_(1.0) ->
@@ -15,7 +17,11 @@ accumulation (upr/train.py, autocast_active); weight gradients, BatchNorm, the
 losses and the optimiser stay fp32.  `amp_fp16=False` keeps the GradScaler
 control flow with fp32 arithmetic.
 """
+import csv
+import math
+import os
 import time
+from datetime import datetime
 
 import torch
 
@@ -91,3 +97,233 @@ def train_one_epoch(model, dataloader, criterion, optimizer, device, epoch, writ
         totals = {k: v / n for k, v in totals.items()}
     totals["_epoch_seconds"] = time.time() - t0
     return totals
+
+
+# ---- the epoch driver (reference trainers/train.py:134-396, :520-600) --------
+LOSS_KEYS = ('total', 'exposure', 'smoothness', 'color', 'spatial', 'decouple', 'perceptual')
+
+
+class StepLR:
+    """torch.optim.lr_scheduler.StepLR for upr.optim.Adam (which is no
+    torch.optim.Optimizer): step() sets param_groups[0]['lr'] to its closed form
+    base_lr * gamma ** (last_epoch // step_size).  base_lr is the lr the
+    optimizer was built with; last_epoch > 0 continues a resumed run in phase."""
+
+    def __init__(self, optimizer, step_size, gamma=0.1, last_epoch=0, base_lr=None):
+        self.optimizer, self.step_size, self.gamma = optimizer, int(step_size), float(gamma)
+        self.base_lr = float(optimizer.param_groups[0]['lr'] if base_lr is None else base_lr)
+        self.last_epoch = int(last_epoch)
+        self._apply()
+
+    def get_lr(self):
+        return self.base_lr * self.gamma ** (self.last_epoch // self.step_size)
+
+    def _apply(self):
+        self.optimizer.param_groups[0]['lr'] = self.get_lr()
+
+    def step(self):
+        self.last_epoch += 1
+        self._apply()
+
+
+class CosineAnnealingWarmRestarts(StepLR):
+    """torch.optim.lr_scheduler.CosineAnnealingWarmRestarts, stepped once per
+    epoch: eta_min + (base_lr - eta_min) * (1 + cos(pi * T_cur / T_i)) / 2 with
+    (T_cur, T_i) the position in the current restart period, from last_epoch."""
+
+    def __init__(self, optimizer, T_0=10, T_mult=2, eta_min=1e-6, last_epoch=0, base_lr=None):
+        self.T_0, self.T_mult, self.eta_min = int(T_0), int(T_mult), float(eta_min)
+        super().__init__(optimizer, 1, 1.0, last_epoch, base_lr)
+
+    def get_lr(self):
+        t, ti = self.last_epoch, self.T_0
+        while t >= ti:
+            t -= ti
+            ti *= self.T_mult
+        return self.eta_min + (self.base_lr - self.eta_min) * (1 + math.cos(math.pi * t / ti)) / 2
+
+
+def save_checkpoint(model, optimizer, epoch, save_dir, is_best=False):
+    """latest_model.pth every call, best_model.pth when is_best, with the
+    reference's three keys.  'model_state_dict' loads into the reference model
+    unchanged; 'optimizer_state_dict' is upr.optim.Adam's own format (step, the
+    flat moment buffers m and v, param_groups), not torch.optim.Adam's."""
+    os.makedirs(save_dir, exist_ok=True)
+    checkpoint = {
+        'epoch': epoch,
+        'model_state_dict': {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
+        'optimizer_state_dict': {k: (v.detach().cpu() if torch.is_tensor(v) else v)
+                                 for k, v in optimizer.state_dict().items()},
+    }
+    if is_best:
+        best_path = os.path.join(save_dir, 'best_model.pth')
+        torch.save(checkpoint, best_path)
+        print(f"Saved best model: {best_path}")
+    latest_path = os.path.join(save_dir, 'latest_model.pth')
+    torch.save(checkpoint, latest_path)
+    print(f"Saved latest model: {latest_path}")
+
+
+def load_checkpoint(model, optimizer, checkpoint_path, map_location='cpu'):
+    """-> the epoch to resume from (saved epoch + 1).  The file is read with
+    map_location (the values are then copied into the model's / optimizer's own
+    buffers, wherever they live)."""
+    if not os.path.exists(checkpoint_path):
+        raise FileNotFoundError(f"Checkpoint not found: {checkpoint_path}")
+    checkpoint = torch.load(checkpoint_path, map_location=map_location, weights_only=True)
+    model.load_state_dict(checkpoint['model_state_dict'])
+    optimizer.load_state_dict(checkpoint['optimizer_state_dict'])
+    print(f"Loaded checkpoint from epoch {checkpoint['epoch']}")
+    return checkpoint['epoch'] + 1
+
+
+def _summary_writer(log_dir):
+    """TensorBoard's SummaryWriter when tensorboard imports, else None."""
+    try:
+        import tensorboard  # noqa: F401
+        from torch.utils.tensorboard import SummaryWriter
+    except Exception:
+        return None
+    return SummaryWriter(log_dir)
+
+
+def save_loss_curves(loss_history, save_dir):
+    """plots/<key>_curve.png and plots/combined_loss_curves.png (reference :520-568) when matplotlib imports."""
+    try:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+    except Exception:
+        print("matplotlib is not installed: loss curves not drawn (results.csv has the numbers)")
+        return False
+    plot_dir = os.path.join(save_dir, 'plots')
+    os.makedirs(plot_dir, exist_ok=True)
+    curves = {k: v for k, v in loss_history.items() if v}
+    for key, values in curves.items():
+        plt.figure(figsize=(10, 6))
+        plt.plot(values)
+        plt.title(f'{key.capitalize()} Loss Curve')
+        _finish_plot(plt, os.path.join(plot_dir, f'{key}_curve.png'))
+    plt.figure(figsize=(12, 8))
+    for key, values in curves.items():
+        if key != 'total':  # the total would flatten the others
+            plt.plot(values, label=key.capitalize())
+    plt.title('Training Loss Curves')
+    plt.legend()
+    _finish_plot(plt, os.path.join(plot_dir, 'combined_loss_curves.png'))
+    return True
+
+
+def _finish_plot(plt, path):
+    plt.xlabel('Epoch')
+    plt.ylabel('Loss')
+    plt.grid(True)
+    plt.tight_layout()
+    plt.savefig(path)
+    plt.close()
+
+
+def save_results_to_csv(loss_history, save_dir):
+    """results.csv: one row per epoch, columns epoch + the loss keys (reference :571-600)."""
+    os.makedirs(save_dir, exist_ok=True)
+    csv_path = os.path.join(save_dir, 'results.csv')
+    keys = list(loss_history)
+    with open(csv_path, 'w', newline='') as f:
+        w = csv.writer(f)
+        w.writerow(['epoch'] + keys)
+        for epoch in range(max((len(v) for v in loss_history.values()), default=0)):
+            w.writerow([epoch] + [loss_history[k][epoch] if epoch < len(loss_history[k]) else '' for k in keys])
+    print(f"Saved results to CSV: {csv_path}")
+    return csv_path
+
+
+def train(args):
+    """The reference's train(args) (trainers/train.py:189-396) on the HIP step
+    and the device data path.  Differences: the schedulers are this module's
+    (closed forms; a resumed run continues the schedule at its epoch instead of
+    restarting it), TensorBoard and the matplotlib curves are used when they
+    import, save_sample_visualizations is not built, and the rows of
+    results.csv are the epochs this call ran.  Returns the loss history."""
+    from datasets.dataset import get_train_dataloader
+    from losses.loss import TotalLoss
+    from models.model import MultiScaleUP_Retinex
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("--mode train runs on ROCm devices only (no CPU fallback)")
+    dev = getattr(args, 'device', None)
+    device = torch.device(dev if dev and str(dev) != 'cpu' else 'cuda')
+    if device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    print(f"Using device: {device}")
+    seed = getattr(args, 'seed', None)
+    if seed is not None:
+        torch.manual_seed(seed)
+    use_preact, use_aspp = getattr(args, 'use_preact', False), getattr(args, 'use_aspp', False)
+    model = MultiScaleUP_Retinex(use_preact=use_preact, use_aspp=use_aspp).to(device)
+    print(f"Number of parameters: {sum(p.numel() for p in model.parameters() if p.requires_grad):,}")
+    use_freq_loss, adaptive_weights = getattr(args, 'use_freq_loss', False), getattr(args, 'adaptive_weights', False)
+    criterion = TotalLoss(weight_exp=getattr(args, 'weight_exp', 10.0), weight_smooth=getattr(args, 'weight_smooth', 1.0),
+                          weight_col=getattr(args, 'weight_col', 0.5), weight_spa=getattr(args, 'weight_spa', 1.0),
+                          weight_decouple=getattr(args, 'weight_decouple', 0.1),
+                          weight_perceptual=getattr(args, 'weight_perceptual', 1.0),
+                          weight_freq=getattr(args, 'weight_freq', 0.5), use_freq_loss=use_freq_loss,
+                          adaptive_weights=adaptive_weights).to(device)
+    print(f"Loss: frequency term {'on' if use_freq_loss else 'off'}, adaptive weights "
+          f"{'on' if adaptive_weights else 'off'}")
+    optimizer = make_optimizer(model, lr=args.lr, weight_decay=args.weight_decay)
+    use_amp = bool(getattr(args, 'use_amp', False))
+    scaler = GradScaler() if use_amp else None
+    if use_amp:
+        print("Mixed precision training enabled (AMP)")
+    patience = getattr(args, 'patience', 20)
+    start_epoch = 0
+    if getattr(args, 'resume', None):
+        start_epoch = load_checkpoint(model, optimizer, args.resume, map_location='cpu')
+    if getattr(args, 'use_cosine_scheduler', False):
+        scheduler = CosineAnnealingWarmRestarts(optimizer, T_0=10, T_mult=2, eta_min=1e-6, last_epoch=start_epoch,
+                                                base_lr=args.lr)
+    else:
+        scheduler = StepLR(optimizer, step_size=args.lr_decay_step, gamma=args.lr_decay_gamma,
+                           last_epoch=start_epoch, base_lr=args.lr)
+    advanced_augment = getattr(args, 'advanced_augment', False)
+    train_loader = get_train_dataloader(image_dir=args.train_dir, batch_size=args.batch_size,
+                                        image_size=args.image_size, num_workers=args.num_workers, shuffle=True,
+                                        advanced_augment=advanced_augment, device=device, seed=seed)
+    print(f"Number of training batches: {len(train_loader)}")
+    if len(train_loader) == 0:
+        print(f"No training batches: {len(train_loader.dataset)} samples, batch_size={args.batch_size}")
+        return None
+    writer = _summary_writer(os.path.join(args.save_dir, 'logs', datetime.now().strftime('%Y%m%d_%H%M%S')))
+    loss_history = {k: [] for k in LOSS_KEYS}
+    best_loss, patience_counter = float('inf'), 0
+    for epoch in range(start_epoch, args.num_epochs):
+        train_loader.set_epoch(epoch)
+        avg = train_one_epoch(model, train_loader, criterion, optimizer, device, epoch, writer, scaler=scaler,
+                              use_amp=use_amp)
+        scheduler.step()
+        current_lr = optimizer.param_groups[0]['lr']
+        for k in LOSS_KEYS:
+            loss_history[k].append(float(avg[k]))
+        print(f"\nEpoch {epoch}: {avg['_epoch_seconds']:.2f}s, lr {current_lr:.6g}, " +
+              ", ".join(f"{k} {loss_history[k][-1]:.6f}" for k in LOSS_KEYS))
+        if writer is not None:
+            writer.add_scalar('Learning_Rate', current_lr, epoch)
+            for k in LOSS_KEYS:
+                writer.add_scalar(f'Epoch_Loss/{k}', loss_history[k][-1], epoch)
+        is_best = loss_history['total'][-1] < best_loss
+        if is_best:
+            best_loss, patience_counter = loss_history['total'][-1], 0
+            print(f"  New best loss: {best_loss:.6f}")
+        else:
+            patience_counter += 1
+            print(f"  Patience: {patience_counter}/{patience}")
+        save_checkpoint(model, optimizer, epoch, args.save_dir, is_best)
+        if patience_counter >= patience:
+            print(f"Early stopping after {epoch + 1} epochs, best loss {best_loss:.6f}")
+            break
+    if writer is not None:
+        writer.close()
+    save_loss_curves(loss_history, args.save_dir)
+    save_results_to_csv(loss_history, args.save_dir)
+    print(f"Training completed. Best loss: {best_loss:.6f}. Models saved in: {args.save_dir}")
+    return loss_history

@@ -122,6 +122,24 @@ class UprPackJob(ctypes.Structure):
                 ("n", ctypes.c_int)]
 
 
+class UprAugParams(ctypes.Structure):
+    """include/upr_train.h UprAugParams: one sample's augmentation record (40 bytes)."""
+    _fields_ = [("flags", ctypes.c_uint32), ("gamma", ctypes.c_float), ("contrast", ctypes.c_float),
+                ("brightness", ctypes.c_float), ("noise_level", ctypes.c_float), ("saturation", ctypes.c_float),
+                ("shift", ctypes.c_float), ("reserved", ctypes.c_uint32), ("sample_id", ctypes.c_uint64)]
+
+
+# include/upr_train.h UPR_AUG_*: bits of UprAugParams.flags (rot90 k in bits 2-3)
+UPR_AUG_HFLIP = 1
+UPR_AUG_VFLIP = 2
+UPR_AUG_ROT_SHIFT = 2
+UPR_AUG_GAMMA = 16
+UPR_AUG_CONTRAST = 32
+UPR_AUG_BRIGHTNESS = 64
+UPR_AUG_NOISE = 128
+UPR_AUG_SATURATION = 256
+UPR_AUG_SHIFT = 512
+
 # include/upr_train.h UPR_T_STORE_*: bits of upr_t_conv_mfma / upr_t_conv_mfma16's `store`
 UPR_T_STORE_CONVT2X2 = 1
 UPR_T_STORE_KEEP16 = 2
@@ -233,6 +251,9 @@ SIGNATURES.update({
     "upr_t_sqsum": (_i, [_p, c_size_t, _p, _p]),
     "upr_t_unscale": (_i, [_p, c_size_t, _p, _p, _p]),
     "upr_t_adam": (_i, [_p, _p, _p, _p, c_size_t, _p, _f, _f, _d, _d, _f, _f, _i, _p, _p]),
+    "upr_augment_workspace": (c_size_t, [_i, _i, _i]),
+    "upr_augment": (_i, [_p, _p, _i, _i, _i, _p, _p, c_u64, _p, _p, c_size_t, _p]),
+    "upr_augment_normals": (_i, [_p, _i, _i, _i, _p, c_u64, _p]),
 })
 
 _lib = None

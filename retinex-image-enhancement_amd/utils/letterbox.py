@@ -83,13 +83,19 @@ def letterbox_geometry(shape, new_shape=640, auto=True, scale_fill=False, scaleu
     return new_unpad, ratio, (dw, dh), border
 
 
+def letterbox_shape(shape, new_shape=640, auto=True, scale_fill=False, scaleup=True):
+    """(H, W) of the letterboxed image for an input of shape (H, W)."""
+    (nw, nh), _, _, (top, bottom, left, right) = letterbox_geometry(shape, new_shape, auto, scale_fill, scaleup)
+    return nh + top + bottom, nw + left + right
+
+
 def _device(t):
     if not torch.cuda.is_available():
         raise RuntimeError("letterbox runs on ROCm devices only (no CPU fallback)")
     return t.device if t.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
 
 
-def _run(src, src_kind, H, W, new_shape, color, auto, scale_fill, scaleup, out_kind):
+def _run(src, src_kind, H, W, new_shape, color, auto, scale_fill, scaleup, out_kind, out=None):
     (nw, nh), ratio, pad, (top, bottom, left, right) = letterbox_geometry((H, W), new_shape, auto, scale_fill,
                                                                           scaleup)
     Ho, Wo = nh + top + bottom, nw + left + right
@@ -98,7 +104,12 @@ def _run(src, src_kind, H, W, new_shape, color, auto, scale_fill, scaleup, out_k
     if (nw, nh) != (W, H):
         xt = _device_taps(nw, W, dev)
         yt = _device_taps(nh, H, dev)
-    if out_kind == 0:
+    if out is not None:
+        # a caller's destination (a slot of a batch buffer): float output only
+        if out_kind != 0 or tuple(out.shape) != (3, Ho, Wo) or out.dtype != torch.float32 \
+                or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous float32 {(3, Ho, Wo)} tensor on {dev}")
+    elif out_kind == 0:
         out = torch.empty((3, Ho, Wo), dtype=torch.float32, device=dev)
     else:
         out = torch.empty((Ho, Wo, 3), dtype=torch.uint8, device=dev)
@@ -135,12 +146,14 @@ def letterbox_tensor(img_tensor, new_shape=640, color=(114, 114, 114), auto=True
 
 
 def letterbox_u8_image(img_u8_hwc, new_shape, color=(114, 114, 114), auto=True, scale_fill=False, scaleup=False,
-                       device=None):
+                       device=None, out=None):
     """Harness fast path: a decoded uint8 HWC image goes to the device as bytes
     (3 B/pixel over PCIe, not 12) and comes back as the letterboxed [3,H',W']
     float tensor -- ToTensor + letterbox_tensor in one launch (bit-identical:
-    (k/255)*255 quantises back to k)."""
+    (k/255)*255 quantises back to k).  out: an optional [3,H',W'] float32
+    destination on the device (the training loader's slot of its batch buffer);
+    letterbox_shape tells H', W' beforehand."""
     t = torch.from_numpy(np.ascontiguousarray(img_u8_hwc))
     dev = device if device is not None else _device(t)
     t = t.to(dev)
-    return _run(t, 0, t.shape[0], t.shape[1], new_shape, color, auto, scale_fill, scaleup, 0)
+    return _run(t, 0, t.shape[0], t.shape[1], new_shape, color, auto, scale_fill, scaleup, 0, out=out)
