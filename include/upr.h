@@ -107,9 +107,13 @@ long long upr_model_forks(const UprModel* model);
  * split-fp16 tensors.  "Split in registers": the 32-channel stride-1 3x3 convs
  * of the row-ring kernel (dec1, the residual head, the EnhancedFAM branch3/4
  * first convs and fusion parts) keep fp32 tensors and split each 8-channel
- * fragment into (hi, lo) fp16 after reading it.  Env UPR_FP32_SPLIT=0, read by
+ * fragment into (hi, lo) fp16 after reading it.  "Weights split once": the
+ * 64-wide convs at half resolution (enc1.conv1 / .conv2, dec2.conv.0 / .3)
+ * do the same to their activations and read weights the handle split when it
+ * was built (upr_pack_split_w_f32).  Env UPR_FP32_SPLIT=0, read by
  * upr_model_create, keeps the fp32 MFMA kernels everywhere; UPR_FP32_SPLIT_REGS=0
- * keeps them for the split-in-registers ops only.  The activations these
+ * keeps them for the split-in-registers and weights-split-once ops,
+ * UPR_FP32_SPLIT_W64=0 for the weights-split-once ops only.  The activations these
  * convs read must stay within the fp16 range (65504): a forward that leaves it
  * sets a flag, and from the next forward on the handle runs the fp32 kernels
  * for good (one line on stderr).  A UPR_MODEL_HEAD_ONLY handle of such a model
@@ -120,7 +124,7 @@ int upr_model_split_state(const UprModel* model);
 
 /* The form every op of the handle's most recent forward ran in, in launch
  * order: 0 = the model dtype's own (exact) kernels, 1 = split tensors, 2 =
- * split in registers.  Fills names[i] (64 bytes each, nullable) and forms[i]
+ * split in registers, 3 = weights split once.  Fills names[i] (64 bytes each, nullable) and forms[i]
  * for i < max_ops and returns the number of ops (0 before the first forward,
  * -1 for NULL).  No reference counterpart. */
 typedef struct {
@@ -195,6 +199,34 @@ int upr_conv2d_nhwc_regs(const void* x, int B, int H, int W, int Cin, const void
 int upr_split_f32(const float* x, void* y, size_t npix, int C, unsigned* overflow, void* stream);
 int upr_unsplit_f32(const void* x, float* y, size_t npix, int C, void* stream);
 size_t upr_pack_split_f32(const float* w, int Cout, int Cin, int kh, int kw, void* out, size_t out_bytes);
+
+/* fp32 convs of 64-wide output tiles on the fp16 MFMA unit with the weights
+ * split once on the host (tensors stay fp32; every activation fragment is
+ * split in registers as in upr_conv2d_nhwc_regs).
+ * upr_pack_split_w_f32 (host only): w fp32 in the packed [Cout][kh*kw*Cin]
+ * layout upr_conv2d_nhwc takes, optionally followed by a second 1x1 K-segment
+ * w2 fp32 [Cout][C2] (NULL / 0: none); Cout % 64 == 0, Cin % 32 == 0, C2 % 32
+ * == 0.  Per output channel n, s_n = the power of two that puts the row's
+ * max|w| (over both segments) in [2^14, 2^15); the blob holds, per row and per
+ * 32 consecutive k, 64 fp16: W_hi = fp16(w s_n) then W_lo = fp16(w s_n -
+ * W_hi), each as 4 runs of 8 where run g holds k 4g..4g+3 and 16+4g..16+4g+3
+ * (the k-slots of one MFMA lane group); after the planes, at the next multiple
+ * of 256 bytes, float 1/s_n [Cout].  Returns the blob's bytes (0: bad
+ * arguments) and fills `out` when out_bytes suffices.
+ * upr_conv2d_nhwc_wsplit: y = relu?(conv(x) + conv1x1(x2) + bias) + residual
+ * (the residual is added after the ReLU), x [B,H,W,Cin], optional second
+ * K-segment x2 [B,H2,W2,C2] read at stride2 without padding (NULL: none),
+ * residual / y [B,Ho,Wo,Cout], all fp32 NHWC; blob / blob_bytes from
+ * upr_pack_split_w_f32 for the same shape (device copy).  Shapes the kernel
+ * does not take, or a blob of another size, return UPR_ERR_UNSUPPORTED (never
+ * another kernel).  `overflow` as for upr_conv2d_nhwc_regs.  No reference
+ * counterpart. */
+size_t upr_pack_split_w_f32(const float* w, int Cout, int Cin, int kh, int kw, const float* w2, int C2, void* out,
+                            size_t out_bytes);
+int upr_conv2d_nhwc_wsplit(const void* x, int B, int H, int W, int Cin, const void* blob, size_t blob_bytes,
+                           const float* bias, int Cout, int kh, int kw, int stride, int pad, int dil,
+                           const void* residual, int relu, void* y, const void* x2, int H2, int W2, int C2,
+                           int stride2, unsigned* overflow, void* stream);
 
 /* float -> uint8 exactly as `(x * 255).astype(np.uint8)` on float32
  * (enhancers/adaptive_params.py:142, letterbox.py:93): truncation, wrap mod

@@ -122,7 +122,10 @@ struct Q32Cursor {
   }
 };
 
-template <int BM, int BN>
+// SC (the weights-split-once form): the accumulators hold the sum scaled by
+// s_n -- times op.scale[n] = 1 / s_n before the bias, and *op.ovf = 1 when an
+// accumulator of a stored row is not finite (an input left the fp16 range)
+template <int BM, int BN, bool SC = false>
 __device__ __forceinline__ void q32_epilogue(const ConvOp& op, f32x4_q (&acc)[Q32Cfg<BM, BN>::WM][Q32Cfg<BM, BN>::WN],
                                              unsigned char* smem, int m0, int n0, int M, int HW) {
   using C = Q32Cfg<BM, BN>;
@@ -144,6 +147,12 @@ __device__ __forceinline__ void q32_epilogue(const ConvOp& op, f32x4_q (&acc)[Q3
   for (int e = 0; e < 8; ++e) {
     bi[e] = op.bias ? op.bias[nch + e] : 0.f;
     psum[e] = 0.f;
+  }
+  float sc[SC ? 8 : 1];
+  float bad = 0.f;  // NaN once an accumulator was not finite (v * 0 is NaN exactly then)
+  if constexpr (SC) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sc[e] = op.scale[nch + e];
   }
   const bool one_image = (m0 / HW) == (min(m0 + BM, M) - 1) / HW;
   const bool convt = op.store == kStoreConvT2x2;
@@ -190,8 +199,17 @@ __device__ __forceinline__ void q32_epilogue(const ConvOp& op, f32x4_q (&acc)[Q3
         }
       }
       if (m < M) {
-        const f32x4_q lo = *(const f32x4_q*)(Es + row * EST + col8 * 8);
-        const f32x4_q hi = *(const f32x4_q*)(Es + row * EST + col8 * 8 + 4);
+        f32x4_q lo = *(const f32x4_q*)(Es + row * EST + col8 * 8);
+        f32x4_q hi = *(const f32x4_q*)(Es + row * EST + col8 * 8 + 4);
+        if constexpr (SC) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            bad = __builtin_fmaf(lo[e], 0.f, bad);
+            bad = __builtin_fmaf(hi[e], 0.f, bad);
+            lo[e] *= sc[e];
+            hi[e] *= sc[4 + e];
+          }
+        }
         float v[8] = {lo[0] + bi[0], lo[1] + bi[1], lo[2] + bi[2], lo[3] + bi[3],
                       hi[0] + bi[4], hi[1] + bi[5], hi[2] + bi[6], hi[3] + bi[7]};
         if (op.img_bias) {
@@ -246,6 +264,9 @@ __device__ __forceinline__ void q32_epilogue(const ConvOp& op, f32x4_q (&acc)[Q3
       for (int g = 0; g < RPI; ++g) t += Es[g * BN + tid];
       pool_add(op.pool, (size_t)(m0 / HW) * op.N + n0 + tid, t);
     }
+  }
+  if constexpr (SC) {
+    if (bad != bad && op.ovf) *op.ovf = 1u;
   }
 }
 
@@ -554,6 +575,219 @@ int launch_conv_wide32(const ConvOp& op, hipStream_t st) {
   // 99.6, 128 x 64 115.7).
   if (n128) return launch_w32<128, 128, 2>(op, steps, st);
   return launch_w32<256, 64, 1>(op, steps, st);
+}
+
+// ---------------------------------------------------------------------------
+// Weights split once (ConvOp::mma16 == 3): the 256 x 64 gathered tile on
+// v_mfma_f32_16x16x32_f16.
+//
+// A is the path above unchanged (fp32 tensors, 128-byte rows by LDS-DMA, the
+// XOR swizzle, Q32Cursor: stride 2 and a second K-segment come with it).  B
+// arrives already split: model.hip pack_split_w stores, per output channel and
+// 32-deep K step, 32 fp16 of W_hi = fp16(w s_n) then 32 of W_lo = fp16(w s_n -
+// W_hi) -- the 128 bytes an fp32 weight row has per step, so the DMA, its
+// swizzle and the 2 x (32 + 8) KB of LDS are those of the fp32 kernel.  Within
+// a plane, 16-byte chunk g holds channels 4g..4g+3, 16+4g..16+4g+3 of the
+// step (wsplit_kslot): the 8 channels lane group g holds of its A row after
+// reading chunks g and 4 + g, so one ds_read_b128 of chunk g (W_hi) or 4 + g
+// (W_lo) is a ready MFMA operand and the loop does no weight arithmetic but
+// one v_pk_mul_f16 x 4 per tile for W_hi 2^-11 (the value pack_split stores as
+// a third plane: that plane would cost 88 KB of LDS and the second block of
+// the CU; a second accumulator set for the lo product costs the registers of
+// it).  With 8 waves along M (64 channels = one wave's 4 tiles) every A row is
+// split by exactly one wave (q_split_a = split_f32x8), and per step a wave issues
+//   acc += hi W_hi;  acc += hi W_lo;  acc += lo (W_hi 2^-11)
+// as 24 MFMAs into 32 accumulator registers.  All fragments of a step are read
+// before the barrier that hands the stage back to the DMA, so the next-but-one
+// step's DMA flies under this step's split and MFMAs; two blocks per CU (<=
+// 128 VGPRs) give each SIMD a second pair of waves to issue from meanwhile.
+// ---------------------------------------------------------------------------
+// split_f32x8 of the 8 channels a lane holds of its A row, bit for bit, with
+// every instruction chosen here: per channel pair one v_cvt_pk_f16_f32 (hi),
+// two v_mul_f32 (v 2^11) and v_fma_mixlo / mixhi_f16 (lo = fp16(v 2^11 - hi
+// 2^11), the fp16 hi read in place and the exact fp32 sum rounded once) -- 2.5
+// VALU instructions per element.  Left to itself hipcc SLP-packs the muls and
+// fmas of neighbouring channels into v_pk_mul_f32 / v_pk_fma_f32 and converts
+// hi back with v_cvt_f32_f16 (3.5 per element, the packed ones an anti-lever
+// beside MFMAs).
+__device__ __forceinline__ void q_split_a(const f32x4_q& v0, const f32x4_q& v1, f16x8_t& hi, f16x8_t& lo) {
+  typedef unsigned u32x4_q __attribute__((ext_vector_type(4)));
+  const float nscale = -kSplitLoScale;
+  u32x4_q h, l;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const float a = p < 2 ? v0[2 * p] : v1[2 * p - 4];
+    const float b = p < 2 ? v0[2 * p + 1] : v1[2 * p - 3];
+    unsigned hp, lp;
+    float ta, tb;
+    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hp) : "v"(a), "v"(b));
+    asm("v_mul_f32 %0, 0x45000000, %1" : "=v"(ta) : "v"(a));
+    asm("v_mul_f32 %0, 0x45000000, %1" : "=v"(tb) : "v"(b));
+    asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(lp) : "v"(hp), "s"(nscale), "v"(ta));
+    asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lp) : "v"(hp), "s"(nscale), "v"(tb));
+    h[p] = hp;
+    l[p] = lp;
+  }
+  hi = __builtin_bit_cast(f16x8_t, h);
+  lo = __builtin_bit_cast(f16x8_t, l);
+}
+
+template <int BM, int BN>
+__global__ __launch_bounds__(512, 4) void conv_wide32_kernel_wsplit(ConvOp op) {
+  using C = Q32Cfg<BM, BN>;
+  constexpr int WM = C::WM, WN = C::WN;
+  static_assert(C::WAVES_N == 1, "one wave holds all the tile's channels: no A row is split twice");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int wm = wave;
+
+  const int M = op.B * op.Ho * op.Wo;
+  const int HW = op.Ho * op.Wo;
+  const int mtiles = (M + BM - 1) / BM;
+  const int ntiles = op.N / BN;
+  const int L = q_xcd_remap(blockIdx.x, mtiles * ntiles);
+  const int ntile = L % ntiles;
+  const int mtile = L / ntiles;
+  const int m0 = mtile * BM;
+  const int n0 = ntile * BN;
+
+  const int q8 = lane >> 3;
+  const int qc = lane & 7;
+  int rb[C::AI], ry[C::AI], rx[C::AI];
+#pragma unroll
+  for (int i = 0; i < C::AI; ++i) {
+    const int m = m0 + wave * (BM / 8) + i * 8 + q8;
+    if (m < M) {
+      const int b = m / HW, r = m - b * HW;
+      rb[i] = b;
+      ry[i] = r / op.Wo;
+      rx[i] = r - ry[i] * op.Wo;
+    } else {
+      rb[i] = -1; ry[i] = 0; rx[i] = 0;
+    }
+  }
+  const int sw_lane = lane >> 4;
+
+  int total_steps = 0;
+  for (int s = 0; s < op.nseg; ++s) total_steps += op.seg[s].kh * op.seg[s].kw * (op.seg[s].C / Q_BK);
+
+  // (the plane blob addressed in 4-byte units: Kpad of them per row, 32 per step)
+  const float* Wt = (const float*)op.W;
+  const float* zero = (const float*)g_w32_zero;
+  Q32Cursor<C::AI> cur(op, rb, ry, rx);
+
+  auto issue = [&](int stage) {
+    unsigned char* As = smem + stage * C::STAGE;
+    unsigned char* Bs = As + C::A_BYTES;
+#pragma unroll
+    for (int i = 0; i < C::AI; ++i) {
+      const int ch = qc ^ ((4 * i + sw_lane) & 7);
+      q_glds16(cur.a_src(i, zero) + ch * 4, As + (wave * (BM / 8) + i * 8) * 128);
+    }
+    const int kb = cur.kb();
+#pragma unroll
+    for (int j = 0; j < C::BJ; ++j) {
+      const int t = wave + 8 * j;
+      if (BN / 8 >= 8 * (j + 1) || t < BN / 8) {
+        const int n = t * 8 + q8;
+        const int ch = qc ^ ((n >> 1) & 7);
+        q_glds16(Wt + (size_t)(n0 + n) * op.Kpad + kb + ch * 4, Bs + t * 8 * 128);
+      }
+    }
+    cur.advance();
+  };
+
+  f32x4_q acc[WM][WN];
+#pragma unroll
+  for (int a = 0; a < WM; ++a)
+#pragma unroll
+    for (int b = 0; b < WN; ++b) acc[a][b] = f32x4_q{0.f, 0.f, 0.f, 0.f};
+
+  const int fr = lane & 15;
+  const int fg = lane >> 4;
+  const int rsw = (fr >> 1) & 7;
+  const int p0 = (fg ^ rsw) * 16, p1 = ((4 + fg) ^ rsw) * 16;  // byte offsets of chunks g, 4 + g in a row
+
+  if (total_steps > 0) issue(0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  if (total_steps > 1) issue(1);
+#pragma unroll 1
+  for (int step = 0; step < total_steps; ++step) {
+    const unsigned char* As = smem + (step & 1) * C::STAGE;
+    const unsigned char* Bs = As + C::A_BYTES;
+    f32x4_q af[WM][2];
+    f16x8_t bh[WN], bl[WN];
+#pragma unroll
+    for (int a = 0; a < WM; ++a) {
+      const unsigned char* row = As + (wm * WM * 16 + a * 16 + fr) * 128;
+      af[a][0] = *(const f32x4_q*)(row + p0);
+      af[a][1] = *(const f32x4_q*)(row + p1);
+    }
+#pragma unroll
+    for (int b = 0; b < WN; ++b) {
+      const unsigned char* row = Bs + (b * 16 + fr) * 128;
+      bh[b] = *(const f16x8_t*)(row + p0);
+      bl[b] = *(const f16x8_t*)(row + p1);
+    }
+    // RAW: own DMA of step+1 retired; WAR: own reads of this stage retired
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    if (step + 2 < total_steps) issue(step & 1);
+    f16x8_t ah[WM], al[WM];
+#pragma unroll
+    for (int a = 0; a < WM; ++a) q_split_a(af[a][0], af[a][1], ah[a], al[a]);
+#pragma unroll
+    for (int b = 0; b < WN; ++b) {
+      const f16x8_t bs = bh[b] * (half_t)kSplitLoInv;
+#pragma unroll
+      for (int a = 0; a < WM; ++a) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[a], bh[b], acc[a][b], 0, 0, 0);
+#pragma unroll
+      for (int a = 0; a < WM; ++a) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[a], bl[b], acc[a][b], 0, 0, 0);
+#pragma unroll
+      for (int a = 0; a < WM; ++a) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[a], bs, acc[a][b], 0, 0, 0);
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  q32_epilogue<BM, BN, true>(op, acc, smem, m0, n0, M, HW);
+}
+
+// The op in the weights-split-once form or kErrUnsupported (never another
+// kernel).  Takes NHWC stores of N % 64 == 0 channels without pool / per-image
+// bias, plain segments of C % 32 == 0 channels whose K steps fill Kpad exactly.
+int launch_conv_wsplit(const ConvOp& op, hipStream_t st) {
+  using C = Q32Cfg<256, 64>;
+  static_assert(2 * C::LDS <= 160 * 1024, "LDS for two blocks per CU");
+  if (op.mma16 != 3 || !op.scale || !op.W || !op.out) return kErrUnsupported;
+  if (op.nseg < 1 || op.nseg > 4 || op.B <= 0 || op.Ho <= 0 || op.Wo <= 0) return kErrUnsupported;
+  if (op.store != kStoreNHWC || op.N <= 0 || op.N % 64 || op.pool || op.img_bias || op.out2 || op.out32) return kErrUnsupported;
+  if (op.Kpad % 32 || ((uintptr_t)op.W % 16) || ((uintptr_t)op.scale % 4)) return kErrUnsupported;
+  if (op.out_cs % 4 || op.out_coff % 4 || ((uintptr_t)op.out % 16)) return kErrUnsupported;
+  if ((op.res1 && (op.res1_cs % 4 || (uintptr_t)op.res1 % 16)) || (op.res2 && (op.res2_cs % 4 || (uintptr_t)op.res2 % 16)))
+    return kErrUnsupported;
+  if (op.bias && (uintptr_t)op.bias % 16) return kErrUnsupported;
+  int steps = 0;
+  for (int s = 0; s < op.nseg; ++s) {
+    const ConvSeg& sg = op.seg[s];
+    if (!sg.src || sg.pre != kPreNone || sg.C <= 0 || sg.C % Q_BK || sg.cs % 4 || sg.coff % 4) return kErrUnsupported;
+    if ((uintptr_t)sg.src % 16 || sg.kh <= 0 || sg.kw <= 0 || sg.stride <= 0 || sg.kbase != steps * Q_BK) return kErrUnsupported;
+    steps += sg.kh * sg.kw * (sg.C / Q_BK);
+  }
+  if (steps * Q_BK != op.Kpad) return kErrUnsupported;
+  const long long M = (long long)op.B * op.Ho * op.Wo;
+  if (M > 0x7fffffffll / 64) return kErrUnsupported;  // 32-bit pixel * channel indexing
+  static bool attr_set = false;
+  if (!attr_set) {
+    const hipError_t e = hipFuncSetAttribute((const void*)conv_wide32_kernel_wsplit<256, 64>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
+    if (e != hipSuccess) return (int)e;
+    attr_set = true;
+  }
+  const int grid = (int)((M + 255) / 256) * (op.N / 64);
+  hipLaunchKernelGGL((conv_wide32_kernel_wsplit<256, 64>), dim3(grid), dim3(512), C::LDS, st, op);
+  return (int)hipGetLastError();
 }
 
 }  // namespace upr

@@ -269,6 +269,45 @@ static bool pack_split(int N, const std::vector<SegWeights>& segs, SplitPack& ou
   return true;
 }
 
+// ---------------------------------------------------------------------------
+// Weights split once (ConvOp::mma16 == 3, conv_wide32.hip): the fp32 tensors
+// stay as they are and the kernel splits its activation fragments in
+// registers; only the weights are prepared here.  w: the packed fp32 [N][K]
+// rows of pack_gemm (K-segments of C % 32 == 0 channels, so every 32
+// consecutive k are 32 channels of one tap).  Per row n: s_n from
+// split_row_shift over the row (the rule of pack_split and of the ring's
+// prologue), W_hi = fp16(w s_n), W_lo = fp16(w s_n - W_hi), stored per 32-deep
+// K step as [W_hi(32) | W_lo(32)] in k-slot order (wsplit_kslot); scale[n] =
+// 1 / s_n.  A row takes 4 K bytes, as the fp32 row does.
+// ---------------------------------------------------------------------------
+struct SplitWPack {
+  std::vector<_Float16> W;   // [N][K / 32][2][32]
+  std::vector<float> scale;  // [N]
+};
+
+static bool pack_split_w(int N, int K, const float* w, SplitWPack& out) {
+  if (!w || N <= 0 || N % 64 || K <= 0 || K % 32) return false;
+  out.W.assign((size_t)N * K * 2, (_Float16)0.f);
+  out.scale.assign(N, 1.f);
+  for (int n = 0; n < N; ++n) {
+    const float* row = w + (size_t)n * K;
+    float mx = 0.f;
+    for (int k = 0; k < K; ++k) mx = std::max(mx, std::fabs(row[k]));
+    const int sh = split_row_shift(mx);
+    const float s = std::ldexp(1.f, sh);
+    out.scale[n] = std::ldexp(1.f, -sh);
+    _Float16* dst = out.W.data() + (size_t)n * K * 2;
+    for (int k = 0; k < K; ++k) {
+      const float ws = row[k] * s;
+      const _Float16 hi = (_Float16)ws;
+      _Float16* step = dst + (size_t)(k / 32) * 64;
+      step[wsplit_kslot(k % 32)] = hi;
+      step[32 + wsplit_kslot(k % 32)] = (_Float16)(ws - (float)hi);
+    }
+  }
+  return true;
+}
+
 // Conv weight [N][C][kh][kw] from a HostTensor, rows scaled by mul (optional).
 static std::vector<double> conv_w(const HostTensor& t, const std::vector<double>* mul) {
   std::vector<double> w = t.v;
@@ -355,6 +394,9 @@ struct Op {
   // split-fp16 region (fp32 plain models): the op's second layer (pack_split),
   // -1 outside the region; split_exit: the op writes plain fp32 (region exit)
   int split_layer = -1, split_exit = 0;
+  // weights split once (fp32 plain models, pack_split_w): blob offsets of the
+  // op's fp16 planes and 1 / s_n vector, SIZE_MAX when the op stays exact
+  size_t w64_w = SIZE_MAX, w64_scale = 0;
   int img_bias = 0;
   size_t head_w = 0; float head_b = 0.f;
   // conv3 / fam
@@ -421,6 +463,10 @@ struct UprModel {
   // the same ovf word.  op_forms: the form each op of the latest forward ran in
   // (upr_model_op_forms)
   int split_regs = 0;
+  // Weights split once (env UPR_FP32_SPLIT_W64, read at creation): in state 1,
+  // with split_regs on, the ops that got planes at build time (Op::w64_w: the
+  // 64-wide convs at half resolution) run in that form (3), same guard word
+  int split_w64 = 0;
   std::vector<int> op_forms;
   std::mutex forms_mu;
 };
@@ -572,6 +618,28 @@ struct Builder {
       o->split_exit = i + 1 == names.size();
     }
     return true;
+  }
+  // Gives the named ops their weights-split-once planes (pack_split_w over the
+  // layer's packed fp32 rows, already in the blob).  An op the kernel would not
+  // take -- decided here, from the layer alone -- gets none and stays exact.
+  void make_w64(const std::vector<std::string>& names) {
+    if (dt != kF32) return;
+    for (const std::string& name : names)
+      for (auto& o : m->ops) {
+        if (o.kind != OP_GEMM || o.name != name) continue;
+        const GemmLayer& L = m->layers[o.layer];
+        bool fits = L.N % 64 == 0 && o.store == kStoreNHWC && o.pool_slot < 0 && !o.img_bias && o.out2 < 0 &&
+                    !L.segs.empty() && L.segs.size() <= 2;
+        int K = 0;
+        for (const SegSpec& s : L.segs) {
+          fits = fits && s.pre == kPreNone && s.C % 32 == 0 && s.kbase == K;
+          K += s.kh * s.kw * s.C;
+        }
+        SplitWPack sp;
+        if (!fits || K != L.Kpad || !pack_split_w(L.N, K, (const float*)(blob.bytes.data() + L.w), sp)) continue;
+        o.w64_w = blob.add(sp.W.data(), sp.W.size() * 2);
+        o.w64_scale = blob.add(sp.scale.data(), sp.scale.size() * 4);
+      }
   }
   void gemm(const std::string& name, int layer, int level, int out, int out_cs, int relu, int res1 = -1,
             int res1_cs = 0, int res2 = -1, int res2_cs = 0, int store = kStoreNHWC, int out_coff = 0,
@@ -896,6 +964,9 @@ static int build_model(UprModel* m, ParamSet& P) {
   }
   bd.upblock(ie + ".dec2", B_D3, B_U2, B_V2, B_D2, 128, 64, 2, B_X2);
   bd.upblock(ie + ".dec1", B_D2, B_U1, B_V1, B_D1, 64, 32, 1, B_X1);
+  // the four 64-wide convs at half resolution: weights split once (form 3)
+  if (bd.ok && m->split_state.load() == 1 && m->split_regs && m->split_w64)
+    bd.make_w64({ie + ".enc1.conv1", ie + ".enc1.conv2", ie + ".dec2.conv.0", ie + ".dec2.conv.3"});
   // residual head + illumination (models/model.py:324-328, :351-358)
   {
     const HostTensor* w0 = bd.T(ie + ".residual_head.0.weight");
@@ -1167,9 +1238,19 @@ static int run_forward(UprModel* m, const void* x, int B, int H, int W, void* en
           rc = launch_conv_wide(split_op(o, ho, wo), st);
           forms[oi] = 1;
         } else {
-          if (regs_now && dt == kF32) { c.mma16 = 1; c.ovf = m->ovf_dev; }
-          rc = launch_conv(c, dt, st);
-          forms[oi] = conv_last_form();
+          rc = kErrUnsupported;
+          if (regs_now && dt == kF32 && o.w64_w != SIZE_MAX) {
+            ConvOp cw = c;
+            cw.W = blob + o.w64_w; cw.scale = fptr(o.w64_scale);
+            cw.mma16 = 3; cw.ovf = m->ovf_dev;
+            rc = launch_conv_wsplit(cw, st);
+            if (rc == kOk) forms[oi] = 3;
+          }
+          if (rc == kErrUnsupported) {
+            if (regs_now && dt == kF32) { c.mma16 = 1; c.ovf = m->ovf_dev; }
+            rc = launch_conv(c, dt, st);
+            forms[oi] = conv_last_form();
+          }
         }
         if (m->prof) {
           // GEMM work of this launch: 2*M*N*K; algorithmic bytes: every source read once,
@@ -1425,6 +1506,10 @@ int upr_model_create(const UprTensorDesc* params, int n_params, int use_preact, 
   // kernels while the region stays split
   const char* sr = getenv("UPR_FP32_SPLIT_REGS");
   m->split_regs = !(sr && *sr && atoi(sr) == 0);
+  // UPR_FP32_SPLIT_W64=0 keeps the weights-split-once ops (the 64-wide convs
+  // at half resolution) on the fp32 MFMA kernel alone
+  const char* sw = getenv("UPR_FP32_SPLIT_W64");
+  m->split_w64 = !(sw && *sw && atoi(sw) == 0);
   int rc = build_model(m.get(), P);
   if (rc == kOk && m->split_state.load() == 1) {
     hipError_t e = hipMalloc((void**)&m->ovf_dev, 256);
@@ -1634,6 +1719,70 @@ size_t upr_pack_split_f32(const float* w, int Cout, int Cin, int kh, int kw, voi
     memcpy((uint8_t*)out + wbytes, sp.scale.data(), sp.scale.size() * 4);
   }
   return need;
+}
+
+// bytes of upr_pack_split_w_f32's blob: the planes (4 bytes per weight), then 1 / s_n
+static size_t split_w_bytes(int Cout, int K, size_t* scale_off) {
+  const size_t wbytes = align_up((size_t)Cout * K * 4, 256);
+  if (scale_off) *scale_off = wbytes;
+  return wbytes + (size_t)Cout * 4;
+}
+
+size_t upr_pack_split_w_f32(const float* w, int Cout, int Cin, int kh, int kw, const float* w2, int C2, void* out,
+                            size_t out_bytes) {
+  if (!w || Cout <= 0 || Cout % 64 || Cin <= 0 || Cin % 32 || kh <= 0 || kw <= 0) return 0;
+  if ((w2 != nullptr) != (C2 > 0) || C2 < 0 || C2 % 32) return 0;
+  const int K1 = kh * kw * Cin, K = K1 + C2;
+  std::vector<float> rows((size_t)Cout * K);
+  for (int n = 0; n < Cout; ++n) {
+    memcpy(rows.data() + (size_t)n * K, w + (size_t)n * K1, (size_t)K1 * 4);
+    if (w2) memcpy(rows.data() + (size_t)n * K + K1, w2 + (size_t)n * C2, (size_t)C2 * 4);
+  }
+  SplitWPack sp;
+  if (!pack_split_w(Cout, K, rows.data(), sp)) return 0;
+  size_t soff = 0;
+  const size_t need = split_w_bytes(Cout, K, &soff);
+  if (out && out_bytes >= need) {
+    memset(out, 0, need);
+    memcpy(out, sp.W.data(), sp.W.size() * 2);
+    memcpy((uint8_t*)out + soff, sp.scale.data(), sp.scale.size() * 4);
+  }
+  return need;
+}
+
+int upr_conv2d_nhwc_wsplit(const void* x, int B, int H, int W, int Cin, const void* blob, size_t blob_bytes,
+                           const float* bias, int Cout, int kh, int kw, int stride, int pad, int dil,
+                           const void* residual, int relu, void* y, const void* x2, int H2, int W2, int C2,
+                           int stride2, unsigned* overflow, void* stream) {
+  if (!x || !blob || !y || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return UPR_ERR_ARG;
+  if (kh <= 0 || kw <= 0 || stride <= 0 || dil <= 0 || pad < 0) return UPR_ERR_ARG;
+  if (x2 && (H2 <= 0 || W2 <= 0 || C2 <= 0 || stride2 <= 0)) return UPR_ERR_ARG;
+  const int Ho = (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1;
+  const int Wo = (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
+  if (Ho <= 0 || Wo <= 0) return UPR_ERR_SHAPE;
+  if (x2 && ((H2 - 1) / stride2 + 1 != Ho || (W2 - 1) / stride2 + 1 != Wo)) return UPR_ERR_SHAPE;
+  if (Cin % 32 || Cout % 64 || (x2 && C2 % 32)) return UPR_ERR_UNSUPPORTED;
+  const int K1 = kh * kw * Cin, K = K1 + (x2 ? C2 : 0);
+  size_t soff = 0;
+  if (blob_bytes != split_w_bytes(Cout, K, &soff)) return UPR_ERR_UNSUPPORTED;  // packed for another shape
+  ConvOp c;
+  memset(&c, 0, sizeof(c));
+  c.nseg = x2 ? 2 : 1;
+  ConvSeg& s = c.seg[0];
+  s.src = x; s.C = Cin; s.cs = Cin; s.coff = 0; s.Hin = H; s.Win = W;
+  s.kh = kh; s.kw = kw; s.stride = stride; s.pad = pad; s.dil = dil; s.pre = kPreNone; s.kbase = 0;
+  if (x2) {
+    ConvSeg& t = c.seg[1];
+    t.src = x2; t.C = C2; t.cs = C2; t.coff = 0; t.Hin = H2; t.Win = W2;
+    t.kh = 1; t.kw = 1; t.stride = stride2; t.pad = 0; t.dil = 1; t.pre = kPreNone; t.kbase = K1;
+  }
+  c.B = B; c.Ho = Ho; c.Wo = Wo; c.N = Cout; c.Kpad = K;
+  c.W = blob; c.scale = (const float*)((const uint8_t*)blob + soff);
+  c.bias = bias; c.relu = relu;
+  c.res2 = residual; c.res2_cs = Cout;
+  c.out = y; c.out_cs = Cout; c.out_coff = 0; c.store = kStoreNHWC;
+  c.mma16 = 3; c.ovf = overflow;
+  return launch_conv_wsplit(c, (hipStream_t)stream);
 }
 
 int upr_split_f32(const float* x, void* y, size_t npix, int C, unsigned* overflow, void* stream) {

@@ -137,6 +137,10 @@ struct ConvOp {
   // form runs its exact fp32 form (conv_last_form tells which ran); 2: it
   // answers kErrUnsupported instead (launch_conv_regs).  ovf as above: set
   // when an accumulator is not finite (an input left the fp16 range).
+  // 3 (launch_conv_wsplit only): the weights were split once on the host -- W
+  // is the fp16 plane blob of model.hip pack_split_w ([N][Kpad / 32][W_hi(32) |
+  // W_lo(32)], as many bytes per row as the fp32 weights), scale the 1 / s_n
+  // vector; only the activation fragments are split in the kernel.
   // (placed in the padding before ovf: the struct, and with it every kernel
   // argument block, keeps its layout)
   int mma16;
@@ -201,6 +205,7 @@ int launch_conv_pw(const ConvOp& op, hipStream_t stream, bool probe = false);
 int launch_conv(const ConvOp& op, int dtype, hipStream_t stream);
 // the form the calling thread's latest launch_conv ran in: 0 = the dtype's own
 // kernels, 2 = split in registers (ConvOp::mma16)
+// (3, weights split once, is set by the caller of launch_conv_wsplit)
 int conv_last_form();
 void conv_set_last_form(int form);
 // an fp32 op in the split-in-registers form only (sets mma16 = 2): kOk, or
@@ -208,6 +213,13 @@ void conv_set_last_form(int form);
 int launch_conv_regs(const ConvOp& op, hipStream_t stream);
 
 int launch_conv_ring32(const ConvOp& op, hipStream_t st);
+// an fp32 op with its weights split once (ConvOp::mma16 == 3; conv_wide32.hip):
+// kOk, or kErrUnsupported -- it never runs another kernel
+int launch_conv_wsplit(const ConvOp& op, hipStream_t st);
+// position of channel c (0..31) of a 32-deep K step within a 32-half weight
+// plane of that form: lane group g = (c % 16) / 4 holds the 8 k-slots 4g..4g+3,
+// 16+4g..16+4g+3, the channels of its two ds_read_b128 of an fp32 A row
+inline int wsplit_kslot(int c) { return ((c & 15) >> 2) * 8 + (c >> 4) * 4 + (c & 3); }
 // fp16 wide-tile convs (conv_wide.hip), also the split-fp16 form of fp32 convs
 // (ConvOp::split_out); probe: only answer kOk / kErrUnsupported
 int launch_conv_wide(const ConvOp& op, hipStream_t st, bool probe = false);

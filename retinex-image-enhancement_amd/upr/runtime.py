@@ -128,7 +128,8 @@ class ModelHandle:
 
     def op_forms(self):
         """(name, form) per op of the most recent forward, in launch order: 0 the
-        model dtype's own kernels, 1 split-fp16 tensors, 2 split in registers."""
+        model dtype's own kernels, 1 split-fp16 tensors, 2 split in registers, 3
+        weights split once."""
         n = int(self._lib.upr_model_op_forms(self._h, None, 0))
         arr = (L.UprOpForm * max(n, 1))()
         n = int(self._lib.upr_model_op_forms(self._h, arr, n))
@@ -345,6 +346,58 @@ def conv2d_nhwc_regs(x, w_packed, bias, kh, kw, stride=1, pad=0, dil=1, residual
                                           stride, pad, dil, _ptr(residual), int(bool(relu)), _ptr(y), _ptr(overflow),
                                           _stream(x.device))
     L.check(rc, "upr_conv2d_nhwc_regs")
+    return y
+
+
+def pack_split_w(w_packed, kh, kw, w2=None):
+    """Packed fp32 conv weight [Cout, kh*kw*Cin] (pack_conv_weight), optionally with
+    a second 1x1 K-segment w2 [Cout, C2] (a projecting shortcut) -> the uint8
+    host blob conv2d_nhwc_wsplit takes: per output channel the fp16 planes W_hi
+    = fp16(w s_n), W_lo = fp16(w s_n - W_hi) in MFMA k-slot order, then float
+    1/s_n [Cout] at the next multiple of 256 bytes (include/upr.h)."""
+    wc = w_packed.detach().to("cpu", torch.float32).contiguous()
+    co, k = wc.shape
+    w2c = None if w2 is None else w2.detach().to("cpu", torch.float32).reshape(co, -1).contiguous()
+    c2 = 0 if w2c is None else w2c.shape[1]
+    p2 = ctypes.c_void_p(w2c.data_ptr()) if w2c is not None else None
+    lib = L.lib()
+    cin = k // (kh * kw) if k % (kh * kw) == 0 else 0
+    need = lib.upr_pack_split_w_f32(ctypes.c_void_p(wc.data_ptr()), co, cin, kh, kw, p2, c2, None, 0)
+    if need == 0:
+        raise ValueError(f"pack_split_w: unsupported weight shape {tuple(wc.shape)} + {c2} (Cout % 64, Cin % 32)")
+    blob = torch.empty(need, dtype=torch.uint8)
+    lib.upr_pack_split_w_f32(ctypes.c_void_p(wc.data_ptr()), co, cin, kh, kw, p2, c2, ctypes.c_void_p(blob.data_ptr()), need)
+    return blob
+
+
+def conv2d_nhwc_wsplit(x, w_blob, cout, bias, kh, kw, stride=1, pad=0, dil=1, residual=None, relu=False, x2=None,
+                       stride2=1, overflow=None):
+    """fp32 conv2d_nhwc on the fp16 MFMA unit with weights split once (w_blob:
+    pack_split_w, on the device), and in no other form: shapes its kernel does
+    not take raise UprError (UPR_ERR_UNSUPPORTED).  y = relu?(conv(x) +
+    conv1x1(x2 at stride2) + bias) + residual (added after the ReLU).
+
+    overflow: optional int32 device tensor of one element, set to 1 when an
+    input was outside the fp16 range (the output is then void)."""
+    _require_device(x)
+    if x.dtype != torch.float32:
+        raise ValueError("conv2d_nhwc_wsplit expects float32 tensors")
+    x = x.contiguous()
+    B, H, W, Cin = x.shape
+    Ho = (H + 2 * pad - dil * (kh - 1) - 1) // stride + 1
+    Wo = (W + 2 * pad - dil * (kw - 1) - 1) // stride + 1
+    y = torch.empty((B, Ho, Wo, cout), dtype=x.dtype, device=x.device)
+    if residual is not None:
+        residual = residual.contiguous()
+    H2 = W2 = C2 = 0
+    if x2 is not None:
+        x2 = x2.contiguous()
+        _, H2, W2, C2 = x2.shape
+    with torch.cuda.device(x.device):
+        rc = L.lib().upr_conv2d_nhwc_wsplit(_ptr(x), B, H, W, Cin, _ptr(w_blob), w_blob.numel(), _ptr(bias), cout, kh,
+                                            kw, stride, pad, dil, _ptr(residual), int(bool(relu)), _ptr(y), _ptr(x2),
+                                            H2, W2, C2, stride2, _ptr(overflow), _stream(x.device))
+    L.check(rc, "upr_conv2d_nhwc_wsplit")
     return y
 
 
