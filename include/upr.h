@@ -113,7 +113,17 @@ long long upr_model_forks(const UprModel* model);
  * was built (upr_pack_split_w_f32).  Env UPR_FP32_SPLIT=0, read by
  * upr_model_create, keeps the fp32 MFMA kernels everywhere; UPR_FP32_SPLIT_REGS=0
  * keeps them for the split-in-registers and weights-split-once ops,
- * UPR_FP32_SPLIT_W64=0 for the weights-split-once ops only.  The activations these
+ * UPR_FP32_SPLIT_W64=0 for the weights-split-once ops only.  The
+ * split-in-registers ops convert each element of their LDS row ring to (hi, lo)
+ * once, in place: one step before its first reader, beside the MFMAs, or at
+ * the top of the step that first reads it, behind a second barrier -- each
+ * kernel program in the form that measured faster.  UPR_RING_SPLIT_LDS=0 (read
+ * by upr_model_create; by upr_conv2d_nhwc_regs and upr_conv2d_nhwc with
+ * UPR_F32_SPLIT_REGS at every call) splits once per filter tap after the LDS
+ * read instead; 2 / 3 put every program on the top-of-step / one-step-ahead
+ * form (for measurements).  It is the same function on the same values in the
+ * same MFMA order, so every setting gives the same bits and the same form
+ * code (2); they differ in speed only.  The activations these
  * convs read must stay within the fp16 range (65504): a forward that leaves it
  * sets a flag, and from the next forward on the handle runs the fp32 kernels
  * for good (one line on stderr).  A UPR_MODEL_HEAD_ONLY handle of such a model

@@ -48,6 +48,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "upr_common.h"
 
@@ -93,19 +94,27 @@ enum RingFlags : int {
   kRingAblDma = 4096, kRingAblMma = 8192, kRingAblSt = 16384,
   // fp32 ring only: split in registers (ConvOp::mma16) -- the fragments are
   // split into fp16 (hi, lo) after the LDS read and run on v_mfma_f32_16x16x32_f16
-  kRingMma16 = 32768
+  kRingMma16 = 32768,
+  // with kRingMma16: the split runs once per ring element, in LDS (hi over
+  // plane 2o, lo over plane 2o + 1 of the element's channel octet o), not once
+  // per tap in registers.  kRingLds alone: a 5-group ring, DMA three steps
+  // ahead, each step converts the group its successor reads first;
+  // + kRingLdsTop: the 4-group ring, the group that has just landed is
+  // converted at the top of the step, behind a second barrier
+  kRingLds = 65536, kRingLdsTop = 131072
 };
 // kRingXPool (fp32 ring): two more K slices after the 3x3 segment, a 1x1 over
 // x and a 1x1 over maxpool3x3(x) (EnhancedFAM branch1 / branch2 composed with
 // the fusion), x staged in a second ring with a -inf halo
 
-// A ring of NPL chunk planes: 4 groups of GROWS rows of RW pixels.  DEINT:
+// A ring of NPL chunk planes: NGRP (4) groups of GROWS rows of RW pixels.  DEINT:
 // ring column p holds source column 2p (p < (RW+1)/2) or 2(p - (RW+1)/2) + 1.
-template <int NPL, int RW_, int GROWS_, bool DEINT_ = false>
+template <int NPL, int RW_, int GROWS_, bool DEINT_ = false, int NGRP_ = 4>
 struct Ring {
   static constexpr int RW = RW_;
   static constexpr int GROWS = GROWS_;
-  static constexpr int RR = 4 * GROWS;           // ring rows (power of two)
+  static constexpr int NGRP = NGRP_;
+  static constexpr int RR = NGRP * GROWS;        // ring rows (a power of two with 4 groups)
   static constexpr int PLANE = RR * RW * 16;     // bytes per chunk plane
   static constexpr int BYTES = NPL * PLANE;
   static constexpr int GPX = GROWS * RW;         // pixels per group
@@ -115,7 +124,7 @@ struct Ring {
   static constexpr bool DEINT = DEINT_;
   static constexpr int HALF = (RW + 1) / 2;
   static_assert(NPL % 4 == 0, "planes are split over the 4 waves");
-  static_assert((RR & (RR - 1)) == 0, "ring rows: power of two");
+  static_assert(NGRP != 4 || (RR & (RR - 1)) == 0, "ring rows: power of two");
 };
 
 // Per-lane DMA geometry of one ring: for DMA instruction i the lane's group
@@ -902,6 +911,21 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, RingCfg<MODE, C, NB, FL
 // and B leaves the sum unchanged): a lane reads its pixel's 8 channels as two
 // conflict-free ds_read_b128 (planes 2fg, 2fg+1) per tap and feeds 8 MFMAs.
 // fp32 MFMA time (32 cycles per 16x16x4) bounds these layers, not HBM.
+//
+// Split forms (kRingMma16): the lane's 8 channels become fp16 (hi, lo) and feed
+// v_mfma_f32_16x16x32_f16.  Per tap: split_f32x8 after every fragment read (a
+// ring element is read by up to nine taps: nine conversions).  In LDS
+// (kRingLds): each element is converted once -- a thread reads planes 2o, 2o +
+// 1 of a pixel (its channel octet o), splits, and writes hi over plane 2o, lo
+// over plane 2o + 1: the same 32 bytes, and the taps' two ds_read_b128 are the
+// MFMA operands as they stand.  Two schedules (ring32_form picks per program):
+// ahead -- the main ring has 5 groups and its DMA leads by three steps: step k
+// reads groups k, k + 1, converts group k + 2 (landed by its top barrier,
+// published by the next one) beside its MFMAs, groups k + 3, k + 4 are in
+// flight; step 0 converts two groups; top of step (kRingLdsTop) -- the 4-group
+// ring, step k converts group k + 1 right after its barrier and a second
+// barrier publishes it.  The x ring of kRingXPool stays fp32, 4 groups, two
+// steps ahead.  All three forms give the same bits.
 // ---------------------------------------------------------------------------
 // fp32 landing zone: rows of CPP 16-byte chunks read by ds_read_b128 lane
 // groups {fr 0-3, 12-15 | fg 0} + {fr 4-11 | fg 1}: (l >> 1) & 7 for 8-chunk
@@ -920,8 +944,19 @@ struct Ring32Cfg {
   static constexpr int DIL = (FL & kRingDil2) ? 2 : 1, HA = DIL;  // ring halo = the taps' reach
   static constexpr bool XP = (FL & kRingXPool) != 0;
   static constexpr int C = 32, NT = NB / 16, NG = 2;
-  using RA = Ring<8, 32 + 2 * HA, 4>;               // 32 fp32 channels = 8 chunk planes
-  using RB = Ring<8, 34, 4>;                        // kRingXPool: x, 1-pixel -inf halo
+  // split in LDS (kRingLds): LSA = converted one step ahead (5 groups: two
+  // being read, one being converted, two in flight; DMA three steps ahead),
+  // else at the top of the step (kRingLdsTop, the 4-group ring as it was)
+  static constexpr bool LS = (FL & kRingLds) != 0, LSA = LS && !(FL & kRingLdsTop);
+  static_assert(!LS || (FL & kRingMma16), "split in LDS: a form of the split-fp16 programs");
+  static_assert(LS || !(FL & kRingLdsTop), "kRingLdsTop qualifies kRingLds");
+  static constexpr int NGRP = LSA ? 5 : 4, LEAD = LSA ? 3 : 2;
+  using RA = Ring<8, 32 + 2 * HA, 4, false, NGRP>;  // 32 fp32 channels = 8 chunk planes
+  // kRingXPool: x, 1-pixel -inf halo; stays fp32 (the 3x3 max is taken in
+  // fp32), 4 groups and two steps ahead in every form
+  using RB = Ring<8, 34, 4>;
+  // conversion items of a group: (channel octet, group pixel), 256 threads
+  static constexpr int NCV = (4 * RA::GPX + 255) / 256;
   static constexpr int NSL = XP ? 11 : 9;           // K slices of 32 channels
   // filter in registers: 9 (11) slices x NT tiles x 8 floats = 144 (176) / 288
   // VGPRs (one wave per SIMD: 32 -> 64 fits in 504 registers without spills;
@@ -942,8 +977,18 @@ struct Ring32Cfg {
   static constexpr int LDS = WBYTES + RA::BYTES + (XP ? RB::BYTES : 0) + 4 * EW;
   static constexpr int G = RA::G + (XP ? RB::G : 0);
   static constexpr int S = HEAD ? NG : NG * NT;
+  // vmcnt waits at the top of step k.  LEAD 2: DMA(k) has landed; younger are
+  // stores(k-2), landing(k-1), DMA(k+1), stores(k-1).  LEAD 3: DMA(k+1) has
+  // landed (step k converts its group), issued one step earlier and needed one
+  // step earlier, so the same instructions are younger: stores(k-2),
+  // landing(k-1), DMA(k+2) (with the x ring's DMA(k+1), issued after it),
+  // stores(k-1).  Step 0: DMA(0) and DMA(1) under the last prologue DMA (LEAD
+  // 3: [x ring DMA(1),] DMA(2)); step 1: landing(0), one DMA, stores(0).  WF:
+  // + the pool atomics of a flush in that window (one step of it with LEAD 2,
+  // two with LEAD 3; a unit has >= 3 steps, so at most one flush)
   static constexpr int W0 = G, W1 = E + G + S, WK = 2 * S + E + G, WF = WK + (POOL ? 4 * NT : 0);
   static_assert(WF <= 63, "vmcnt immediate");
+  static_assert(!LS || LDS <= 160 * 1024, "the deeper ring fits one block per CU");
   static_assert(!RESPRE || RES, "kRingResPre qualifies kRingRes");
   static_assert(!(HEAD && (POOL || DIL == 2)), "head: plain 3x3");
   static_assert(!XP || (WREG && DIL == 1 && !RES && !HEAD), "x / maxpool slices: the FAM h3 part");
@@ -975,6 +1020,8 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
 
   // filter: lane (fr = n within tile, fg) holds W[nt*16 + fr][tap*32 + fg*8 .. +7]
   constexpr bool M16 = K::M16;
+  using RingCvt = std::integral_constant<bool, K::LS>;  // the main ring holds (hi, lo)
+  static_assert(K::NCV <= 3, "one conversion item per tap row");
   f32x4 wr[K::WREG && !M16 ? K::NSL : 1][NT][2];
   // split in registers: (W_hi, W_lo) of w s_n, s_n from the row's largest
   // magnitude (the row is read twice: once for the maximum, once to split);
@@ -1059,17 +1106,41 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
   };
   // RingLanes addresses half_t elements: an fp32 chunk c (4 channels) is at
   // half offset 8c, i.e. plane c <-> chunk c of the pixel
-  auto issue = [&](int k) {
+  // DMA(k) of the main ring goes to its group ga = (k + 1) mod NGRP; the x
+  // ring's (group gx = (k + 1) & 3) rides with it at LEAD 2 and has a cursor of
+  // its own, one step behind, at LEAD 3
+  Cursor dcx = cc;
+  auto issue = [&](int ga, int gx) {
     const bool live = dc.j < nu;
-    la.issue(srcA, csA, dc.b, sa.Hin, sa.Win, dc.y0 + 4 * dc.s + HA, dc.x0 - HA, live, zero, ringA, (k + 1) & 3, wave);
-    if constexpr (K::XP)
-      lb.issue(srcB, csB, dc.b, sx.Hin, sx.Win, dc.y0 + 4 * dc.s + 1, dc.x0 - 1, live, ninf, ringB, (k + 1) & 3, wave);
+    la.issue(srcA, csA, dc.b, sa.Hin, sa.Win, dc.y0 + 4 * dc.s + HA, dc.x0 - HA, live, zero, ringA, ga, wave);
+    if constexpr (K::XP && K::LEAD == 2)
+      lb.issue(srcB, csB, dc.b, sx.Hin, sx.Win, dc.y0 + 4 * dc.s + 1, dc.x0 - 1, live, ninf, ringB, gx, wave);
     advance(dc);
   };
+  auto issue_x = [&](int gx) {
+    if constexpr (K::XP && K::LEAD == 3) {
+      lb.issue(srcB, csB, dcx.b, sx.Hin, sx.Win, dcx.y0 + 4 * dcx.s + 1, dcx.x0 - 1, dcx.j < nu, ninf, ringB, gx, wave);
+      advance(dcx);
+    }
+  };
+  // split in LDS: the lane's conversion items of a group, item q = (channel
+  // octet o = q / GPX, group pixel q % GPX) at planes 2o, 2o + 1 (consecutive
+  // lanes take consecutive pixels: conflict-free 16-byte accesses)
+  int cvoff[K::LS ? K::NCV : 1];
+  if constexpr (K::LS) {
+#pragma unroll
+    for (int j = 0; j < K::NCV; ++j) {
+      const int q = j * 256 + tid;
+      cvoff[j] = q < 4 * RA::GPX ? 2 * (q / RA::GPX) * RA::PLANE + (q % RA::GPX) * 16 : -1;
+    }
+  }
 
   __syncthreads();
-  issue(0);
-  issue(1);
+  issue(1, 1);
+  issue_x(1);
+  issue(2, 2);
+  issue_x(2);
+  if constexpr (K::LEAD == 3) issue(3, 0);
 
   float bv[NT][4];
 #pragma unroll
@@ -1110,15 +1181,29 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
   for (int nt = 0; nt < (K::POOL ? NT : 1); ++nt)
 #pragma unroll
     for (int i = 0; i < 4; ++i) pool[nt][i] = 0.f;
-  bool flushed = false;
+  bool flushed = false, flushed2 = false;  // a pool flush one / two steps back
+  int gb = 0;                              // kk mod NGRP (rings of 5 groups)
 
   for (int kk = 0; kk < KT; ++kk) {
+    // group of step kk + d's DMA(kk + d - 1), 0 <= d < NGRP; ring row (4 kk + c) mod RR, 0 <= c < RR
+    auto grp_at = [&](int d) {
+      if constexpr (K::NGRP == 4) return (kk + d) & 3;
+      else return gb + d >= K::NGRP ? gb + d - K::NGRP : gb + d;
+    };
+    auto ring_row = [&](int c) {
+      if constexpr (K::NGRP == 4) return (4 * kk + c) & 15;
+      else return 4 * gb + c >= RA::RR ? 4 * gb + c - RA::RR : 4 * gb + c;
+    };
+    // split in LDS: this wave's conversion writes of the previous step are
+    // done before the barrier publishes them
+    if constexpr (K::LS) __builtin_amdgcn_s_waitcnt(0xC07F);
     // (the previous step's pool atomics, when it ended a unit, are younger than DMA(kk) too)
     if (kk == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K::W0) : "memory");
     else if (kk == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K::W1) : "memory");
-    else if (K::POOL && flushed) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K::WF) : "memory");
+    else if (K::POOL && (flushed || (K::LEAD == 3 && flushed2))) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K::WF) : "memory");
     else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K::WK) : "memory");
     __builtin_amdgcn_s_barrier();
+    flushed2 = flushed;
     flushed = false;
     const int s = cc.s, b = cc.b, x0 = cc.x0;
     const int yend = min(H, cc.y0 + a.rs);
@@ -1152,7 +1237,56 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
         __builtin_amdgcn_global_load_lds(p, (lds_void_ptr_r)epi, 16, 0, 0);
       }
     }
-    issue(kk + 2);
+    issue(grp_at(K::LEAD + 1), (kk + 3) & 3);
+    issue_x((kk + 3) & 3);
+
+    // split in LDS: a group's conversion = reads of the lane's items (cv_read),
+    // then per item split_f32x8 and hi -> plane 2o, lo -> plane 2o + 1 (cv_write:
+    // the item's own 32 bytes, nothing another lane touches)
+    f32x4 ct[K::LS ? K::NCV : 1][2];
+    auto cv_on = [&](int j) { return (j + 1) * 256 <= 4 * RA::GPX || cvoff[K::LS ? j : 0] >= 0; };
+    auto cv_read = [&](int grp) {
+      if constexpr (K::LS) {
+#pragma unroll
+        for (int j = 0; j < K::NCV; ++j)
+          if (cv_on(j)) {
+            const unsigned char* p = ringA + grp * (RA::GPX * 16) + cvoff[j];
+            ct[j][0] = *(const f32x4*)p;
+            ct[j][1] = *(const f32x4*)(p + RA::PLANE);
+          }
+      }
+    };
+    auto cv_write = [&](int grp, int j) {
+      if constexpr (K::LS) {
+        if (cv_on(j)) {
+          unsigned char* p = ringA + grp * (RA::GPX * 16) + cvoff[j];
+          const float v[8] = {ct[j][0][0], ct[j][0][1], ct[j][0][2], ct[j][0][3],
+                              ct[j][1][0], ct[j][1][1], ct[j][1][2], ct[j][1][3]};
+          f16x8_t hi, lo;
+          split_f32x8(v, hi, lo);
+          *(f16x8_t*)p = hi;
+          *(f16x8_t*)(p + RA::PLANE) = lo;
+        }
+      }
+    };
+    auto cv_group = [&](int grp) {  // one whole group, nothing overlapped
+      cv_read(grp);
+#pragma unroll
+      for (int j = 0; j < K::NCV; ++j) cv_write(grp, j);
+    };
+    const int cvg = grp_at(K::LSA ? 2 : 1);  // the group this step converts
+    if constexpr (K::LSA) {
+      // ahead: DMA(kk + 1)'s group, which step kk + 1 reads first; its reads go
+      // out here, the splits and writes ride with the MFMAs below.  Step 0 also
+      // converts DMA(0)'s group (both have landed: W0)
+      if (kk == 0) cv_group(1);
+      cv_read(cvg);
+    } else if constexpr (K::LS) {
+      // top of the step: DMA(kk)'s group, published by a second barrier
+      cv_group(cvg);
+      __builtin_amdgcn_s_waitcnt(0xC07F);
+      __builtin_amdgcn_s_barrier();
+    }
 
     f32x4 acc[NT][NG];
 #pragma unroll
@@ -1168,10 +1302,17 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
         for (int g = 0; g < NG; ++g) acc2[nt][g] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     // one 32-channel K slice of pixel group g against filter slice t
-    auto mm16 = [&](int t, int g, const f32x4& x0, const f32x4& x1, const f16x8_t (&wlo)[NT]) {
-      const float v[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+    // (x0, x1: the lane's two 16-byte chunks; CVT: of a converted ring, hi and
+    // lo as they stand, else 8 fp32 values split here)
+    auto mm16 = [&](auto cvt, int t, int g, const f32x4& x0, const f32x4& x1, const f16x8_t (&wlo)[NT]) {
       f16x8_t xh, xl;
-      split_f32x8(v, xh, xl);
+      if constexpr (decltype(cvt)::value) {
+        xh = __builtin_bit_cast(f16x8_t, x0);
+        xl = __builtin_bit_cast(f16x8_t, x1);
+      } else {
+        const float v[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+        split_f32x8(v, xh, xl);
+      }
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
         acc[nt][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t][nt], xh, acc[nt][g], 0, 0, 0);
@@ -1198,7 +1339,7 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
         f16x8_t wlt[2][NT];  // W_lo of tap t in wlt[t & 1] (read with chunk 2t, used by chunks 2t and 2t + 1)
         auto ldt = [&](int c, f32x4 (&x)[2]) {
           const int r = (c >> 1) / 3, sc = (c >> 1) % 3, g = c & 1;
-          const unsigned char* xr = ringA + abase + ((4 * kk + 4 + wave - HA + (r - 1) * DIL) & 15) * (RA::RW * 16) +
+          const unsigned char* xr = ringA + abase + ring_row(4 + wave - HA + (r - 1) * DIL) * (RA::RW * 16) +
                                     (g * 16 + HA + (sc - 1) * DIL) * 16;
 #pragma unroll
           for (int h = 0; h < 2; ++h) x[h] = *(const f32x4*)(xr + h * RA::PLANE);
@@ -1208,7 +1349,7 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
               wlt[(c >> 1) & 1][nt] = *(const f16x8_t*)(Wl + ((c >> 1) * NT + nt) * 1024 + lane * 16);
           }
         };
-        auto mmt = [&](int c, const f32x4 (&x)[2]) { mm16(c >> 1, c & 1, x[0], x[1], wlt[(c >> 1) & 1]); };
+        auto mmt = [&](int c, const f32x4 (&x)[2]) { mm16(RingCvt{}, c >> 1, c & 1, x[0], x[1], wlt[(c >> 1) & 1]); };
         ldt(0, tx[0]);
         ldt(1, tx[1]);
         RING_LDS_DONE;
@@ -1219,6 +1360,8 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
           if (c + 1 < 18) ldt(c + 1, tx[(c + 1) & 1]);
           RING_FENCE;
           mmt(c, tx[c & 1]);
+          // converting ahead: one item beside each of the first chunks' MFMAs
+          if (K::LSA && c <= K::NCV) cv_write(cvg, c - 1);
           RING_LDS_DONE;
         }
       }
@@ -1226,7 +1369,7 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
     if (s >= 0 && !TAPCH) {
       // chunk = one tap row r: 3 taps x 2 groups x 2 halves of X (+ 3 x NT x 2 of W from LDS)
       // ring row of tap row r (input row y + (r - 1) * DIL); ring column of tap sc below
-      auto rowA = [&](int r) { return ((4 * kk + 4 + wave - HA + (r - 1) * DIL) & 15) * (RA::RW * 16); };
+      auto rowA = [&](int r) { return ring_row(4 + wave - HA + (r - 1) * DIL) * (RA::RW * 16); };
       constexpr int NW = K::WREG ? 1 : 3;
       f32x4 bx[2][3][NG][2], bw[2][NW][NT][2];
       auto ld = [&](int r, f32x4 (&x)[3][NG][2], f32x4 (&w)[NW][NT][2]) {
@@ -1253,7 +1396,9 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
 #pragma unroll
           for (int sc = 0; sc < 3; ++sc)
 #pragma unroll
-            for (int g = 0; g < NG; ++g) mm16(r * 3 + sc, g, x[sc][g][0], x[sc][g][1], wl[r * 3 + sc]);
+            for (int g = 0; g < NG; ++g) mm16(RingCvt{}, r * 3 + sc, g, x[sc][g][0], x[sc][g][1], wl[r * 3 + sc]);
+          // converting ahead: one item beside each tap row's MFMAs
+          if (K::LSA && r < K::NCV) cv_write(cvg, r);
           return;
         }
 #pragma unroll
@@ -1321,8 +1466,8 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
           // the 3x3 max is taken in fp32 as in the exact form, then split
 #pragma unroll
           for (int g = 0; g < NG; ++g) {
-            mm16(9, g, ctr[g][0], ctr[g][1], wl[K::XP ? 9 : 0]);
-            mm16(10, g, mx[g][0], mx[g][1], wl[K::XP ? 10 : 0]);
+            mm16(std::false_type{}, 9, g, ctr[g][0], ctr[g][1], wl[K::XP ? 9 : 0]);
+            mm16(std::false_type{}, 10, g, mx[g][0], mx[g][1], wl[K::XP ? 10 : 0]);
           }
         } else {
 #pragma unroll
@@ -1343,6 +1488,13 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
     }
 #undef RING_LDS_DONE
 #undef RING_FENCE
+    if constexpr (K::LSA) {
+      // a unit's DMA-only step has no MFMAs to hide the conversion behind
+      if (s < 0) {
+#pragma unroll
+        for (int j = 0; j < K::NCV; ++j) cv_write(cvg, j);
+      }
+    }
 
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K::G) : "memory");
     if constexpr (M16) {
@@ -1433,6 +1585,7 @@ __global__ __launch_bounds__(256) void conv_ring32_kernel(RingArgs a) {
       }
     }
     advance(cc);
+    if constexpr (K::NGRP != 4) gb = gb + 1 == K::NGRP ? 0 : gb + 1;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if constexpr (M16) {
@@ -1630,7 +1783,16 @@ template <int MODE, int NB, int FL>
 static int ring32_form(const ConvOp& op, hipStream_t st) {
   if constexpr (Ring32Cfg<MODE, NB, FL>::WREG) {
     if (op.mma16) {
-      const int rc = launch_ring32_cfg<MODE, NB, FL | kRingMma16>(op, st);
+      // ConvOp::ring_split: where the activations are split (the results are
+      // bit-equal).  0 = the form that measured faster for the program
+      // (DESIGN.md 4.3): converted ahead for the plain 32 -> 32 convs (+-
+      // residual), at the top of the step for the head, 32 -> 64, dilation-2 and
+      // x / maxpool programs
+      constexpr bool AHEAD = MODE == kRingConv && NB == 32 && !(FL & (kRingDil2 | kRingXPool));
+      const int form = op.ring_split ? op.ring_split : AHEAD ? 3 : 2;
+      const int rc = form == 1   ? launch_ring32_cfg<MODE, NB, FL | kRingMma16>(op, st)
+                     : form == 2 ? launch_ring32_cfg<MODE, NB, FL | kRingMma16 | kRingLds | kRingLdsTop>(op, st)
+                                 : launch_ring32_cfg<MODE, NB, FL | kRingMma16 | kRingLds>(op, st);
       if (rc == kOk) conv_set_last_form(2);
       return rc;
     }

@@ -463,6 +463,11 @@ struct UprModel {
   // the same ovf word.  op_forms: the form each op of the latest forward ran in
   // (upr_model_op_forms)
   int split_regs = 0;
+  // ConvOp::ring_split of those ops (env UPR_RING_SPLIT_LDS, read at creation:
+  // unset / 1 -> 0, the split once per ring element in LDS, each program in
+  // its faster form; 0 -> 1, once per tap in registers; 2 / 3 -> every program
+  // converts at the top of the step / one step ahead)
+  int ring_split = 0;
   // Weights split once (env UPR_FP32_SPLIT_W64, read at creation): in state 1,
   // with split_regs on, the ops that got planes at build time (Op::w64_w: the
   // 64-wide convs at half resolution) run in that form (3), same guard word
@@ -1247,7 +1252,7 @@ static int run_forward(UprModel* m, const void* x, int B, int H, int W, void* en
             if (rc == kOk) forms[oi] = 3;
           }
           if (rc == kErrUnsupported) {
-            if (regs_now && dt == kF32) { c.mma16 = 1; c.ovf = m->ovf_dev; }
+            if (regs_now && dt == kF32) { c.mma16 = 1; c.ovf = m->ovf_dev; c.ring_split = m->ring_split; }
             rc = launch_conv(c, dt, st);
             forms[oi] = conv_last_form();
           }
@@ -1464,6 +1469,14 @@ int launch_unsplit_f32(const void* x, float* y, size_t npix, int C, hipStream_t 
   return (int)hipGetLastError();
 }
 
+// ConvOp::ring_split from UPR_RING_SPLIT_LDS as it is set now
+static int ring_split_env() {
+  const char* e = getenv("UPR_RING_SPLIT_LDS");
+  if (!e || !*e) return 0;
+  const int v = atoi(e);
+  return v == 0 ? 1 : v == 2 || v == 3 ? v : 0;
+}
+
 }  // namespace upr
 
 // ===========================================================================
@@ -1506,6 +1519,8 @@ int upr_model_create(const UprTensorDesc* params, int n_params, int use_preact, 
   // kernels while the region stays split
   const char* sr = getenv("UPR_FP32_SPLIT_REGS");
   m->split_regs = !(sr && *sr && atoi(sr) == 0);
+  // UPR_RING_SPLIT_LDS=0 keeps those ops' per-tap split (the same bits)
+  m->ring_split = ring_split_env();
   // UPR_FP32_SPLIT_W64=0 keeps the weights-split-once ops (the 64-wide convs
   // at half resolution) on the fp32 MFMA kernel alone
   const char* sw = getenv("UPR_FP32_SPLIT_W64");
@@ -1701,6 +1716,7 @@ int upr_conv2d_nhwc_regs(const void* x, int B, int H, int W, int Cin, const void
   c.res2 = residual; c.res2_cs = Cout;
   c.out = y; c.out_cs = Cout; c.out_coff = 0; c.store = kStoreNHWC;
   c.mma16 = 1; c.ovf = overflow;
+  c.ring_split = ring_split_env();  // read at the call: one process can run both programs
   return launch_conv_regs(c, (hipStream_t)stream);
 }
 

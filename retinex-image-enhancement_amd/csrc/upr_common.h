@@ -145,6 +145,14 @@ struct ConvOp {
   // argument block, keeps its layout)
   int mma16;
   unsigned* ovf;
+  // Where the row ring's split-in-registers programs (mma16 1 / 2) split their
+  // activations; every choice gives the same bits.  0: once per ring element,
+  // in LDS, in the form (2 or 3) that measured faster for the program; 1: once
+  // per tap, in registers after the LDS read (env UPR_RING_SPLIT_LDS=0); 2: in
+  // LDS at the top of the step that first reads the group, behind a second
+  // barrier (UPR_RING_SPLIT_LDS=2); 3: in LDS one step ahead of the first
+  // reader, beside the MFMAs, in a 5-group ring (UPR_RING_SPLIT_LDS=3)
+  int ring_split;
 };
 
 // 2^11 / 2^-11: the scale of the lo half of a split-fp16 value (ConvOp::split_out)
