@@ -304,6 +304,42 @@ size_t upr_content_aware_workspace(int B, int H, int W);
 int upr_content_aware(const void* x, const void* enh, void* out, float* saliency, float* attention, void* workspace,
                       size_t workspace_bytes, int B, int H, int W, int dtype, void* stream);
 
+/* calculate_metrics with calculate_psnr / calculate_ssim / calculate_niqe /
+ * calculate_saturation / calculate_naturalness (utils/utils.py:95-333) for every
+ * image of enh [B,3,H,W] (H, W >= 8); `ref` (the ground truth, same shape and
+ * dtype) may be NULL.  The reference takes one image per call on the host;
+ * here each image of the batch is measured on its own, and its result does
+ * not depend on B or on its position.  fp16 input is widened to fp32 exactly.
+ * metrics fp64 [B][UPR_METRICS_N], in the order of the UPR_METRIC_* indices:
+ * mean_brightness, contrast (:125-130), entropy (np.histogram, 256 bins over
+ * [0,1], :133-137), niqe (:250-278; gray and gray^2 in float32, the 7x7 means
+ * in fp64 with scipy's `reflect` border, sigma = sqrt(max(E[g^2] - mu^2, 0)) --
+ * the reference yields NaN where float32 rounding makes a flat window's
+ * variance negative), saturation (:281-303), naturalness (:306-333), then mse
+ * (:170), psnr (:186-202) and ssim (:205-247; 11x11 box means in fp64, zero
+ * border, divisor 121), the last three NaN when ref is NULL.
+ * sums fp64 [B][UPR_METRICS_NSUMS] (nullable), the raw per-image sums:
+ * 0-2 sum x per channel, 3-5 sum x^2 per channel, 6 sum of the per-pixel
+ * saturation, 7 sum sigma, 8 sum mu, 9 sum mu^2 (NIQE), 10 sum (x - y)^2 over
+ * the three channels, 11-13 sum of the SSIM map per channel (10-13 NaN when
+ * ref is NULL).  hist int32 [B,256] (nullable): the entropy's histogram.
+ * Sums are added in a fixed order: a rerun gives the same bits. */
+enum { UPR_METRICS_N = 9, UPR_METRICS_NSUMS = 14 };
+enum {
+  UPR_METRIC_MEAN_BRIGHTNESS = 0,
+  UPR_METRIC_CONTRAST = 1,
+  UPR_METRIC_ENTROPY = 2,
+  UPR_METRIC_NIQE = 3,
+  UPR_METRIC_SATURATION = 4,
+  UPR_METRIC_NATURALNESS = 5,
+  UPR_METRIC_MSE = 6,
+  UPR_METRIC_PSNR = 7,
+  UPR_METRIC_SSIM = 8
+};
+size_t upr_image_metrics_workspace(int B, int H, int W);
+int upr_image_metrics(const void* enh, const void* ref, double* metrics, double* sums, int32_t* hist,
+                      void* workspace, size_t workspace_bytes, int B, int H, int W, int dtype, void* stream);
+
 /* Host copies of the 8-bit Lab integer tables (for CPU-side verification):
  * gamma[256], cbrt[3072], yf[512], invgamma[4096] (uint16), rgb2xyz[9], xyz2rgb[9]. */
 void upr_lab_tables(uint16_t* gamma, uint16_t* cbrt, uint16_t* yf, uint16_t* invgamma, int32_t* rgb2xyz,

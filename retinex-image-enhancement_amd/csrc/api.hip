@@ -24,6 +24,9 @@ int launch_ms_features(const void* x, void* out, int B, int H, int W, int scale_
 size_t content_aware_ws(int B, int H, int W);
 int launch_content_aware(const void* x, const void* enh, void* out, float* sal_out, float* att_out, uint8_t* ws,
                          int B, int H, int W, int dtype, hipStream_t st);
+size_t metrics_ws(int B, int H, int W);
+int launch_metrics(const void* enh, const void* ref, double* metrics, double* sums, int* hist, uint8_t* ws, int B,
+                   int H, int W, int dtype, hipStream_t st);
 int launch_decompose(const void* x, const void* illu, void* refl, int B, int C, int HW, int illu_c, int dtype,
                      hipStream_t st);
 int launch_decompose_bwd(const void* x, const void* illu, const void* g, void* gx, void* gillu, int B, int C, int HW,
@@ -121,6 +124,20 @@ int upr_content_aware(const void* x, const void* enh, void* out, float* saliency
   if (workspace_bytes < content_aware_ws(B, H, W)) return UPR_ERR_WORKSPACE;
   return launch_content_aware(x, enh, out, saliency, attention, (uint8_t*)workspace, B, H, W, dtype,
                               (hipStream_t)stream);
+}
+
+size_t upr_image_metrics_workspace(int B, int H, int W) {
+  if (B <= 0 || H <= 0 || W <= 0) return 0;
+  return metrics_ws(B, H, W);
+}
+
+int upr_image_metrics(const void* enh, const void* ref, double* metrics, double* sums, int32_t* hist,
+                      void* workspace, size_t workspace_bytes, int B, int H, int W, int dtype, void* stream) {
+  if (!enh || !metrics || !workspace || !dtype_ok(dtype)) return UPR_ERR_ARG;
+  // (one image's byte offsets are 32-bit buffer offsets, and 2^30 must lie past the image)
+  if (B < 1 || H < 8 || W < 8 || (long long)H * W * 3 * 4 > 0x40000000LL) return UPR_ERR_SHAPE;
+  if (workspace_bytes < metrics_ws(B, H, W)) return UPR_ERR_WORKSPACE;
+  return launch_metrics(enh, ref, metrics, sums, hist, (uint8_t*)workspace, B, H, W, dtype, (hipStream_t)stream);
 }
 
 int upr_retinex_decompose(const void* x, const void* illu, void* refl, int B, int C, int H, int W, int illu_c,

@@ -13,6 +13,9 @@ and every step runs on the HIP path (train_step, losses/loss.py TotalLoss,
 upr.optim.Adam); schedulers, early stopping, latest_model.pth / best_model.pth
 and results.csv follow the reference (trainers/train.py:189-396).  --seed also
 seeds the shuffle, the augmentation draws and the noise generator.
+--mode evaluate (an addition) runs no model: the image-quality metrics of
+utils/utils.py for every image of --input_path, against --reference_dir when
+given, written to <output_dir>/metrics.csv.
 """
 import argparse
 import os
@@ -33,7 +36,7 @@ from enhancers.adaptive_params import AdaptiveParameterAdjuster  # noqa: E402
 
 def build_parser():
     p = argparse.ArgumentParser(description='UP-Retinex: 基于Retinex理论的低光照图像增强 (MI355X)')
-    p.add_argument('--mode', type=str, choices=['train', 'predict', 'enhance'], default='predict')
+    p.add_argument('--mode', type=str, choices=['train', 'predict', 'enhance', 'evaluate'], default='predict')
     p.add_argument('--train_dir', type=str, default='./data/train')
     p.add_argument('--test_dir', type=str, default='./data/test')
     p.add_argument('--input_path', type=str, default='./data/test')
@@ -73,6 +76,8 @@ def build_parser():
     # additions
     p.add_argument('--seed', type=int, default=None, help='seed the random init (reproducible outputs)')
     p.add_argument('--precision', choices=['fp32', 'fp16'], default='fp32')
+    p.add_argument('--reference_dir', type=str, default=None,
+                   help='--mode evaluate: ground-truth images, matched by file stem (adds psnr / ssim / mse)')
     return p
 
 
@@ -106,6 +111,77 @@ def _predict_one(model, path, args):
         create_comparison(x, enh, os.path.join(args.output_dir, f"{name}_comparison.png"), illu_map=illu)
 
 
+def _reference_stems(reference_dir):
+    by_stem = {}
+    for f in list_images(reference_dir):
+        by_stem.setdefault(Path(f).stem, f)
+    return by_stem
+
+
+def _reference_for(path, reference_dir, by_stem=None):
+    """The ground truth of NAME.ext: the file of --reference_dir with stem NAME,
+    else with NAME's trailing `_enhanced` removed."""
+    stem = Path(path).stem
+    stems = [stem] + ([stem[:-len('_enhanced')]] if stem.endswith('_enhanced') else [])
+    if by_stem is None:
+        by_stem = _reference_stems(reference_dir)
+    for s in stems:
+        if s in by_stem:
+            return by_stem[s]
+    raise ValueError(f"no reference image for '{path}' in '{reference_dir}' (looked for stem "
+                     f"{' or '.join(repr(s) for s in stems)})")
+
+
+def evaluate(args):
+    """Metrics of every image of --input_path (utils.utils.batch_metrics) -> <output_dir>/metrics.csv:
+    `file`, then the metric names in calculate_metrics' order; one row per image
+    (values as repr(float)) and a last row `mean` of the column means.
+    Consecutive images of one size share a launch, up to --batch_size."""
+    from utils.utils import batch_metrics, metric_names
+    p = Path(args.input_path)
+    files = [str(p)] if p.is_file() else (list_images(str(p)) if p.is_dir() else None)
+    if not files:
+        print(f"错误: 输入路径 '{args.input_path}' 不存在")
+        return None
+    paired = args.reference_dir is not None
+    names = metric_names(paired)
+    by_stem = _reference_stems(args.reference_dir) if paired else None
+    cols = []  # per launch: [n_metrics, b] device tensors
+
+    def flush(xs, ys):
+        if xs:
+            m = batch_metrics(torch.cat(xs), torch.cat(ys) if paired else None)
+            cols.append(torch.stack([m[n] for n in names]))
+
+    xs, ys = [], []
+    for f in files:
+        x, _ = load_image(f, args.max_size, device=args.device)
+        y = None
+        if paired:
+            rf = _reference_for(f, args.reference_dir, by_stem)
+            y, _ = load_image(rf, args.max_size, device=args.device)
+            if y.shape != x.shape:
+                raise ValueError(f"reference '{rf}' is {tuple(y.shape[2:])} after loading, '{f}' is "
+                                 f"{tuple(x.shape[2:])}")
+        if xs and (x.shape != xs[0].shape or len(xs) >= max(1, args.batch_size)):
+            flush(xs, ys)
+            xs, ys = [], []
+        xs.append(x)
+        ys.append(y)
+    flush(xs, ys)
+    table = torch.cat(cols, dim=1).t().cpu().tolist()  # the one device-to-host copy
+    means = [sum(r[k] for r in table) / len(table) for k in range(len(names))]
+    os.makedirs(args.output_dir, exist_ok=True)
+    out = os.path.join(args.output_dir, 'metrics.csv')
+    with open(out, 'w') as fh:
+        fh.write(','.join(('file',) + tuple(names)) + '\n')
+        for f, r in zip(files, table):
+            fh.write(','.join([os.path.basename(f)] + [repr(float(v)) for v in r]) + '\n')
+        fh.write(','.join(['mean'] + [repr(float(v)) for v in means]) + '\n')
+    print(f"评估完成: {len(files)} 张图像, " + ', '.join(f"{n}={v:.4f}" for n, v in zip(names, means)) + f" -> {out}")
+    return out
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.device is None:
@@ -115,6 +191,9 @@ def main(argv=None):
     if args.mode == 'train':
         from trainers.train import train
         train(args)
+        return
+    if args.mode == 'evaluate':
+        evaluate(args)
         return
     if args.mode == 'predict':
         if not os.path.exists(args.checkpoint):

@@ -45,6 +45,11 @@ class UprOpForm(ctypes.Structure):
                 ("form", ctypes.c_int)]
 
 
+# include/upr.h UPR_METRICS_* / UPR_METRIC_*: upr_image_metrics' output widths and metric order
+UPR_METRICS_N = 9
+UPR_METRICS_NSUMS = 14
+METRIC_NAMES = ("mean_brightness", "contrast", "entropy", "niqe", "saturation", "naturalness", "mse", "psnr", "ssim")
+
 UPR_OP_CONV_IGEMM = 0
 UPR_OP_OTHER = 1
 UPR_CALIB_MFMA_F16 = 0
@@ -94,6 +99,9 @@ SIGNATURES = {
     "upr_multiscale_features": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "upr_content_aware_workspace": (c_size_t, [c_int, c_int, c_int]),
     "upr_content_aware": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int,
+                                  c_int, c_int, c_void_p]),
+    "upr_image_metrics_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "upr_image_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int,
                                   c_int, c_int, c_void_p]),
     "upr_lab_tables": (None, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "upr_retinex_decompose": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -518,6 +518,34 @@ def content_aware(x, enh=None, saliency=False, attention=False):
     return out, sal, att
 
 
+def image_metrics(enh, ref=None, sums=False, hist=False):
+    """calculate_metrics (utils/utils.py:95-333) of every image of enh [B,3,H,W]
+    against ref (same shape and dtype, optional).  Returns (metrics [B,9] f64 in
+    the order of _lib.METRIC_NAMES, the last three NaN without ref; sums [B,14]
+    f64 or None; hist [B,256] int32 or None), all on the device, no synchronisation."""
+    _require_device(enh)
+    if enh.dim() != 4 or enh.shape[1] != 3:
+        raise RuntimeError(f"expected an image batch of shape [B, 3, H, W], got {tuple(enh.shape)}")
+    if ref is not None:
+        _require_device(ref, "reference")
+        if ref.shape != enh.shape or ref.dtype != enh.dtype or ref.device != enh.device:
+            raise RuntimeError("image_metrics: the reference must match the image's shape, dtype and device")
+        ref = ref.contiguous()
+    enh = enh.contiguous()
+    B, _, H, W = enh.shape
+    dev = enh.device
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        m = torch.empty((B, L.UPR_METRICS_N), dtype=torch.float64, device=dev)
+        s = torch.empty((B, L.UPR_METRICS_NSUMS), dtype=torch.float64, device=dev) if sums else None
+        h = torch.empty((B, 256), dtype=torch.int32, device=dev) if hist else None
+        ws = _WS.get(dev, lib.upr_image_metrics_workspace(B, H, W))
+        rc = lib.upr_image_metrics(_ptr(enh), _ptr(ref), _ptr(m), _ptr(s), _ptr(h), _ptr(ws),
+                                   ctypes.c_size_t(ws.numel()), B, H, W, dtype_code(enh.dtype), _stream(dev))
+    L.check(rc, "upr_image_metrics")
+    return m, s, h
+
+
 class _Decompose(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, illu):
