@@ -385,11 +385,15 @@ int upr_t_bilinear16(const UprView* x, int B, int H, int W, int C, const UprView
 /* out[B][C] (+)= scale * sum over pixels (AdaptiveAvgPool2d(1) with scale = 1/HW). */
 int upr_t_pixel_sum(const float* x, int B, int HW, int C, int cs, int coff, float scale, float* out, int accumulate,
                     void* stream);
-/* y[b][p][c] (+)= v[b][c] * scale  (broadcast of a per-image vector). */
+/* y[b][p][y_coff + c] (+)= v[b][c] * scale  (broadcast of a per-image vector
+ * into a channel slice, channel stride y_cs).  y_cs < y_coff + C:
+ * UPR_ERR_ARG, nothing written. */
 int upr_t_broadcast(const float* v, int B, int HW, int C, float scale, float* y, int y_cs, int y_coff, int accumulate,
                     void* stream);
 /* y16[b][p][y_coff + c] = (half)(v[b][c] * scale): the fp16 form (a channel
- * slice of an fp16 copy, channel stride y_cs). */
+ * slice of an fp16 copy, channel stride y_cs).  y_cs < y_coff + C:
+ * UPR_ERR_ARG; C, y_cs or y_coff no multiple of 4, or y16 not 8-byte aligned:
+ * UPR_ERR_UNSUPPORTED.  Nothing written in either case. */
 int upr_t_broadcast16(const float* v, int B, int HW, int C, float scale, void* y16, int y_cs, int y_coff,
                       void* stream);
 
@@ -406,7 +410,12 @@ int upr_t_fam_sa_bwd(const float* g, const float* o2, const float* sa, int B, in
  * (the fusion concat's first slice read in place, no split copy). */
 int upr_t_fam_sa_bwd_cs(const float* g, int g_cs, const float* o2, const float* sa, int B, int HW, int C,
                         float* g_o2, float* g_spre, void* stream);
-/* g_o2 += g_m (mean/max routes); g_o = g_o2*ca; g_ca[b][c] += sum_p g_o2*o. */
+/* g_t = g_o2 + g_m[..][0]/C on every channel + g_m[..][1] on the channel of
+ * o2's maximum (torch.max(dim)'s: the first maximum, or the first NaN); g_o =
+ * g_t*ca; g_ca[b][c] = sum_p g_t*o.  g_o2 is read only; g_o and g_ca are
+ * overwritten (g_ca needs no zeroing by the caller).  C <= 32, else
+ * UPR_ERR_ARG (nothing written).  C == 32 on 16-byte aligned buffers sums g_ca
+ * in a fixed order (deterministic); the rest adds block partials atomically. */
 int upr_t_fam_ca_bwd(const float* g_o2, const float* g_m, const float* o, const float* o2, const float* ca, int B,
                      int HW, int C, float* g_o, float* g_ca, void* stream);
 /* g_o = (g_o + g_pool[b][c]/HW) * (o > 0). */

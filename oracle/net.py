@@ -78,7 +78,8 @@ def fam(sd, p, x):
                              F.relu(_conv(sd, p + ".channel_attention.1", g))))
     out = out * ca
     # spatial attention: [mean_c, max_c] -> 7x7 conv -> sigmoid (model.py:56-59, 92-95)
-    m = torch.cat([out.mean(1, keepdim=True), out.amax(1, keepdim=True)], 1)
+    # (torch.max(dim), not amax: on a tie its gradient goes to one index whole, amax splits it)
+    m = torch.cat([out.mean(1, keepdim=True), torch.max(out, 1, keepdim=True)[0]], 1)
     sa = torch.sigmoid(_conv(sd, p + ".spatial_attention.0", m, padding=3))
     return out * sa
 

@@ -744,10 +744,13 @@ int upr_t_bilinear16(const UprView* x, int B, int H, int W, int C, const UprView
 
 int upr_t_pixel_sum(const float* x, int B, int HW, int C, int cs, int coff, float scale, float* out, int accumulate,
                     void* stream) {
-  if (!x || !out || B <= 0 || HW <= 0) return UPR_ERR_ARG;
+  if (!x || !out || B <= 0 || HW <= 0 || C <= 0) return UPR_ERR_ARG;
   if (C % 4 == 0 && C <= 1024 && cs % 4 == 0 && coff % 4 == 0 && ((uintptr_t)x & 15) == 0) {
     hipStream_t st = ST(stream);
-    int chunks = HW / 1024;
+    // about 32 rows a lane whatever C (R = 256 / (C / 4) row groups a block; C = 32: HW / 1024).
+    // HW / 1024 for every C left a lane of the wide forms (C = 256: R = 4, C = 1024: R = 1) a
+    // sequential chain of up to 1024 / R rows, 8 ulp off float64 at 300 rows, on a handful of blocks.
+    int chunks = HW / (32 * (256 / (C / 4)));
     chunks = chunks < 1 ? 1 : (chunks > 256 ? 256 : chunks);
     float* part = (float*)scratch(kSlotPart, sizeof(float) * (size_t)B * chunks * C, st);
     if (!part) return (int)hipErrorOutOfMemory;
@@ -766,7 +769,7 @@ int upr_t_pixel_sum(const float* x, int B, int HW, int C, int cs, int coff, floa
 
 int upr_t_broadcast(const float* v, int B, int HW, int C, float scale, float* y, int y_cs, int y_coff, int accumulate,
                     void* stream) {
-  if (!v || !y) return UPR_ERR_ARG;
+  if (!v || !y || B <= 0 || HW <= 0 || C <= 0 || y_cs < y_coff + C) return UPR_ERR_ARG;
   const long long n = (long long)B * HW * C;
   hipLaunchKernelGGL(broadcast_kernel, dim3(grid_for(n)), dim3(256), 0, ST(stream), v, B, HW, C, scale, y, y_cs,
                      y_coff, accumulate);
