@@ -39,17 +39,38 @@ int upr_t_zero(void* p, size_t bytes, void* stream);
 
 /* ---- convolution ------------------------------------------------------- */
 
-/* nn.Conv2d.forward for any channel count (model.py:29-62 small convs:
+/* The direct (small-channel) convolution family: upr_t_conv_direct,
+ * upr_t_conv_direct16, upr_t_conv_direct_dgrad, upr_t_conv_direct_wgrad and
+ * upr_t_conv_direct_wgrad_relu.  All five check their arguments the same way
+ * and launch nothing, write nothing, when a check fails:
+ *   UPR_ERR_ARG    a NULL view, a view with NULL data, a NULL w (forward,
+ *                  dgrad) or dw (wgrad); B, H, W, Cin, Cout, kh, kw, stride or
+ *                  dil <= 0; pad < 0;
+ *   UPR_ERR_SHAPE  Ho != (H + 2 pad - dil (kh - 1) - 1) / stride + 1, the same
+ *                  for Wo, or a window larger than the padded image.
+ * bias and dbias may be NULL.  Each entry picks a kernel by shape, strides and
+ * pointer alignment (csrc/train_small.hip, else the generic kernels of
+ * csrc/train_conv.hip, which take every shape); the result does not depend on
+ * the choice beyond fp32 summation order.
+ *
+ * nn.Conv2d.forward for any channel count (model.py:29-62 small convs:
  * input/scale 3->32, output_layer 32->3, residual_head.2 32->1, channel /
- * spatial attention; VGG conv1_1 of loss.py:198-211): direct FMA kernel,
- * weights in PyTorch layout [Cout][Cin][kh][kw]. */
+ * spatial attention; VGG conv1_1 of loss.py:198-211), weights in PyTorch
+ * layout [Cout][Cin][kh][kw]: y = conv(x) + bias (+ y when accumulate), then
+ * ReLU when relu.  3 -> 32 / 64 3x3 stride 1 into a channel-contiguous,
+ * 16-byte aligned y runs on fp32 MFMA; Cout <= 4 with at most 48 KiB of
+ * weights one thread a pixel (1x1 over 16 / 32 / 64 aligned channels: a wave
+ * per 64 pixels); everything else a direct FMA kernel, one thread an output. */
 int upr_t_conv_direct(const UprView* x, int B, int H, int W, int Cin, const float* w, const float* bias, int Cout,
                       int kh, int kw, int stride, int pad, int dil, const UprView* y, int Ho, int Wo, int relu,
                       int accumulate, void* stream);
 /* The same forward also writing y16 = (half)y compact [B*Ho*Wo][Cout] (the
- * next autocast conv's operand): the 3 -> 32 / 64 3x3 kernel only, else
- * UPR_ERR_UNSUPPORTED (nothing launched).  skip32: y is not written (an
- * activation whose readers all take y16; accumulate must be 0). */
+ * next autocast conv's operand; 8-byte aligned): the 3 -> 32 / 64 3x3 MFMA
+ * kernel only, else (another shape, Cout <= 4, a y that is not
+ * channel-contiguous and 16-byte aligned, a misaligned y16)
+ * UPR_ERR_UNSUPPORTED, nothing launched.  skip32: y is not written (an
+ * activation whose readers all take y16).  A NULL y16, or skip32 with
+ * accumulate: UPR_ERR_ARG. */
 int upr_t_conv_direct16(const UprView* x, int B, int H, int W, int Cin, const float* w, const float* bias, int Cout,
                         int kh, int kw, int stride, int pad, int dil, const UprView* y, int Ho, int Wo, int relu,
                         int accumulate, void* y16, int skip32, void* stream);
@@ -59,19 +80,30 @@ int upr_t_conv_direct16(const UprView* x, int B, int H, int W, int Cin, const fl
  * accumulation on MFMA.  dx [B][H][W][3] view (+= when accumulate). */
 int upr_t_conv_dgrad_c3_16(const void* dy16, int B, int H, int W, const float* w, int Cout, const UprView* dx,
                            int accumulate, void* stream);
-/* d(loss)/d(input) of the same conv (autograd of F.conv2d). */
+/* d(loss)/d(input) of the same conv (autograd of F.conv2d): dx [B][H][W][Cin]
+ * view, overwritten or += when accumulate; dy [B][Ho][Wo][Cout].  Stride 1
+ * with Cin 1 / 2 / 3 / 32 and at most 64 KiB of weights: one thread an input
+ * pixel; else one thread an element. */
 int upr_t_conv_direct_dgrad(const UprView* dy, int Ho, int Wo, const float* w, int B, int H, int W, int Cin, int Cout,
                             int kh, int kw, int stride, int pad, int dil, const UprView* dx, int accumulate,
                             void* stream);
-/* d(loss)/d(weight) [Cout][Cin][kh][kw] and d(loss)/d(bias) [Cout] (nullable),
- * both ACCUMULATED (fp32 atomics). */
+/* d(loss)/d(weight) [Cout][Cin][kh][kw] and d(loss)/d(bias) [Cout] (nullable:
+ * then no bias gradient is formed), both ACCUMULATED (+=).  Every form writes
+ * one partial row a block and a second kernel adds the rows in block order:
+ * no atomics, the same bits run to run.  Cout <= 32 with Cin kh kw (+ 1 with
+ * dbias) <= 128 columns runs on fp32 MFMA, the 7x7 2 -> 1 pad-3 conv with
+ * dbias and the 1x1 32 -> 1 / 3 conv over aligned x on kernels of their own;
+ * else the generic kernel, at most 4096 entries (Cout Cin kh kw, + Cout with
+ * dbias); more entries: UPR_ERR_UNSUPPORTED, nothing written. */
 int upr_t_conv_direct_wgrad(const UprView* x, const UprView* dy, int B, int H, int W, int Cin, int Ho, int Wo,
                             int Cout, int kh, int kw, int stride, int pad, int dil, float* dw, float* dbias,
                             void* stream);
 /* The same with dy masked by y > 0 on the fly (y: the producing ReLU's output,
  * dy's shape) -- a ReLU backward whose masked gradient only this weight
- * gradient reads (the first conv of a stem, its input the image).  Cout <= 32
- * on the generic small-channel kernel, else UPR_ERR_UNSUPPORTED. */
+ * gradient reads (the first conv of a stem, its input the image).  y > 0 is
+ * false for 0, -0 and NaN.  Cout <= 32 and at most 128 columns (the MFMA
+ * small-channel kernel), else UPR_ERR_UNSUPPORTED, nothing written; a NULL y
+ * or y data: UPR_ERR_ARG. */
 int upr_t_conv_direct_wgrad_relu(const UprView* x, const UprView* dy, const UprView* y, int B, int H, int W, int Cin,
                                  int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil, float* dw,
                                  float* dbias, void* stream);

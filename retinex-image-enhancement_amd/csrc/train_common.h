@@ -134,6 +134,9 @@ int small_conv_dgrad_c3_16(const void* dy16, int B, int H, int W, const float* w
 int small_conv_wgrad(const UprView* xv, const UprView* dyv, int B, int H, int W, int Cin, int Ho, int Wo, int Cout,
                      int kh, int kw, int stride, int pad, int dil, float* dw, float* dbias, hipStream_t st,
                      const UprView* ymask = nullptr);
+// dw[co][k] (k < KC) and dbias[co] (k == KC; skipped when NULL) += the sum over blocks of part[block][co][KC + 1],
+// in block order (small_wgrad_fin_kernel)
+int small_wgrad_finish(const float* part, int blocks, int Cout, int KC, float* dw, float* dbias, hipStream_t st);
 // train_wgrad.hip: split-K GEMM weight gradient (train_conv.hip's conv_wgrad_kernel takes the shapes it does not)
 int wgrad_gemm(const float* x, int B, int H, int W, int Cin, int x_cs, int x_coff, const float* dy, int Ho, int Wo,
                int Cout, int dy_cs, int dy_coff, int kh, int kw, int stride, int pad, int dil, float* dwp,

@@ -117,12 +117,17 @@ __global__ __launch_bounds__(256) void conv_direct_dgrad_kernel(V dy, int Ho, in
 
 // Weight gradient of a small conv: a chunk of CH output pixels is staged in
 // LDS as dy[CH][Cout] and its im2col rows col[CH][taps*Cin]; each thread owns
-// weight entries (co, ci, tap) (+ a bias entry) and sums over the chunk.
-// Blocks loop over chunks (grid-stride) and issue their atomics once.
+// weight entries (co, ci, tap) (+ a bias entry), sums each over the chunk and
+// adds the chunk's sum to its running sum.  Blocks loop over chunks
+// (grid-stride) and write one partial row each, part[block][co][KC + 1] in
+// PyTorch's (ci, ky, kx) order with the bias entry last, which
+// small_wgrad_finish adds in block order.  (One fp32 atomic a block and entry
+// made up to 1024 additions in arrival order at the full magnitude of the
+// sum: 7 ulp on the bias of a 260 x 260 image.)
 __global__ __launch_bounds__(256) void conv_direct_wgrad_kernel(V x, V dy, int B, int H, int W, int Cin, int Ho,
                                                                 int Wo, int Cout, int kh, int kw, int s, int p,
-                                                                int d, int CH, float* __restrict__ dw,
-                                                                float* __restrict__ dbias) {
+                                                                int d, int CH, int with_bias,
+                                                                float* __restrict__ part) {
   extern __shared__ float sm[];
   const int taps = kh * kw;
   const int KC = taps * Cin;
@@ -130,7 +135,7 @@ __global__ __launch_bounds__(256) void conv_direct_wgrad_kernel(V x, V dy, int B
   float* scol = sm + CH * Cout;  // [CH][KC]
   const long long P = (long long)B * Ho * Wo;
   const int nW = Cout * KC;
-  const int nE = nW + (dbias ? Cout : 0);
+  const int nE = nW + (with_bias ? Cout : 0);
   constexpr int MAXE = 16;
   float acc[MAXE];
 #pragma unroll
@@ -169,7 +174,7 @@ __global__ __launch_bounds__(256) void conv_direct_wgrad_kernel(V x, V dy, int B
     for (int k = 0; k < MAXE; ++k) {
       const int e = threadIdx.x + k * 256;
       if (e >= nE) break;
-      float a = acc[k];
+      float a = 0.f;
       if (e < nW) {
         const int co = e / KC, kk = e - co * KC;
         for (int pp = 0; pp < CH; ++pp) a = fmaf(sdy[pp * Cout + co], scol[pp * KC + kk], a);
@@ -177,9 +182,10 @@ __global__ __launch_bounds__(256) void conv_direct_wgrad_kernel(V x, V dy, int B
         const int co = e - nW;
         for (int pp = 0; pp < CH; ++pp) a += sdy[pp * Cout + co];
       }
-      acc[k] = a;
+      acc[k] += a;
     }
   }
+  float* row = part + (size_t)blockIdx.x * Cout * (KC + 1);
 #pragma unroll
   for (int k = 0; k < MAXE; ++k) {
     const int e = threadIdx.x + k * 256;
@@ -188,9 +194,9 @@ __global__ __launch_bounds__(256) void conv_direct_wgrad_kernel(V x, V dy, int B
       // e = co*KC + tap*Cin + ci -> PyTorch [co][ci][ky][kx]
       const int co = e / KC, kk = e - co * KC;
       const int tap = kk / Cin, ci = kk - tap * Cin;
-      atomicAdd(dw + ((size_t)co * Cin + ci) * taps + tap, acc[k]);
+      row[(size_t)co * (KC + 1) + ci * taps + tap] = acc[k];
     } else {
-      atomicAdd(dbias + (e - nW), acc[k]);
+      row[(size_t)(e - nW) * (KC + 1) + KC] = acc[k];
     }
   }
 }
@@ -452,15 +458,26 @@ __global__ __launch_bounds__(256) void cast_f16_kernel(const float* __restrict__
 
 using namespace upr;
 
+// The argument checks of the four direct-conv entries (upr_t_conv_direct /
+// _direct16 / _direct_dgrad / _direct_wgrad / _direct_wgrad_relu): a and b are
+// the call's two activation views, p its weight (or weight-gradient) pointer
+static int direct_conv_args(const UprView* a, const UprView* b, const void* p, int B, int H, int W, int Cin, int Cout,
+                            int kh, int kw, int stride, int pad, int dil, int Ho, int Wo) {
+  if (!a || !b || !a->data || !b->data || !p) return UPR_ERR_ARG;
+  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 || dil <= 0)
+    return UPR_ERR_ARG;
+  const long long eh = (long long)H + 2ll * pad - (long long)dil * (kh - 1) - 1;
+  const long long ew = (long long)W + 2ll * pad - (long long)dil * (kw - 1) - 1;
+  if (eh < 0 || ew < 0 || Ho != eh / stride + 1 || Wo != ew / stride + 1) return UPR_ERR_SHAPE;
+  return UPR_OK;
+}
+
 extern "C" {
 
 int upr_t_conv_direct(const UprView* x, int B, int H, int W, int Cin, const float* w, const float* bias, int Cout,
                       int kh, int kw, int stride, int pad, int dil, const UprView* y, int Ho, int Wo, int relu,
                       int accumulate, void* stream) {
-  if (!x || !y || !x->data || !y->data || !w || B <= 0 || Cin <= 0 || Cout <= 0 || stride <= 0 || dil <= 0)
-    return UPR_ERR_ARG;
-  if (Ho != (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1 || Wo != (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1)
-    return UPR_ERR_SHAPE;
+  if (const int bad = direct_conv_args(x, y, w, B, H, W, Cin, Cout, kh, kw, stride, pad, dil, Ho, Wo)) return bad;
   {
     const int rc = small_conv_fwd(x, B, H, W, Cin, w, bias, Cout, kh, kw, stride, pad, dil, y, Ho, Wo, relu,
                                   accumulate, ST(stream));
@@ -487,11 +504,8 @@ int upr_t_conv_dgrad_c3_16(const void* dy16, int B, int H, int W, const float* w
 int upr_t_conv_direct16(const UprView* x, int B, int H, int W, int Cin, const float* w, const float* bias, int Cout,
                         int kh, int kw, int stride, int pad, int dil, const UprView* y, int Ho, int Wo, int relu,
                         int accumulate, void* y16, int skip32, void* stream) {
-  if (!x || !y || !x->data || !y->data || !w || !y16 || B <= 0 || Cin <= 0 || Cout <= 0 || stride <= 0 || dil <= 0)
-    return UPR_ERR_ARG;
-  if (Ho != (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1 || Wo != (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1)
-    return UPR_ERR_SHAPE;
-  if (skip32 && accumulate) return UPR_ERR_ARG;
+  if (!y16 || (skip32 && accumulate)) return UPR_ERR_ARG;
+  if (const int bad = direct_conv_args(x, y, w, B, H, W, Cin, Cout, kh, kw, stride, pad, dil, Ho, Wo)) return bad;
   const int rc = small_conv_fwd(x, B, H, W, Cin, w, bias, Cout, kh, kw, stride, pad, dil, y, Ho, Wo, relu, accumulate,
                                 ST(stream), y16, skip32);
   return rc == kErrUnsupported ? UPR_ERR_UNSUPPORTED : rc;
@@ -500,7 +514,7 @@ int upr_t_conv_direct16(const UprView* x, int B, int H, int W, int Cin, const fl
 int upr_t_conv_direct_dgrad(const UprView* dy, int Ho, int Wo, const float* w, int B, int H, int W, int Cin, int Cout,
                             int kh, int kw, int stride, int pad, int dil, const UprView* dx, int accumulate,
                             void* stream) {
-  if (!dy || !dx || !dy->data || !dx->data || !w || B <= 0 || stride <= 0 || dil <= 0) return UPR_ERR_ARG;
+  if (const int bad = direct_conv_args(dy, dx, w, B, H, W, Cin, Cout, kh, kw, stride, pad, dil, Ho, Wo)) return bad;
   {
     const int rc = small_conv_dgrad(dy, Ho, Wo, w, B, H, W, Cin, Cout, kh, kw, stride, pad, dil, dx, accumulate,
                                     ST(stream));
@@ -522,7 +536,8 @@ int upr_t_conv_stem_wgrad_relu16(const UprView* x, const float* dy, const void* 
 int upr_t_conv_direct_wgrad_relu(const UprView* x, const UprView* dy, const UprView* y, int B, int H, int W, int Cin,
                                  int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil, float* dw,
                                  float* dbias, void* stream) {
-  if (!x || !dy || !y || !dw || B <= 0) return UPR_ERR_ARG;
+  if (!y || !y->data) return UPR_ERR_ARG;
+  if (const int bad = direct_conv_args(x, dy, dw, B, H, W, Cin, Cout, kh, kw, stride, pad, dil, Ho, Wo)) return bad;
   const int rc = small_conv_wgrad(x, dy, B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil, dw, dbias, ST(stream),
                                   y);
   return rc == kErrUnsupported ? UPR_ERR_UNSUPPORTED : rc;
@@ -531,7 +546,7 @@ int upr_t_conv_direct_wgrad_relu(const UprView* x, const UprView* dy, const UprV
 int upr_t_conv_direct_wgrad(const UprView* x, const UprView* dy, int B, int H, int W, int Cin, int Ho, int Wo,
                             int Cout, int kh, int kw, int stride, int pad, int dil, float* dw, float* dbias,
                             void* stream) {
-  if (!x || !dy || !dw || B <= 0) return UPR_ERR_ARG;
+  if (const int bad = direct_conv_args(x, dy, dw, B, H, W, Cin, Cout, kh, kw, stride, pad, dil, Ho, Wo)) return bad;
   {
     const int rc = small_conv_wgrad(x, dy, B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil, dw, dbias, ST(stream));
     if (rc != kErrUnsupported) return rc;
@@ -545,9 +560,11 @@ int upr_t_conv_direct_wgrad(const UprView* x, const UprView* dy, int B, int H, i
   const long long P = (long long)B * Ho * Wo;
   const int grid = grid_for(P, CH, 1024);
   const size_t lds = sizeof(float) * CH * (Cout + KC);
+  float* part = (float*)scratch(kSlotPart, sizeof(float) * (size_t)grid * Cout * (KC + 1), ST(stream));
+  if (!part) return (int)hipErrorOutOfMemory;
   hipLaunchKernelGGL(conv_direct_wgrad_kernel, dim3(grid), dim3(256), lds, ST(stream), mkv(x), mkv(dy), B, H, W, Cin,
-                     Ho, Wo, Cout, kh, kw, stride, pad, dil, CH, dw, dbias);
-  LAUNCH_CHECK();
+                     Ho, Wo, Cout, kh, kw, stride, pad, dil, CH, dbias != nullptr, part);
+  return small_wgrad_finish(part, grid, Cout, KC, dw, dbias, ST(stream));
 }
 
 int upr_t_conv_mfma(const float* x, int B, int H, int W, int Cin, int x_cs, int x_coff, const float* wp,

@@ -147,9 +147,15 @@ __global__ __launch_bounds__(256) void small_fwd_kernel(V x, int B, int H, int W
   const int ox = pix % Wo;
   const int r = pix / Wo;
   const int oy = r % Ho, b = r / Ho;
-  float acc[COUT];
+  // four partial sums an output, by position in the channel quad: a quarter of
+  // the (tap, ci) chain each (one chain of 98 terms for the 7x7 2 -> 1 conv, 64
+  // for a 64-channel head, lost 2-3 ulp), and the 16-byte and the scalar loads
+  // add in the same order
+  float acc[4][COUT];
 #pragma unroll
-  for (int c = 0; c < COUT; ++c) acc[c] = bias ? bias[c] : 0.f;
+  for (int e = 0; e < 4; ++e)
+#pragma unroll
+    for (int c = 0; c < COUT; ++c) acc[e][c] = 0.f;
   for (int ky = 0; ky < kh; ++ky) {
     const int iy = oy * s - p + ky * d;
     if (iy < 0 || iy >= H) continue;
@@ -159,26 +165,28 @@ __global__ __launch_bounds__(256) void small_fwd_kernel(V x, int B, int H, int W
       const float* xp = x.d + x.at(b, iy, ix, 0);
       const float* wt = smf + (ky * kw + kx) * Cin * COUT;
       int ci = 0;
-      if (xvec) {
-        for (; ci + 4 <= Cin; ci += 4) {
-          const f32x4 v = *(const f32x4*)(xp + ci);
+      for (; ci + 4 <= Cin; ci += 4) {
+        f32x4 v;
+        if (xvec) v = *(const f32x4*)(xp + ci);
+        else v = f32x4{xp[ci * x.sc], xp[(ci + 1) * x.sc], xp[(ci + 2) * x.sc], xp[(ci + 3) * x.sc]};
 #pragma unroll
-          for (int e = 0; e < 4; ++e)
+        for (int e = 0; e < 4; ++e)
 #pragma unroll
-            for (int c = 0; c < COUT; ++c) acc[c] = fmaf(v[e], wt[(ci + e) * COUT + c], acc[c]);
-        }
+          for (int c = 0; c < COUT; ++c) acc[e][c] = fmaf(v[e], wt[(ci + e) * COUT + c], acc[e][c]);
       }
-      for (; ci < Cin; ++ci) {
-        const float v = xp[ci * x.sc];
 #pragma unroll
-        for (int c = 0; c < COUT; ++c) acc[c] = fmaf(v, wt[ci * COUT + c], acc[c]);
+      for (int e = 0; e < 3; ++e) {  // the last Cin % 4 channels
+        if (ci + e >= Cin) break;
+        const float v = xp[(ci + e) * x.sc];
+#pragma unroll
+        for (int c = 0; c < COUT; ++c) acc[e][c] = fmaf(v, wt[(ci + e) * COUT + c], acc[e][c]);
       }
     }
   }
   float* yp = y.d + y.at(b, oy, ox, 0);
 #pragma unroll
   for (int c = 0; c < COUT; ++c) {
-    float v = acc[c];
+    float v = ((acc[0][c] + acc[1][c]) + (acc[2][c] + acc[3][c])) + (bias ? bias[c] : 0.f);
     if (accum) v += yp[c * y.sc];
     if (relu) v = fmaxf(v, 0.f);
     yp[c * y.sc] = v;
@@ -266,9 +274,18 @@ __global__ __launch_bounds__(256) void small_dgrad_kernel(V dy, int Ho, int Wo, 
   const int ix = pix % W;
   const int r = pix / W;
   const int iy = r % H, b = r / H;
-  float acc[CIN];
+  // CIN <= 3: four partial sums an input channel, by position in the output
+  // channel quad -- a quarter of the (tap, co) chain each; two (even / odd
+  // channels) in the compile-time Cout form, whose registers four would take
+  // past 96, a wave a SIMD fewer and 30 % of its speed (one chain of 576 terms
+  // at 3x3, Cout 64 lost 8 ulp).  The 16-byte and the scalar dy loads add in
+  // the same order.  CIN 32 keeps one sum (Cout is small there).
+  constexpr int NA = CIN > 3 ? 1 : (COUTT > 0 ? 2 : 4);
+  float acc[NA][CIN];
 #pragma unroll
-  for (int c = 0; c < CIN; ++c) acc[c] = 0.f;
+  for (int a = 0; a < NA; ++a)
+#pragma unroll
+    for (int c = 0; c < CIN; ++c) acc[a][c] = 0.f;
   for (int ky = 0; ky < kh; ++ky) {
     const int oy = iy + p - ky * d;
     if (oy < 0 || oy >= Ho) continue;
@@ -287,39 +304,50 @@ __global__ __launch_bounds__(256) void small_dgrad_kernel(V dy, int Ho, int Wo, 
 #pragma unroll
           for (int e = 0; e < 4; ++e)
 #pragma unroll
-            for (int c = 0; c < CIN; ++c) acc[c] = fmaf(g4[q][e], wt[(4 * q + e) * CIN + c], acc[c]);
+            for (int c = 0; c < CIN; ++c)
+              acc[e % NA][c] = fmaf(g4[q][e], wt[(4 * q + e) * CIN + c], acc[e % NA][c]);
         co = COUTT;
       }
-      if (dvec) {  // channel-contiguous, 16-byte aligned dy rows: 4 channels per load
-        for (; co + 4 <= Cout; co += 4) {
-          const f32x4 g4 = *(const f32x4*)(dyp + co);
-          const float* wc = wt + co * CIN;
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int c = 0; c < CIN; ++c) acc[c] = fmaf(g4[q], wc[q * CIN + c], acc[c]);
-        }
-      }
-      for (; co < Cout; ++co) {
-        const float g = dyp[co * dy.sc];
+      // 4 channels a pass: one 16-byte load on channel-contiguous, 16-byte aligned dy rows (dvec)
+      for (; co + 4 <= Cout; co += 4) {
+        f32x4 g4;
+        if (dvec) g4 = *(const f32x4*)(dyp + co);
+        else g4 = f32x4{dyp[co * dy.sc], dyp[(co + 1) * dy.sc], dyp[(co + 2) * dy.sc], dyp[(co + 3) * dy.sc]};
         const float* wc = wt + co * CIN;
 #pragma unroll
-        for (int c = 0; c < CIN; ++c) acc[c] = fmaf(g, wc[c], acc[c]);
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int c = 0; c < CIN; ++c) acc[q % NA][c] = fmaf(g4[q], wc[q * CIN + c], acc[q % NA][c]);
+      }
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {  // the last Cout % 4 channels
+        if (co + q >= Cout) break;
+        const float g = dyp[(co + q) * dy.sc];
+        const float* wc = wt + (co + q) * CIN;
+#pragma unroll
+        for (int c = 0; c < CIN; ++c) acc[q % NA][c] = fmaf(g, wc[c], acc[q % NA][c]);
       }
     }
+  }
+  float sum[CIN];
+#pragma unroll
+  for (int c = 0; c < CIN; ++c) {
+    if constexpr (NA == 4) sum[c] = (acc[0][c] + acc[1][c]) + (acc[2][c] + acc[3][c]);
+    else if constexpr (NA == 2) sum[c] = acc[0][c] + acc[1][c];
+    else sum[c] = acc[0][c];
   }
   float* xp = dx.d + dx.at(b, iy, ix, 0);
   if (CIN % 4 == 0 && vec) {  // channel-contiguous, 16-byte aligned rows (host-checked)
 #pragma unroll
     for (int c = 0; c < CIN; c += 4) {
-      f32x4 v = f32x4{acc[c], acc[c + 1], acc[c + 2], acc[c + 3]};
+      f32x4 v = f32x4{sum[c], sum[c + 1], sum[c + 2], sum[c + 3]};
       if (accum) v += *(const f32x4*)(xp + c);
       *(f32x4*)(xp + c) = v;
     }
   } else {
 #pragma unroll
     for (int c = 0; c < CIN; ++c) {
-      float v = acc[c];
+      float v = sum[c];
       if (accum) v += xp[c * dx.sc];
       xp[c * dx.sc] = v;
     }
@@ -363,11 +391,19 @@ __global__ __launch_bounds__(256) void small_wgrad_mfma_kernel(V x, V dy, int B,
       c_kind[t] = 2;
     }
   }
-  f32x16 acc[NT];
+  // an MFMA adds its two products to the accumulator one after the other, so
+  // an accumulator is a chain of 2 * pairs_per_wave additions.  Two tiles run
+  // 16 pairs a batch where the other counts run 8: there the pairs alternate
+  // between two accumulators a tile, added at the end (a chain of 32 lost 37
+  // ulp of a cancelling 255-pixel bias sum where plain fp32 torch lost 5)
+  constexpr int NA = NT == 2 ? 2 : 1;
+  f32x16 acc[NA][NT];
 #pragma unroll
-  for (int t = 0; t < NT; ++t)
+  for (int a = 0; a < NA; ++a)
 #pragma unroll
-    for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[a][t][e] = 0.f;
   // 32-bit pixel math (P < 2^31, host-checked): the 64-bit div / mod per
   // pixel dominated these kernels
   const int gw = blockIdx.x * 4 + wave;
@@ -403,7 +439,12 @@ __global__ __launch_bounds__(256) void small_wgrad_mfma_kernel(V x, V dy, int B,
 #pragma unroll
     for (int u = 0; u < SW_UNROLL; ++u)
 #pragma unroll
-      for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u][t], acc[t], 0, 0, 0);
+      for (int t = 0; t < NT; ++t)
+        acc[u % NA][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u][t], acc[u % NA][t], 0, 0, 0);
+  }
+  if constexpr (NA == 2) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[0][t] += acc[1][t];
   }
   // block reduction over the 4 waves into this block's partial row
   // part[block][co * (KC + 1) + k] (k == KC: the bias column); summed over the
@@ -412,7 +453,7 @@ __global__ __launch_bounds__(256) void small_wgrad_mfma_kernel(V x, V dy, int B,
 #pragma unroll
   for (int t = 0; t < NT; ++t)
 #pragma unroll
-    for (int e = 0; e < 16; ++e) red[wave][t][e][lane] = acc[t][e];
+    for (int e = 0; e < 16; ++e) red[wave][t][e][lane] = acc[0][t][e];
   __syncthreads();
   for (int idx = tid; idx < NT * 16 * 64; idx += 256) {
     const int t = idx / (16 * 64);
@@ -450,6 +491,11 @@ __global__ __launch_bounds__(256) void small_wgrad_fin_kernel(const float* __res
     if (k < KC) dw[(size_t)co * KC + k] += red[0];
     else dbias[co] += red[0];
   }
+}
+
+int small_wgrad_finish(const float* part, int blocks, int Cout, int KC, float* dw, float* dbias, hipStream_t st) {
+  hipLaunchKernelGGL(small_wgrad_fin_kernel, dim3(Cout * (KC + 1)), dim3(256), 0, st, part, blocks, Cout, KC, dw, dbias);
+  return (int)hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------
@@ -680,6 +726,7 @@ int small_conv_dgrad(const UprView* dyv, int Ho, int Wo, const float* w, int B, 
 // (part[block][99]), summed in block order by small_wgrad_fin_kernel.
 // ---------------------------------------------------------------------------
 constexpr int SA_TR = 8, SA_TC = 64, SA_K = 7, SA_P = 3;
+static_assert(SA_TR == 8 && SA_TC % 8 == 0, "sa_wgrad_kernel adds 4 rows a thread, 8 columns a pass");
 
 __global__ __launch_bounds__(256) void sa_wgrad_kernel(V x, V dy, int B, int H, int W, int tiles_x, int tiles_y,
                                                        float* __restrict__ part) {
@@ -712,17 +759,36 @@ __global__ __launch_bounds__(256) void sa_wgrad_kernel(V x, V dy, int B, int H, 
   if (t < 198) {
     e = t % 99;
     const int r0 = (t / 99) * (SA_TR / 2);
+    // a row in 8 interleaved partial sums of 8 terms, added as a tree, then
+    // the 4 row sums as a tree (one chain of the 256 terms lost 15 ulp on the
+    // bias of a 16 x 128 image where a pairwise sum loses under one)
+    float rs[SA_TR / 2];
     if (e < 98) {
       const int ci = e / 49, tap = e - ci * 49, ky = tap / 7, kx = tap - ky * 7;
-      for (int r = r0; r < r0 + SA_TR / 2; ++r) {
-#pragma unroll 8
-        for (int c = 0; c < SA_TC; ++c) a = fmaf(ds[r][c], xs[ci][r + ky][c + kx], a);
+#pragma unroll
+      for (int rr = 0; rr < SA_TR / 2; ++rr) {
+        const float* dr = ds[r0 + rr];
+        const float* xr = &xs[ci][r0 + rr + ky][kx];
+        float a8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+        for (int c = 0; c < SA_TC; c += 8)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) a8[j] = fmaf(dr[c + j], xr[c + j], a8[j]);
+        rs[rr] = ((a8[0] + a8[1]) + (a8[2] + a8[3])) + ((a8[4] + a8[5]) + (a8[6] + a8[7]));
       }
     } else {
-      for (int r = r0; r < r0 + SA_TR / 2; ++r)
-#pragma unroll 8
-        for (int c = 0; c < SA_TC; ++c) a += ds[r][c];
+#pragma unroll
+      for (int rr = 0; rr < SA_TR / 2; ++rr) {
+        const float* dr = ds[r0 + rr];
+        float a8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+        for (int c = 0; c < SA_TC; c += 8)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) a8[j] += dr[c + j];
+        rs[rr] = ((a8[0] + a8[1]) + (a8[2] + a8[3])) + ((a8[4] + a8[5]) + (a8[6] + a8[7]));
+      }
     }
+    a = (rs[0] + rs[1]) + (rs[2] + rs[3]);
   }
   // the two halves in a fixed order: rows 0-3 first, then rows 4-7
   if (t < 99) red[t] = a;
