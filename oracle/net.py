@@ -50,7 +50,7 @@ def _r16(t):
 
 def amp_conv(fn, x, w, b, cin, cout, **kw):
     """MODE["amp"]: the product's autocast arithmetic for MFMA-shaped convs
-    (Cin, Cout multiples of 32; upr/train.py Conv / ConvT with autocast on):
+    (Cin, Cout multiples of 32; upr/train/ Conv / ConvT with autocast on):
     fp16 operands, wide accumulation, bias in fp32, fp16-rounded output.
     Otherwise a plain conv."""
     if MODE["amp"] and cin % 32 == 0 and cout % 32 == 0:

@@ -1,7 +1,7 @@
 """Functional torch-CPU fp32 restatement of the UP-Retinex training step.
 
 TEST INFRASTRUCTURE ONLY (see oracle/__init__.py): the checker for the HIP
-training path (upr/train.py + csrc/train_*.hip), never imported by the product.
+training path (upr/train/ + csrc/train_*.hip), never imported by the product.
 
 Restates (paths relative to the reference root):
   * losses/loss.py:12-753   the 7 loss terms + calculate_texture_complexity +

@@ -7,7 +7,7 @@ values) and checkpoints load unchanged.  Execution is not PyTorch's: on a ROCm
 device `MultiScaleUP_Retinex.forward` / `ResidualIENet.forward` run the fused
 gfx950 kernel graph of libupr.so (BatchNorm folded, implicit-GEMM MFMA convs,
 fused FAM attention and Retinex tail).  In training mode the forward runs the
-HIP training engine (upr/train.py: batch-statistics BatchNorm, Dropout, an
+HIP training engine (upr/train/: batch-statistics BatchNorm, Dropout, an
 explicit backward reached through `loss.backward()`).  The submodules
 (EnhancedFAM, ResBlock, PreActResBlock, ASPPModule, UpBlock) called on their own
 run on the per-module HIP layer objects (upr/modules.py), in eval or training

@@ -13,7 +13,7 @@ skipped on inf/nan, scale update — upr.amp.GradScaler (a torch.amp.GradScaler
 handed in is mirrored by one with its settings).  As in the reference, the
 forward and the loss of that branch run under torch.autocast: the engine then
 computes its MFMA convolutions (and their input gradients) in fp16 with fp32
-accumulation (upr/train.py, autocast_active); weight gradients, BatchNorm, the
+accumulation (upr/train/, autocast_active); weight gradients, BatchNorm, the
 losses and the optimiser stay fp32.  `amp_fp16=False` keeps the GradScaler
 control flow with fp32 arithmetic.
 """

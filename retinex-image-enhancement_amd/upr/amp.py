@@ -23,7 +23,7 @@ scale schedule) at fp32 arithmetic.
 import torch
 
 from . import _lib as L
-from .train import _chk, _p, _stream, zero
+from ._dev import _chk, _p, _stream, zero
 
 
 def next_scale(scale, tracker, found_inf, growth_factor, backoff_factor, growth_interval):

@@ -3,7 +3,7 @@
 `loss.backward()` -> clip -> `optimizer.step()`).
 
 Autograd nodes, each a whole subgraph whose forward and backward are the
-HIP engines of upr/train.py and upr/loss_engine.py:
+HIP engines of upr/train/ and upr/loss_engine.py:
   _ModelStep  MultiScaleUP_Retinex training forward; backward = the explicit
               network backward, accumulating every parameter's gradient into
               the flat gradient buffer (the .grad views);
@@ -18,7 +18,8 @@ import ctypes
 import torch
 
 from . import _lib as L
-from .train import FlatParams, UPRetinexTrainGraph, _chk, _p, _stream, zero
+from ._dev import _chk, _p, _stream, zero
+from .train import FlatParams, UPRetinexTrainGraph
 
 _weights_epoch = [0]
 
@@ -128,7 +129,7 @@ def head_train_forward(model, x, refl):
 
 class _IENetStep(torch.autograd.Function):
     """ResidualIENet.forward (models/model.py:333-360) in training mode on its
-    own: forward = the IENet layer objects of upr/train.py, backward = their
+    own: forward = the IENet layer objects of upr/train/, backward = their
     explicit backward from dL/d(illumination) (sigmoid backward on the device,
     then the residual head and the network); parameter gradients accumulate
     into the .grad views.  No gradient w.r.t. the network input (as the full

@@ -21,8 +21,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .train import (Act, Conv, _chk, _fp, _h16, _p, _stream, autocast_active, empty, maxpool_into, pack_convs,
-                    relu_mask, set_amp, zero)
+from ._dev import _chk, _fp, _h16, _p, _stream, empty, took, zero
+from .train import Act, Conv, autocast_active, maxpool_into, pack_convs, relu_mask, set_amp
 
 WEIGHTS = dict(exposure=10.0, smoothness=1.0, color=0.5, spatial=1.0, decouple=0.1, perceptual=1.0,
                frequency=0.5)
@@ -120,18 +120,16 @@ class VGGPerceptual:
                 # the next conv's ReLU mask and fp16 operand fused into the gather when
                 # that frozen conv reads the masked gradient in fp16 only (relu_mask's only16)
                 nxt = entries[j + 1] if j + 1 < len(entries) else None
-                if nxt is not None and nxt[0] == "conv" and inp.t16 is not None and inp.coff == 0 \
-                        and inp.cs == inp.C:
+                inp16 = inp.compact16()
+                if nxt is not None and nxt[0] == "conv" and inp16 is not None:
                     cn = self.convs[nxt[1]]
                     if cn.frozen and ((cn.amp and cn.mfma) or cn.dgrad16_c3):
                         g16 = _h16(gi.M * gi.C, gi.t.device)
                         rc = lib.upr_t_maxpool_bwd_code16(_p(i), ctypes.byref(g_src.view()), inp.B, inp.H, inp.W,
-                                                          inp.C, 2, 2, 0, out.H, out.W, _p(inp.t16), _p(g16), st)
-                        if rc == 0:
-                            gi.t16, gi.t16_grad, gi.stale32 = g16, True, True
+                                                          inp.C, 2, 2, 0, out.H, out.W, _p(inp16), _p(g16), st)
+                        if took(rc, "pool_bwd16"):
+                            gi.attach16(g16, grad=True, only=True)
                             premasked = True
-                        elif rc != L.UPR_ERR_UNSUPPORTED:
-                            _chk(rc, "pool_bwd16")
                 if not premasked:
                     _chk(lib.upr_t_maxpool_bwd_code(_p(i), ctypes.byref(g_src.view()), inp.B, inp.H, inp.W, inp.C, 2,
                                                     2, 0, out.H, out.W, ctypes.byref(gi.view()), 0, st), "pool_bwd")
@@ -145,10 +143,10 @@ class VGGPerceptual:
                 # inp is the previous conv's ReLU output: its mask goes into this dgrad's epilogue
                 nxt = entries[j + 1] if j + 1 < len(entries) else None
                 mask = None
-                if nxt is not None and nxt[0] == "conv" and inp.t16 is not None:
+                if nxt is not None and nxt[0] == "conv" and inp.compact16() is not None:
                     cn = self.convs[nxt[1]]
                     only16 = cn.frozen and ((cn.amp and cn.mfma) or cn.dgrad16_c3)
-                    mask = (inp.t16, inp.C, only16)
+                    mask = (inp.any16(), only16)
                 if c.mfma:
                     premasked = bool(c.bwd(inp, g, gi, mask=mask))
                 else:
@@ -240,8 +238,8 @@ class TotalLossEngine:
         for a, b in zip(fe, fl):
             n = a.t.numel()
             g = Act.new(a.B, a.H, a.W, a.C, dev, fresh=False) if grads else None
-            if a.stale32 or b.stale32:  # fp16-only features (autocast): the MSE reads the fp16 copies
-                rc = lib.upr_t_mse16(_p(a.t16), _p(b.t16), n, _p(acc[1:2]), _fp(g.t) if g else None,
+            if a.only16 or b.only16:  # fp16-only features (autocast): the MSE reads the fp16 copies
+                rc = lib.upr_t_mse16(_p(a.compact16()), _p(b.compact16()), n, _p(acc[1:2]), _fp(g.t) if g else None,
                                      ctypes.c_float(w["perceptual"] / n), st)
             else:
                 rc = lib.upr_t_mse(_fp(a.t), _fp(b.t), n, _p(acc[1:2]), _fp(g.t) if g else None,

@@ -3,7 +3,7 @@
 Reference modules (models/model.py): EnhancedFAM (:11-97), ResBlock (:100-135),
 PreActResBlock (:138-178), ASPPModule (:181-251), UpBlock (:254-274).  Inside
 MultiScaleUP_Retinex they run fused into the inference graph (csrc/model.hip);
-called on their own they run on the per-module layer objects of upr/train.py
+called on their own they run on the per-module layer objects of upr/train/
 (fp32 NHWC activations, MFMA implicit-GEMM convs, BatchNorm kernels):
 
   * eval mode: BatchNorm from the running statistics (`upr_t_bn_eval_stats`),
@@ -32,8 +32,9 @@ import ctypes
 import torch
 
 from . import _lib as L
-from .train import (FAMT, ASPPT, Act, PreActResBlockT, ResBlockT, UpBlockT, _chk, _stream, autocast_active, empty,
-                    nchw_view, set_amp)
+from ._dev import _chk, _stream, empty
+from .train import (FAMT, ASPPT, Act, PreActResBlockT, ResBlockT, UpBlockT, autocast_active, nchw_view, pack_convs,
+                    set_amp)
 
 _LAYERS = {"EnhancedFAM": FAMT, "ResBlock": ResBlockT, "PreActResBlock": PreActResBlockT, "ASPPModule": ASPPT,
            "UpBlock": UpBlockT}
@@ -99,8 +100,7 @@ def _eval_layer(module, cm, dev):
 
 def _run(layer, x, fp16):
     set_amp(fp16 or autocast_active())
-    for c in layer.convs():
-        c.pack()
+    pack_convs(layer.convs(), layer)
     return layer.fwd(_to_nhwc(x))
 
 

@@ -14,7 +14,8 @@ import torch
 
 from . import _lib as L
 from .autograd import bump_weights_epoch
-from .train import FlatParams, _chk, _p, _stream, zero
+from ._dev import _chk, _p, _stream, zero
+from .train import FlatParams
 
 
 def _flat_of(params):

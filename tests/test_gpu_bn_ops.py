@@ -752,7 +752,7 @@ def test_bn_class_res_post_relu_accumulate(amp):
         bn = T.BN(m)
         xa = T.Act(x.view(B, H, W, C).to(DEV))
         if amp:
-            xa.t16 = x.half().to(DEV).view(-1)
+            xa.attach16(x.half().to(DEV).view(-1))
         ra = T.Act(d["res"].view(B, H, W, C).to(DEV))
         ya = bn.fwd(xa, relu=True, res=ra, res_post=True)
         torch.cuda.synchronize()
@@ -779,9 +779,10 @@ def test_bn_class_res_post_relu_accumulate(amp):
         _within_restated(f"BN class dgamma amp={amp}", m.weight.grad, dg64, rs[1])
         _within_restated(f"BN class dbeta amp={amp}", m.bias.grad, db64, rs[2])
         if amp:
-            assert ya.t16 is not None and torch.equal(ya.t16.view(M, C), ya.t.view(M, C).half())
-            assert gx.t16 is not None and gx.t16_grad and torch.equal(gx.t16.view(M, C), gx.t.view(M, C).half())
-            assert not ya.stale32 and not gx.stale32
+            ya16, gx16 = ya.compact16(), gx.compact16(grad=True)  # (the latter: only a copy marked as a gradient's)
+            assert ya16 is not None and torch.equal(ya16.view(M, C), ya.t.view(M, C).half())
+            assert gx16 is not None and torch.equal(gx16.view(M, C), gx.t.view(M, C).half())
+            assert not ya.only16 and not gx.only16
     finally:
         T.set_amp(False)
 

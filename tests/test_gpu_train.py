@@ -1645,7 +1645,7 @@ def test_amp_fp16_only_stores_bitwise():
             torch.cuda.synchronize()
             g = model.__dict__["_upr_train"]["graph"]
             asp = [b for b in g.ie.mid if type(b).__name__ == "ASPPT"][0]
-            stale = (asp.cat.stale32, g.s1f.cat.stale32)
+            stale = (asp.cat.only16, g.s1f.cat.only16)
             grads = {n: p.grad.detach().clone() for n, p in model.named_parameters() if p.grad is not None}
             return float(total), grads, stale
         finally:

@@ -1,25 +1,188 @@
-"""Print the arguments of selected C-ABI calls made during one AMP training
-step (bench.py --train --amp), e.g. to see the BN backward flags per layer.
-usage: python tools/call_flags.py upr_t_bn_bwd_fused16[,name2...]"""
+"""The C-ABI calls a training step makes, and what it computes.
+
+  python tools/call_flags.py NAME[,NAME...]
+      print the arguments and call sites of the named calls during one AMP
+      training step (bench.py --train --amp), e.g. to see the BN backward
+      flags per layer.
+
+  python tools/call_flags.py --trace T.txt --save S.pt [--root DIR] [--step train|head|fam|aspp]
+                             [--variant plain|preact_aspp] [--amp] [--B 2 --H 96 --W 160] [--seed 0] [--steps 2]
+      wrap EVERY entry of upr._lib.SIGNATURES, run the chosen step in this
+      process and write one line per call, in order: the function name and its
+      arguments.  Ints and floats as they are; a pointer as 0 or p<address mod
+      512> (torch's allocations are 512-byte aligned: a channel offset stays
+      visible, where the allocator put the tensor does not); a struct passed by
+      reference (UprView, UprLossParams) as its fields.  --save: the step's loss
+      terms, enh / refl / illu, every parameter gradient before the optimiser,
+      every parameter and buffer after it and the scaler's scale (train); the
+      output, the input gradient and every parameter gradient / buffer (head /
+      fam / aspp: upr/modules.py submodules in train mode, --amp = float16).
+      --root: drive another checkout's package (it still runs the library
+      UPR_LIB names), to compare two trees call by call and bit by bit.
+"""
+import argparse
+import ctypes
 import os
 import runpy
 import sys
 import traceback
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "retinex-image-enhancement_amd"))
-from upr import _lib as L  # noqa: E402
+HERE = os.path.dirname(os.path.abspath(__file__))
 
-names = sys.argv[1].split(",")
-lib = L.lib()
-for n in names:
-    f = getattr(lib, n)
 
-    def wrap(*a, _f=f, _n=n):
-        vals = [getattr(x, "value", x) for x in a]
-        where = " <- ".join(f"{os.path.basename(f.filename)}:{f.lineno}" for f in traceback.extract_stack()[-2:-6:-1])
-        print(_n, [v if isinstance(v, int) and abs(v) < 1 << 20 else ("p" if v else 0) for v in vals], where,
-              flush=True)
-        return _f(*a)
-    setattr(lib, n, wrap)
-sys.argv = ["bench.py", "--train", "--amp", "--steps", "1", "--warmup", "0", "--cpu-seconds", "0"]
-runpy.run_path(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "bench.py"), run_name="__main__")
+def _mark(v):
+    v = getattr(v, "value", v)
+    if not v:
+        return "0"
+    return f"p{v % 512}" if isinstance(v, int) else "p?"
+
+
+def _fmt(a, typ):
+    obj = getattr(a, "_obj", None)  # byref(...)
+    if obj is not None:
+        if not isinstance(obj, ctypes.Structure):
+            return "&"
+        return "{" + ",".join(_fmt(getattr(obj, n), t) for n, t in obj._fields_) + "}"
+    if typ is ctypes.c_void_p or (isinstance(typ, type) and issubclass(typ, ctypes._Pointer)):
+        return _mark(a)
+    v = getattr(a, "value", a)
+    return repr(float(v)) if typ in (ctypes.c_float, ctypes.c_double) else str(v)
+
+
+class _Traced:
+    """Proxy over the ctypes library (installed as upr._lib._lib, so it catches the
+    calls every module makes through L.lib()): one line per call."""
+
+    def __init__(self, lib, sigs, out):
+        self._lib, self._sigs, self._out, self.n = lib, sigs, out, 0
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        sig = self._sigs.get(name)
+        if sig is None:
+            return fn
+
+        def call(*a, _types=sig[1]):
+            self._out.write(name + " " + " ".join(_fmt(x, t) for x, t in zip(a, _types)) + "\n")
+            self.n += 1
+            return fn(*a)
+        setattr(self, name, call)
+        return call
+
+
+def _train(args, torch, dev, saved):
+    from losses.loss import TotalLoss
+    from models.model import UP_Retinex
+    from trainers.train import GradScaler, make_optimizer, train_step
+    pre = args.variant == "preact_aspp"
+    torch.manual_seed(args.seed)
+    model = UP_Retinex(use_preact=pre, use_aspp=pre).to(dev).train()
+    crit = TotalLoss(use_freq_loss=True).to(dev)
+    opt = make_optimizer(model, lr=1e-4, weight_decay=1e-5)
+    scaler = GradScaler() if args.amp else None
+    g = torch.Generator().manual_seed(args.seed + 1)
+    for s in range(args.steps):
+        x = (torch.rand(args.B, 3, args.H, args.W, generator=g) * 0.6).to(dev)
+        hook = model.register_forward_hook(lambda m, i, o, s=s: saved.update(
+            {f"s{s}.{n}": t.detach().clone() for n, t in zip(("enh", "refl", "illu"), o)}))
+
+        def grads(s=s):
+            saved.update({f"s{s}.grad.{n}": p.grad.detach().clone() for n, p in model.named_parameters()
+                          if p.grad is not None})
+        loss, d = train_step(model, x, crit, opt, scaler=scaler, use_amp=args.amp, grad_hook=grads)
+        hook.remove()
+        saved[f"s{s}.loss"] = loss.detach().clone()
+        saved.update({f"s{s}.term.{k}": torch.tensor(float(v), dtype=torch.float64) for k, v in d.items()})
+        saved.update({f"s{s}.param.{n}": p.detach().clone() for n, p in model.named_parameters()})
+        saved.update({f"s{s}.buffer.{n}": b.detach().clone() for n, b in model.named_buffers()})
+        if scaler is not None:
+            saved[f"s{s}.scale"] = torch.tensor(float(scaler.get_scale()), dtype=torch.float64)
+
+
+def _sub(args, torch, dev, saved):
+    from models.model import ASPPModule, EnhancedFAM, UP_Retinex
+    torch.manual_seed(args.seed)
+    g = torch.Generator().manual_seed(args.seed + 1)
+    dt = torch.float16 if args.amp and args.step != "head" else torch.float32
+    if args.step == "head":  # the multi-scale head alone; --amp: under autocast (it takes float32 tensors)
+        model = UP_Retinex(use_preact=False, use_aspp=False).to(dev).train()
+        x = (torch.rand(args.B, 3, args.H, args.W, generator=g) * 0.6).to(dev)
+        inp = torch.rand(args.B, 3, args.H, args.W, generator=g).to(dev).requires_grad_(True)
+        with torch.autocast("cuda", dtype=torch.float16, enabled=args.amp):
+            y = model.multi_scale_enhance(x, inp, None)
+    else:
+        C = 32 if args.step == "fam" else 64
+        model = (EnhancedFAM(C, C) if args.step == "fam" else ASPPModule(C, C)).to(dev).to(dt).train()
+        inp = torch.randn(args.B, C, args.H, args.W, generator=g).to(dev).to(dt).requires_grad_(True)
+        y = model(inp)
+    w = torch.randn(y.shape, generator=g).to(dev).to(y.dtype)
+    (y * w).sum().backward()
+    saved["out"], saved["grad.input"] = y.detach().clone(), inp.grad.detach().clone()
+    saved.update({f"grad.{n}": p.grad.detach().clone() for n, p in model.named_parameters() if p.grad is not None})
+    saved.update({f"buffer.{n}": b.detach().clone() for n, b in model.named_buffers()})
+
+
+def trace_step(args):
+    root = os.path.abspath(args.root) if args.root else os.path.dirname(HERE)
+    sys.path[:0] = [os.path.join(root, "retinex-image-enhancement_amd"), root]
+    import torch
+    from upr import _lib as L
+    dev = torch.device("cuda", 0)
+    saved = {}
+    with open(args.trace, "w") as out:
+        prox = _Traced(L.lib(), L.SIGNATURES, out)
+        L._lib = prox
+        try:
+            (_train if args.step == "train" else _sub)(args, torch, dev, saved)
+            torch.cuda.synchronize()
+        finally:
+            L._lib = prox._lib
+    if args.save:
+        torch.save({k: v.cpu() for k, v in saved.items()}, args.save)
+    print(f"{prox.n} calls -> {args.trace}; {len(saved)} tensors -> {args.save}")
+
+
+def print_calls(names):
+    sys.path.insert(0, os.path.join(HERE, "..", "retinex-image-enhancement_amd"))
+    from upr import _lib as L
+    lib = L.lib()
+    for n in names:
+        f = getattr(lib, n)
+
+        def wrap(*a, _f=f, _n=n):
+            vals = [getattr(x, "value", x) for x in a]
+            where = " <- ".join(f"{os.path.basename(f.filename)}:{f.lineno}"
+                                for f in traceback.extract_stack()[-2:-6:-1])
+            print(_n, [v if isinstance(v, int) and abs(v) < 1 << 20 else ("p" if v else 0) for v in vals], where,
+                  flush=True)
+            return _f(*a)
+        setattr(lib, n, wrap)
+    sys.argv = ["bench.py", "--train", "--amp", "--steps", "1", "--warmup", "0", "--cpu-seconds", "0"]
+    runpy.run_path(os.path.join(HERE, "..", "bench.py"), run_name="__main__")
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("names", nargs="?", help="comma-separated functions to print with their call sites")
+    ap.add_argument("--trace", help="write every call of the chosen step to this file")
+    ap.add_argument("--save", help="torch.save the step's results here")
+    ap.add_argument("--root", help="checkout whose package to drive (default: this one)")
+    ap.add_argument("--step", choices=("train", "head", "fam", "aspp"), default="train")
+    ap.add_argument("--variant", choices=("plain", "preact_aspp"), default="plain")
+    ap.add_argument("--amp", action="store_true")
+    ap.add_argument("--B", type=int, default=2)
+    ap.add_argument("--H", type=int, default=96)
+    ap.add_argument("--W", type=int, default=160)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--steps", type=int, default=2, help="training steps to trace (train)")
+    args = ap.parse_args()
+    if args.names:
+        print_calls(args.names.split(","))
+    elif args.trace:
+        trace_step(args)
+    else:
+        ap.error("give function names to print, or --trace FILE")
+
+
+if __name__ == "__main__":
+    main()
