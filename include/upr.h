@@ -340,6 +340,42 @@ size_t upr_image_metrics_workspace(int B, int H, int W);
 int upr_image_metrics(const void* enh, const void* ref, double* metrics, double* sums, int32_t* hist,
                       void* workspace, size_t workspace_bytes, int B, int H, int W, int dtype, void* stream);
 
+/* Lossless 8-bit RGB PNG files written entirely on the device (no reference
+ * counterpart: the reference saves through PIL on the host).  hwc_u8 is B
+ * images u8 [H,W,3]; image b's complete file is written contiguously at out +
+ * b * out_stride and its length to sizes[b] (device int64), so the host only
+ * copies sizes[b] bytes and writes them.  The file: signature, IHDR (bit depth
+ * 8, colour type 2, no interlace), one IDAT per strip of rows_per_strip rows
+ * (clamped to H; the last strip may be shorter), a trailing IDAT with the
+ * Adler-32, IEND.  A strip is one deflate block of dynamic Huffman codes over
+ * literals and end-of-block only (code lengths <= 15 bits, no LZ77 matches,
+ * no run symbols in the code-length alphabet, HDIST 0 with a distance code of
+ * length 0) followed by an empty stored block, or, when that would be no
+ * smaller, stored blocks of at most 65535 bytes: a file never exceeds
+ * bytes_per_image.  `filter` is a UPR_PNG_FILTER_* value; ADAPTIVE takes per
+ * row the type with the smallest sum of min(v, 256 - v) over the filtered
+ * bytes (ties: the lowest type).  Filters see raw pixels: the row above a
+ * strip's first row is the image row above it.  All checksums (CRC-32 of every
+ * chunk, Adler-32) are computed on the device; the output is a function of
+ * the pixels and the arguments only.
+ * upr_png_bound: the largest file of one H x W image (out_stride must be at
+ * least that) and the scratch bytes per image (upr_png_encode needs B times
+ * that, 16-byte aligned).  UPR_ERR_SHAPE, with nothing launched, when
+ * rows_per_strip * (3 W + 1) > UPR_PNG_MAX_STRIP_BYTES or bytes_per_image
+ * would exceed 2^31. */
+enum {
+  UPR_PNG_FILTER_NONE = 0,
+  UPR_PNG_FILTER_SUB = 1,
+  UPR_PNG_FILTER_UP = 2,
+  UPR_PNG_FILTER_AVG = 3,
+  UPR_PNG_FILTER_PAETH = 4,
+  UPR_PNG_FILTER_ADAPTIVE = 5
+};
+enum { UPR_PNG_MAX_STRIP_BYTES = 1 << 24 };
+int upr_png_bound(int H, int W, int rows_per_strip, size_t* bytes_per_image, size_t* scratch_bytes);
+int upr_png_encode(const uint8_t* hwc_u8, int B, int H, int W, int filter, int rows_per_strip, uint8_t* out,
+                   size_t out_stride, int64_t* sizes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Host copies of the 8-bit Lab integer tables (for CPU-side verification):
  * gamma[256], cbrt[3072], yf[512], invgamma[4096] (uint16), rgb2xyz[9], xyz2rgb[9]. */
 void upr_lab_tables(uint16_t* gamma, uint16_t* cbrt, uint16_t* yf, uint16_t* invgamma, int32_t* rgb2xyz,

@@ -1,7 +1,9 @@
 """Enhance harness (drop-in for reference enhancers/simple_enhance.py).
 
-Image decode/encode stays on the host (PIL), everything between load and save
-runs on the device.  Intentional divergences, each a reference bug:
+Image decode stays on the host (PIL); everything between load and save runs on
+the device.  PNG encode is the host's (PIL, the default) or, with
+png_encoder="device", the device's (upr.png: larger files, no host encode).
+Intentional divergences, each a reference bug:
   * enhance_single_image accepts and ignores `adjuster=` so main.py's
     single-file branch works (reference main.py:240-249 vs simple_enhance.py:135
     raises TypeError);
@@ -22,10 +24,21 @@ from enhancers.multi_scale import MultiScaleEnhancer
 from enhancers.content_aware import ContentAwareEnhancer
 from utils.letterbox import letterbox_u8_image
 
-# PNG encoders running beside the GPU (PIL's encoder releases the GIL); 3 files per
-# image, ~90 / ~160 ms of host CPU each for a 512^2 / comparison PNG of a noisy image,
-# so the batch harness is encode-bound: one writer per usable core but two, at most 14
-# (os.cpu_count() is the whole machine on a shared box; UPR_PNG_WRITERS overrides)
+# Writer threads running beside the GPU; 3 files per image.
+# png_encoder="host": each writer runs PIL's PNG encoder (it releases the GIL), ~90 /
+# ~160 ms of host CPU for a 512^2 / comparison PNG of a noisy image, so the batch
+# harness is encode-bound: one writer per usable core but two, at most 14
+# (os.cpu_count() is the whole machine on a shared box; UPR_PNG_WRITERS overrides).
+# png_encoder="device": the files are encoded on the GPU (upr.png) behind the image's
+# other launches; a writer only waits for them, copies the file's bytes and writes them.
+PNG_ENCODERS = ("host", "device")
+
+
+def _check_encoder(png_encoder):
+    if png_encoder not in PNG_ENCODERS:
+        raise ValueError(f"png_encoder must be one of {PNG_ENCODERS}, got {png_encoder!r}")
+
+
 def _writer_count():
     try:
         n = int(os.environ.get("UPR_PNG_WRITERS", "0"))
@@ -67,6 +80,12 @@ def _to_u8_hwc(t):
     return runtime.to_u8_hwc(t.detach()).cpu().numpy()
 
 
+def _to_u8_hwc_device(t):
+    """The same pixels as _to_u8_hwc, left on the device (png_encoder="device")."""
+    from upr import runtime
+    return runtime.to_u8_hwc(t.detach())
+
+
 def _write_png(arr, save_path, msg):
     Image.fromarray(arr).save(save_path)
     print(f"{msg}: {save_path}")
@@ -79,27 +98,65 @@ def _emit(arr, save_path, msg, writer):
         writer.submit(_write_png, arr, save_path, msg)
 
 
-def save_image(tensor, save_path, writer=None):
+def _write_device_pngs(buf, sizes, done, jobs):
+    """Files of one upr.png.encode_device call: wait for it, copy sizes[b] bytes of image b
+    and write them (no encoding on the host)."""
+    done.synchronize()
+    for b, n in enumerate(sizes.tolist()):
+        data = buf[b, :n].cpu().numpy().tobytes()
+        save_path, msg = jobs[b]
+        with open(save_path, "wb") as fh:
+            fh.write(data)
+        print(f"{msg}: {save_path}")
+
+
+def _emit_device(u8_images, jobs, writer):
+    """u8_images: u8 [B,H,W,3] (or [H,W,3]) on the device, jobs: (save_path, msg) per image.
+    The encode is queued on the current stream here; the copy and the write happen on the
+    writer thread (or right away without one)."""
+    from upr import png
+    buf, sizes = png.encode_device(u8_images)
+    done = torch.cuda.Event()
+    done.record(torch.cuda.current_stream(buf.device))
+    if writer is None:
+        _write_device_pngs(buf, sizes, done, jobs)
+    else:
+        writer.submit(_write_device_pngs, buf, sizes, done, jobs)
+
+
+def save_image(tensor, save_path, writer=None, png_encoder="host"):
     """[1,C,H,W] or [C,H,W] -> PNG; 1-channel maps are replicated to RGB (reference :65-99)."""
+    _check_encoder(png_encoder)
     if tensor.dim() == 4:
         tensor = tensor.squeeze(0)
-    _emit(_to_u8_hwc(tensor), save_path, "已保存", writer)
+    if png_encoder == "device":
+        _emit_device(_to_u8_hwc_device(tensor), [(save_path, "已保存")], writer)
+    else:
+        _emit(_to_u8_hwc(tensor), save_path, "已保存", writer)
 
 
-def create_comparison(img_low, img_enhanced, save_path, writer=None, illu_map=None):
+def create_comparison(img_low, img_enhanced, save_path, writer=None, illu_map=None, png_encoder="host"):
     """[input | enhanced] side by side (reference :102-132); with `illu_map`
     the predictor's 3-panel form [input | enhanced | illumination]
     (reference predictors/predict.py:102-140)."""
-    panels = [_to_u8_hwc(img_low.squeeze(0)), _to_u8_hwc(img_enhanced.squeeze(0))]
+    _check_encoder(png_encoder)
+    to_u8 = _to_u8_hwc_device if png_encoder == "device" else _to_u8_hwc
+    panels = [to_u8(img_low.squeeze(0)), to_u8(img_enhanced.squeeze(0))]
     if illu_map is not None:
-        panels.append(_to_u8_hwc(illu_map.squeeze(0)))
-    _emit(np.concatenate(panels, axis=1), save_path, "已保存对比图像", writer)
+        panels.append(to_u8(illu_map.squeeze(0)))
+    if png_encoder == "device":  # the panel is joined on the device, along W
+        _emit_device(torch.cat(panels, dim=1), [(save_path, "已保存对比图像")], writer)
+    else:
+        _emit(np.concatenate(panels, axis=1), save_path, "已保存对比图像", writer)
 
 
 def enhance_single_image(model, image_path, output_dir, device, max_size=None, enable_multi_scale=False,
-                         enable_content_aware=False, adjuster=None, precision="fp32", _decoded=None, _writer=None):
+                         enable_content_aware=False, adjuster=None, precision="fp32", _decoded=None, _writer=None,
+                         png_encoder="host"):
     """Enhance one file and write {name}_enhanced/_illumination/_comparison.png (reference :135-199).
-    precision="fp16" runs the fp16 storage / fp16-MFMA graph (input cast to half)."""
+    precision="fp16" runs the fp16 storage / fp16-MFMA graph (input cast to half).
+    png_encoder="device" encodes the three files on the GPU (same pixels, larger files)."""
+    _check_encoder(png_encoder)
     print(f"正在处理: {os.path.basename(image_path)}")
     img_low, _ = load_image(image_path, max_size, decoded=_decoded)
     if precision == "fp16":
@@ -119,9 +176,10 @@ def enhance_single_image(model, image_path, output_dir, device, max_size=None, e
     print(f"增强耗时: {time.time() - start:.4f}s")
     os.makedirs(output_dir, exist_ok=True)
     name = os.path.splitext(os.path.basename(image_path))[0]
-    save_image(img_enhanced, os.path.join(output_dir, f"{name}_enhanced.png"), _writer)
-    save_image(illu_map, os.path.join(output_dir, f"{name}_illumination.png"), _writer)
-    create_comparison(img_low, img_enhanced, os.path.join(output_dir, f"{name}_comparison.png"), _writer)
+    save_image(img_enhanced, os.path.join(output_dir, f"{name}_enhanced.png"), _writer, png_encoder)
+    save_image(illu_map, os.path.join(output_dir, f"{name}_illumination.png"), _writer, png_encoder)
+    create_comparison(img_low, img_enhanced, os.path.join(output_dir, f"{name}_comparison.png"), _writer,
+                      png_encoder=png_encoder)
     print("图像增强完成！")
     return img_enhanced, illu_map
 
@@ -133,8 +191,9 @@ def list_images(input_dir):
 
 
 def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preact=True, use_aspp=True, seed=None,
-                         precision="fp32"):
+                         precision="fp32", png_encoder="host"):
     """Enhance every image of a directory (reference :202-250)."""
+    _check_encoder(png_encoder)
     print("正在加载模型...")
     if seed is not None:
         torch.manual_seed(seed)
@@ -158,7 +217,7 @@ def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preac
             if i < len(image_files):
                 nxt = reader.submit(_decode, image_files[i])
             enhance_single_image(model, path, output_dir, device, max_size, precision=precision, _decoded=decoded,
-                                 _writer=writer)
+                                 _writer=writer, png_encoder=png_encoder)
             total += time.time() - t0
             print("-" * 50)
     print("=" * 50)

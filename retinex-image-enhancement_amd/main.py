@@ -3,7 +3,9 @@
 
 `--mode enhance` is the hot path: every image runs the fused gfx950 graph
 (libupr.so) and the device-side enhancers.  Additions: --seed (the reference
-never seeds its random init, main.py:229) and --precision {fp32,fp16}.
+never seeds its random init, main.py:229), --precision {fp32,fp16} and
+--png_encoder {host,device} (enhance / predict: PIL on the host, the default, or
+the device-side encoder of upr.png -- same pixels, larger files, no host encode).
 Intentional divergences (reference bugs): a single-file --mode enhance works
 (reference main.py:240-249 raises TypeError); --mode predict unpacks the
 model's 3-tuple (reference predict.py:163 raises ValueError).
@@ -76,6 +78,8 @@ def build_parser():
     # additions
     p.add_argument('--seed', type=int, default=None, help='seed the random init (reproducible outputs)')
     p.add_argument('--precision', choices=['fp32', 'fp16'], default='fp32')
+    p.add_argument('--png_encoder', choices=['host', 'device'], default='host',
+                   help='--mode enhance / predict: who encodes the PNGs (device: lossless, larger files)')
     p.add_argument('--reference_dir', type=str, default=None,
                    help='--mode evaluate: ground-truth images, matched by file stem (adds psnr / ssim / mse)')
     return p
@@ -105,10 +109,12 @@ def _predict_one(model, path, args):
         enh, _, illu = model(x)
     os.makedirs(args.output_dir, exist_ok=True)
     name = os.path.splitext(os.path.basename(path))[0]
-    save_image(enh, os.path.join(args.output_dir, f"{name}_enhanced.png"))
-    save_image(illu, os.path.join(args.output_dir, f"{name}_illumination.png"))
+    enc = args.png_encoder
+    save_image(enh, os.path.join(args.output_dir, f"{name}_enhanced.png"), png_encoder=enc)
+    save_image(illu, os.path.join(args.output_dir, f"{name}_illumination.png"), png_encoder=enc)
     if not args.no_comparison:
-        create_comparison(x, enh, os.path.join(args.output_dir, f"{name}_comparison.png"), illu_map=illu)
+        create_comparison(x, enh, os.path.join(args.output_dir, f"{name}_comparison.png"), illu_map=illu,
+                          png_encoder=enc)
 
 
 def _reference_stems(reference_dir):
@@ -220,11 +226,12 @@ def main(argv=None):
         enhance_single_image(model=model, image_path=str(p), output_dir=args.output_dir, device=args.device,
                              max_size=args.max_size, adjuster=AdaptiveParameterAdjuster(),
                              enable_multi_scale=args.multi_scale, enable_content_aware=args.content_aware,
-                             precision=args.precision)
+                             precision=args.precision, png_encoder=args.png_encoder)
     elif p.is_dir():
         # reference: enhance_batch_images builds UP_Retinex() with its defaults (preact + ASPP)
         enhance_batch_images(input_dir=str(p), output_dir=args.output_dir, device=args.device,
-                             max_size=args.max_size, seed=args.seed, precision=args.precision)
+                             max_size=args.max_size, seed=args.seed, precision=args.precision,
+                             png_encoder=args.png_encoder)
     else:
         print(f"错误: 输入路径 '{args.input_path}' 不存在")
         return

@@ -50,6 +50,10 @@ UPR_METRICS_N = 9
 UPR_METRICS_NSUMS = 14
 METRIC_NAMES = ("mean_brightness", "contrast", "entropy", "niqe", "saturation", "naturalness", "mse", "psnr", "ssim")
 
+# include/upr.h UPR_PNG_FILTER_*: upr_png_encode's `filter`
+PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "avg": 3, "paeth": 4, "adaptive": 5}
+UPR_PNG_MAX_STRIP_BYTES = 1 << 24
+
 UPR_OP_CONV_IGEMM = 0
 UPR_OP_OTHER = 1
 UPR_CALIB_MFMA_F16 = 0
@@ -103,6 +107,9 @@ SIGNATURES = {
     "upr_image_metrics_workspace": (c_size_t, [c_int, c_int, c_int]),
     "upr_image_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int,
                                   c_int, c_int, c_void_p]),
+    "upr_png_bound": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
+    "upr_png_encode": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                               c_size_t, c_void_p]),
     "upr_lab_tables": (None, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "upr_retinex_decompose": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_void_p]),

@@ -3,7 +3,7 @@
 letterbox -> model + CLAHE-in-Lab enhancer -> device u8 -> PNG encode):
 enhance_batch_images over N synthetic low-light PNGs, images/s including IO.
 
-  python tools/harness_bench.py --n 32 --size 512 [--precision fp16]
+  python tools/harness_bench.py --n 32 --size 512 [--precision fp16] [--png_encoder device]
 """
 import argparse
 import contextlib
@@ -27,7 +27,9 @@ def main():
     ap.add_argument("--n", type=int, default=32)
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--precision", choices=["fp32", "fp16"], default="fp32")
+    ap.add_argument("--png_encoder", choices=["host", "device"], default="host")
     args = ap.parse_args()
+    kw = {"png_encoder": args.png_encoder} if args.png_encoder != "host" else {}
     from enhancers.simple_enhance import enhance_batch_images
     with tempfile.TemporaryDirectory(dir="/tmp") as d:
         src, out = os.path.join(d, "in"), os.path.join(d, "out")
@@ -37,16 +39,17 @@ def main():
             a = (rng.integers(0, 256, (args.size, args.size, 3)) * 0.35).astype(np.uint8)
             Image.fromarray(a).save(os.path.join(src, f"img{k:03d}.png"))
         with contextlib.redirect_stdout(io.StringIO()):
-            enhance_batch_images(src, out + "_warm", "cuda", seed=0, precision=args.precision)  # warm-up (packing)
+            enhance_batch_images(src, out + "_warm", "cuda", seed=0, precision=args.precision, **kw)  # warm-up (packing)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            enhance_batch_images(src, out, "cuda", seed=0, precision=args.precision)
+            enhance_batch_images(src, out, "cuda", seed=0, precision=args.precision, **kw)
             torch.cuda.synchronize()
             el = time.perf_counter() - t0
         n_out = len(os.listdir(out))
     print(json.dumps({"metric": "enhance harness images/s (decode + letterbox + UP_Retinex preact+ASPP + "
                                 "CLAHE-in-Lab + 3 PNG writes per image)", "value": args.n / el, "unit": "images/s",
-                      "n": args.n, "size": args.size, "precision": args.precision, "seconds": el,
+                      "n": args.n, "size": args.size, "precision": args.precision, "png_encoder": args.png_encoder,
+                      "seconds": el,
                       "files_written": n_out}))
 
 
