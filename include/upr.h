@@ -362,7 +362,20 @@ int upr_image_metrics(const void* enh, const void* ref, double* metrics, double*
  * least that) and the scratch bytes per image (upr_png_encode needs B times
  * that, 16-byte aligned).  UPR_ERR_SHAPE, with nothing launched, when
  * rows_per_strip * (3 W + 1) > UPR_PNG_MAX_STRIP_BYTES or bytes_per_image
- * would exceed 2^31. */
+ * would exceed 2^31.
+ * The _ex forms take a match mode; upr_png_bound and upr_png_encode are the
+ * _ex forms with UPR_PNG_MATCH_NONE, the file described above.  With
+ * UPR_PNG_MATCH_LZ a strip's filtered bytes are also parsed greedily into
+ * literals and LZ77 matches (length 3..258, distance 1..32768, never reaching
+ * before the strip's first filtered byte, so each IDAT payload stays an
+ * independent deflate stream on a byte boundary), coded with a literal/length
+ * and a distance code (<= 15 bits, HLIT and HDIST as used, extra bits as in
+ * RFC 1951 3.2.5), and the strip is written in the smallest of three forms:
+ * that block, the literal-only block, stored blocks.  No strip is larger than
+ * with MATCH_NONE, so bytes_per_image is the same; scratch_bytes grows by the
+ * staged filtered bytes and one 32-bit match word per filtered byte.  The
+ * output is still a function of the pixels and the arguments only.  A match
+ * value other than the two is UPR_ERR_ARG. */
 enum {
   UPR_PNG_FILTER_NONE = 0,
   UPR_PNG_FILTER_SUB = 1,
@@ -372,7 +385,12 @@ enum {
   UPR_PNG_FILTER_ADAPTIVE = 5
 };
 enum { UPR_PNG_MAX_STRIP_BYTES = 1 << 24 };
+enum { UPR_PNG_MATCH_NONE = 0, UPR_PNG_MATCH_LZ = 1 };
 int upr_png_bound(int H, int W, int rows_per_strip, size_t* bytes_per_image, size_t* scratch_bytes);
+int upr_png_bound_ex(int H, int W, int rows_per_strip, int match, size_t* bytes_per_image, size_t* scratch_bytes);
+int upr_png_encode_ex(const uint8_t* hwc_u8, int B, int H, int W, int filter, int match, int rows_per_strip,
+                      uint8_t* out, size_t out_stride, int64_t* sizes, void* scratch, size_t scratch_bytes,
+                      void* stream);
 int upr_png_encode(const uint8_t* hwc_u8, int B, int H, int W, int filter, int rows_per_strip, uint8_t* out,
                    size_t out_stride, int64_t* sizes, void* scratch, size_t scratch_bytes, void* stream);
 

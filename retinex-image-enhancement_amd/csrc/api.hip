@@ -31,8 +31,8 @@ int launch_decompose(const void* x, const void* illu, void* refl, int B, int C, 
                      hipStream_t st);
 int launch_decompose_bwd(const void* x, const void* illu, const void* g, void* gx, void* gillu, int B, int C, int HW,
                          int illu_c, int dtype, hipStream_t st);
-int png_bound(int H, int W, int rows_per_strip, size_t* bytes_per_image, size_t* scratch_bytes);
-int launch_png_encode(const uint8_t* img, int B, int H, int W, int filter, int rows_per_strip, uint8_t* out,
+int png_bound(int H, int W, int rows_per_strip, int match, size_t* bytes_per_image, size_t* scratch_bytes);
+int launch_png_encode(const uint8_t* img, int B, int H, int W, int filter, int match, int rows_per_strip, uint8_t* out,
                       size_t out_stride, long long* sizes, uint8_t* scratch, size_t scratch_bytes, hipStream_t st);
 }  // namespace upr
 
@@ -158,17 +158,30 @@ int upr_retinex_decompose_bwd(const void* x, const void* illu, const void* g, vo
   return launch_decompose_bwd(x, illu, g, gx, gillu, B, C, H * W, illu_c, dtype, (hipStream_t)stream);
 }
 
-int upr_png_bound(int H, int W, int rows_per_strip, size_t* bytes_per_image, size_t* scratch_bytes) {
+int upr_png_bound_ex(int H, int W, int rows_per_strip, int match, size_t* bytes_per_image, size_t* scratch_bytes) {
   if (!bytes_per_image || !scratch_bytes) return UPR_ERR_ARG;
-  return png_bound(H, W, rows_per_strip, bytes_per_image, scratch_bytes);
+  if (match != UPR_PNG_MATCH_NONE && match != UPR_PNG_MATCH_LZ) return UPR_ERR_ARG;
+  return png_bound(H, W, rows_per_strip, match, bytes_per_image, scratch_bytes);
+}
+
+int upr_png_bound(int H, int W, int rows_per_strip, size_t* bytes_per_image, size_t* scratch_bytes) {
+  return upr_png_bound_ex(H, W, rows_per_strip, UPR_PNG_MATCH_NONE, bytes_per_image, scratch_bytes);
+}
+
+int upr_png_encode_ex(const uint8_t* hwc_u8, int B, int H, int W, int filter, int match, int rows_per_strip,
+                      uint8_t* out, size_t out_stride, int64_t* sizes, void* scratch, size_t scratch_bytes,
+                      void* stream) {
+  if (!hwc_u8 || !out || !sizes || !scratch || B <= 0 || H <= 0 || W <= 0 || rows_per_strip <= 0) return UPR_ERR_ARG;
+  if (filter < UPR_PNG_FILTER_NONE || filter > UPR_PNG_FILTER_ADAPTIVE || ((size_t)scratch & 15)) return UPR_ERR_ARG;
+  if (match != UPR_PNG_MATCH_NONE && match != UPR_PNG_MATCH_LZ) return UPR_ERR_ARG;
+  return launch_png_encode(hwc_u8, B, H, W, filter, match, rows_per_strip, out, out_stride, (long long*)sizes,
+                           (uint8_t*)scratch, scratch_bytes, (hipStream_t)stream);
 }
 
 int upr_png_encode(const uint8_t* hwc_u8, int B, int H, int W, int filter, int rows_per_strip, uint8_t* out,
                    size_t out_stride, int64_t* sizes, void* scratch, size_t scratch_bytes, void* stream) {
-  if (!hwc_u8 || !out || !sizes || !scratch || B <= 0 || H <= 0 || W <= 0 || rows_per_strip <= 0) return UPR_ERR_ARG;
-  if (filter < UPR_PNG_FILTER_NONE || filter > UPR_PNG_FILTER_ADAPTIVE || ((size_t)scratch & 15)) return UPR_ERR_ARG;
-  return launch_png_encode(hwc_u8, B, H, W, filter, rows_per_strip, out, out_stride, (long long*)sizes,
-                           (uint8_t*)scratch, scratch_bytes, (hipStream_t)stream);
+  return upr_png_encode_ex(hwc_u8, B, H, W, filter, UPR_PNG_MATCH_NONE, rows_per_strip, out, out_stride, sizes, scratch,
+                           scratch_bytes, stream);
 }
 
 void upr_lab_tables(uint16_t* gamma, uint16_t* cbrt, uint16_t* yf, uint16_t* invgamma, int32_t* rgb2xyz,

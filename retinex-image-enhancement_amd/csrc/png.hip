@@ -15,6 +15,13 @@
 //                      Adler-32 of the image, signature / IHDR / trailer / IEND
 //   png_gather_kernel  one workgroup per (strip, image): chunk -> its place in the file
 //
+// With match = UPR_PNG_MATCH_LZ (upr_png_encode_ex) the strip kernel also stages the strip's
+// filtered bytes in scratch (and in LDS when they fit), finds LZ77 matches inside the strip
+// (64 positions per step, four candidates per position: distance 1 / 3, the byte above, the earliest equal hash of the step,
+// the most recent equal hash before it), resolves the greedy parse with per-run exit tables
+// instead of one serial walk, builds the literal/length and distance codes and writes the
+// matched block when it is smaller than both the literal-only block and the stored form.
+//
 // Every byte is written with ordinary vector stores; nothing is computed on the host.
 #include "upr_common.h"
 
@@ -25,7 +32,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kRun = 16;                   // consecutive symbols one thread packs per chunk
 constexpr int kChunk = kThreads * kRun;    // symbols per chunk
-constexpr int kStageWords = 2048;          // >= (kChunk * 15 + 3 + 31) / 32 + 2
+constexpr int kStageWords = 2048;          // >= (kChunk * 15 + 3 + 31) / 32 + 2; match mode: see emit_chunk
 constexpr int kLit = 257;                  // literals + end-of-block
 constexpr int kCl = 19;                    // code-length alphabet
 constexpr int kSymPad = 288;
@@ -37,6 +44,26 @@ constexpr int kTailBytes = 16 + 12;        // Adler IDAT + IEND
 // rows_per_strip * (3W + 1) limit: histogram counts, bit offsets (15 bits per
 // symbol) and the 64-bit Adler partial sums all stay in range below it
 constexpr long long kMaxStripBytes = 1LL << 24;
+// match mode LZ
+constexpr int kMatchLz = 1;
+constexpr int kLl = 286;                   // literal/length alphabet
+constexpr int kDist = 30;                  // distance alphabet
+constexpr int kMinMatch = 3, kMaxMatch = 258;
+constexpr unsigned kMaxDist = 32768;
+constexpr unsigned kFar3 = 4096;           // a match of 3 bytes further back costs more than 3 literals
+constexpr int kHashBits = 12;
+constexpr int kHashSize = 1 << kHashBits;
+constexpr int kStep = kThreads / 4;        // positions matched per step, 4 threads each
+constexpr int kStepTab = 256;              // hash slots of the earliest-in-step table
+constexpr int kSuper = kRun * kRun;        // positions per super-run of the parse
+constexpr unsigned kTaken = 0x8000u;       // match word: length | kTaken | distance << 16
+constexpr int kFbSlack = 48;               // bytes readable behind a strip's staged bytes
+// dynamic LDS for a strip's bytes at the most: with the static 40 KB a workgroup stays within
+// 64 KB, two or more to a compute unit; 16 rows of 512 pixels (24592 + 48 bytes) still fit
+constexpr unsigned kLzLdsMax = 24640;
+static_assert(kStep == 64, "the step table packs the position in 6 bits");
+static_assert(kChunk == kRun * kSuper && kChunk + kMaxMatch < 0xFFFF, "parse tables are u16 over three levels of kRun");
+static_assert(kStepTab + (kRun + kThreads) / 2 <= kStageWords, "the step table and the entry lists live in the stage");
 
 struct PngGeom {
   int H, W, rps, ns;        // ns strips of rps rows (the last may be shorter)
@@ -45,12 +72,15 @@ struct PngGeom {
   size_t file_bound;        // bytes of one image's file, at most
   size_t scratch_image;     // scratch bytes of one image
   size_t off_sizes, off_adler, off_offs, off_ftype;  // arrays behind the ns slots
+  // match mode LZ: per strip lz_stride bytes at off_lz, the filtered bytes (+ kFbSlack) and
+  // from lz_md one match word per filtered byte
+  size_t off_lz, lz_md, lz_stride;
 };
 
 inline size_t stored_bytes(size_t n) { return n + 5 * ((n + 65534) / 65535) + 5; }
 
 // kOk and the geometry, or the status of a shape the encoder does not take
-int png_geom(int H, int W, int rps, PngGeom* g) {
+int png_geom(int H, int W, int rps, int match, PngGeom* g) {
   if (H <= 0 || W <= 0 || rps <= 0) return kErrArg;
   if (rps > H) rps = H;
   const long long rowb = 3LL * W + 1;
@@ -71,6 +101,10 @@ int png_geom(int H, int W, int rps, PngGeom* g) {
   g->off_offs = g->off_adler + align_up((size_t)ns * 8, 16);
   g->off_ftype = g->off_offs + align_up((size_t)ns * 4, 16);
   g->scratch_image = g->off_ftype + align_up((size_t)H, 16);
+  g->off_lz = g->scratch_image;
+  g->lz_md = align_up((size_t)(rowb * rps) + kFbSlack, 16);
+  g->lz_stride = g->lz_md + align_up(4 * (size_t)(rowb * rps), 16);
+  if (match == kMatchLz) g->scratch_image += (size_t)ns * g->lz_stride;
   return kOk;
 }
 
@@ -82,7 +116,25 @@ struct PngArgs {
   size_t out_stride;
   PngGeom g;
   int filter;
+  unsigned lds_bytes;       // dynamic LDS of the strip kernel's launch
 };
+
+// RFC 1951 3.2.5: code and number of extra bits of a match length 3 .. 258 / distance 1 .. 32768;
+// the extra bits' value is the low `eb` bits of len - 3 / dist - 1
+__host__ __device__ __forceinline__ unsigned len_code(unsigned len, unsigned* eb) {
+  const unsigned l = len - 3;
+  if (len == 258 || l < 8) { *eb = 0; return len == 258 ? 285u : 257u + l; }
+  const unsigned k = 31u - (unsigned)__builtin_clz(l);
+  *eb = k - 2;
+  return 261u + 4u * (k - 2) + ((l >> (k - 2)) & 3u);
+}
+__host__ __device__ __forceinline__ unsigned dist_code(unsigned dist, unsigned* eb) {
+  const unsigned x = dist - 1;
+  if (x < 4) { *eb = 0; return x; }
+  const unsigned k = 31u - (unsigned)__builtin_clz(x);
+  *eb = k - 1;
+  return 2u * k + ((x >> (k - 1)) & 1u);
+}
 
 // ---- small workgroup helpers (kThreads = 4 waves of 64) -----------------------------------------
 __device__ __forceinline__ unsigned wave_incl_scan(unsigned v, int lane) {
@@ -204,7 +256,9 @@ struct HuffWork {
 // lens[s] = code length of symbol s (0: unused) of a Huffman code over cnt[0 .. n) no deeper than
 // `limit`: the plain Huffman code if it fits, else the code of the counts halved (non-zero counts
 // kept >= 1) as often as needed.  Deterministic: the sort key is (count, symbol), the two-queue
-// merge prefers a leaf on a tie.  All threads call it; at least two counts are non-zero.
+// merge prefers a leaf on a tie.  All threads call it; at least one count is non-zero.  A single
+// used symbol gets length 1 (the m == 1 branch): match mode relies on that for a strip whose
+// matches share one distance code; the literal alphabets always hold two symbols or more.
 __device__ void huff_lengths(const unsigned* cnt, int n, int limit, unsigned* lens, HuffWork& w) {
   const int tid = threadIdx.x;
   for (int s = tid; s < n; s += kThreads) { w.cnt[s] = cnt[s]; lens[s] = 0; }
@@ -306,8 +360,244 @@ struct StripLds {
   HuffWork hw;
 };
 
+// ---- match mode LZ ------------------------------------------------------------------------------
+struct LzLds {
+  unsigned hist[kSymPad], lens[kSymPad], codes[kSymPad];  // literal/length alphabet of the parse
+  unsigned dhist[32], dlens[32], dcodes[32];              // distance alphabet
+  unsigned clhist[32], cllens[32], clcodes[32];
+  union {
+    unsigned recent[kHashSize];  // matching: hash -> 1 + the most recent position before the step
+    struct {
+      unsigned short e1[kChunk];  // parse: where the greedy walk from a position leaves its run ...
+      unsigned short e2[kChunk];  // ... and its super-run (chunk-local positions)
+    } p;
+  } u;
+  unsigned exitp, nl, nd;
+};
+struct LzNone {};
+// what kLzLdsMax promises: static and dynamic LDS of the match-mode kernel within 64 KiB
+static_assert(sizeof(StripLds) + sizeof(LzLds) + kLzLdsMax <= 64 * 1024, "LDS of the match-mode strip kernel");
+
+// bytes i .. i + 7 of the staged bytes (fbw: their 8-byte words) from two aligned words; reads up
+// to 15 bytes behind i
+__device__ __forceinline__ unsigned long long load8(const unsigned long long* fbw, unsigned i) {
+  const unsigned long long lo = fbw[i >> 3], hi = fbw[(i >> 3) + 1];
+  const unsigned sh = (i & 7u) * 8u;
+  return (lo >> sh) | ((hi << 1) << (63u - sh));
+}
+
+// common prefix of the bytes at i and at p, at most maxlen (0: none); x0 = load8(fbw, i).  The
+// first 8 bytes decide most candidates; behind them 32 bytes per round, so that one LDS round
+// trip covers them.  Reads up to 39 bytes behind i + maxlen - 1.
+__device__ __forceinline__ unsigned match_len(const unsigned long long* fbw, unsigned i, unsigned p, unsigned maxlen,
+                                              unsigned long long x0) {
+  if (!maxlen) return 0;
+  x0 ^= load8(fbw, p);
+  if (x0) return min((unsigned)(__ffsll((long long)x0) - 1) >> 3, maxlen);
+  unsigned l = 8;
+  while (l < maxlen) {
+    const unsigned ia = i + l, ip = p + l;
+    const unsigned long long* wa = fbw + (ia >> 3);
+    const unsigned long long* wp = fbw + (ip >> 3);
+    const unsigned sa = (ia & 7u) * 8u, sp = (ip & 7u) * 8u;
+    unsigned long long a[5], q[5], x[4];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) { a[k] = wa[k]; q[k] = wp[k]; }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      x[k] = ((a[k] >> sa) | ((a[k + 1] << 1) << (63u - sa))) ^ ((q[k] >> sp) | ((q[k + 1] << 1) << (63u - sp)));
+    if (x[0] | x[1] | x[2] | x[3]) {
+      const int k = x[0] ? 0 : (x[1] ? 1 : (x[2] ? 2 : 3));
+      const unsigned long long xk = x[0] ? x[0] : (x[1] ? x[1] : (x[2] ? x[2] : x[3]));
+      l += 8u * (unsigned)k + ((unsigned)(__ffsll((long long)xk) - 1) >> 3);
+      break;
+    }
+    l += 32;
+  }
+  return min(l, maxlen);
+}
+
+// kRun entries per thread, bits | count << 56 (count <= 48), appended to the strip's bit stream
+// through the stage as the literal-only form does; all threads call it.  What a call may bring:
+// the header chunk at most 16 + 17 + 3 kCl + 7 (kLl + kDist) bits; a chunk of kChunk positions at
+// most 15 bits per position that its entries cover plus one entry of 48 bits, because a literal
+// is at most 15 bits and a match of length L at most 15 L (3 <= L <= 10: no length extra bits,
+// 15 + 15 + 13; a match of 3 reaches kFar3 back at the most, 10 distance extra bits; L >= 11:
+// 48 <= 15 L), and only the chunk's last match covers positions behind the chunk.
+static_assert(31 + kChunk * 15 + 48 <= (kStageWords - 2) * 32, "a chunk of matched entries fits the stage");
+static_assert(31 + 16 + 17 + 3 * kCl + 7 * (kLl + kDist) <= (kStageWords - 2) * 32, "the header fits the stage");
+__device__ __forceinline__ void emit_chunk(const unsigned long long (&sym)[kRun], StripLds& L, unsigned* dataw,
+                                           unsigned& carry, unsigned& outw) {
+  const int tid = threadIdx.x;
+  unsigned nbits = 0;
+#pragma unroll
+  for (int k = 0; k < kRun; ++k) nbits += (unsigned)(sym[k] >> 56);
+  unsigned total;
+  const unsigned pos = carry + block_excl_scan(nbits, L.red, &total);
+  unsigned wi = pos >> 5, nb = pos & 31u;
+  unsigned long long acc = 0;
+#pragma unroll
+  for (int k = 0; k < kRun; ++k) {
+    const unsigned c = (unsigned)(sym[k] >> 56), c1 = min(c, 24u);
+    // two parts of at most 24 bits, so the accumulator never holds more than 31 + 24 bits
+    acc |= (sym[k] & 0xffffffull) << nb;
+    nb += c1;
+    if (nb >= 32) { atomicOr(&L.stage[wi], (unsigned)acc); ++wi; acc >>= 32; nb -= 32; }
+    acc |= ((sym[k] >> 24) & 0xffffffull) << nb;
+    nb += c - c1;
+    if (nb >= 32) { atomicOr(&L.stage[wi], (unsigned)acc); ++wi; acc >>= 32; nb -= 32; }
+  }
+  if (nb) atomicOr(&L.stage[wi], (unsigned)acc);
+  __syncthreads();
+  const unsigned T = carry + total;
+  const unsigned full = T >> 5;
+  for (unsigned k = tid; k < full; k += kThreads) dataw[outw + k] = L.stage[k];
+  const unsigned cw = L.stage[full];
+  __syncthreads();
+  for (unsigned k = tid; k <= full; k += kThreads) L.stage[k] = 0;
+  __syncthreads();
+  if (tid == 0) L.stage[0] = cw;
+  __syncthreads();
+  outw += full;
+  carry = T & 31u;
+}
+
+// Workgroup barrier that orders LDS accesses only: stores to global memory stay in flight.  The
+// matcher's steps exchange data through LDS alone; what they store to scratch is read after a
+// __syncthreads().
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// Matches of the strip's staged bytes (fbw: their 8-byte words, in LDS when the strip fits the
+// launch's dynamic LDS, else in scratch; kFbSlack readable bytes behind them): md[i] = length |
+// distance << 16 of the match taken at i if the parse reaches i, 0 for a literal.  kStep
+// positions per step, four threads
+// each: distances 1 and 3, distance rowb, the earliest position of this step with the same
+// 3-byte hash (tab, tagged with the step), the most recent one before the step (recent, filled
+// by atomicMax after the step's lookups).  Longest wins, then the nearest: no dependence on timing.
+__device__ __forceinline__ void lz_match(const unsigned long long* fbw, unsigned* md, unsigned n, unsigned rowb,
+                                         LzLds& Z, unsigned* tab) {
+  const int tid = threadIdx.x;
+  const unsigned q = (unsigned)tid >> 2, role = (unsigned)tid & 3u;
+  for (int k = tid; k < kHashSize; k += kThreads) Z.u.recent[k] = 0;
+  bool pend = false;
+  unsigned pend_h = 0, pend_i = 0;
+  __syncthreads();
+  for (unsigned base = 0, step = 1; base < n; base += kStep, ++step) {
+    const unsigned i = base + q;
+    const bool ok = i + kMinMatch <= n;
+    const unsigned long long x0 = i < n ? load8(fbw, i) : 0ull;
+    const unsigned h = (((unsigned)x0 & 0xffffffu) * 0x9E3779B1u) >> (32 - kHashBits);
+    if (role == 0) {
+      if (pend) atomicMax(&Z.u.recent[pend_h], pend_i + 1);
+      if (ok) atomicMax(&tab[h & (kStepTab - 1)], step << 6 | (unsigned)(kStep - 1 - q));
+    }
+    lds_barrier();
+    unsigned key = 0;  // length << 16 | 65536 - distance
+    {
+      // one instruction stream for the four roles: both tables are read by every thread, the
+      // role only selects the distance (0: no candidate); role 0 has a second one
+      const unsigned maxlen = ok ? min((unsigned)kMaxMatch, n - i) : 0u;
+      const unsigned vt = tab[h & (kStepTab - 1)], vr = Z.u.recent[h];
+      const unsigned pt = base + (unsigned)(kStep - 1) - (vt & 63u);
+      const unsigned dt = ((vt >> 6) == step && pt < i) ? i - pt : 0u;
+      const unsigned dr = (vr && i - (vr - 1) <= kMaxDist) ? i - (vr - 1) : 0u;
+      const unsigned dup = (rowb <= kMaxDist && i >= rowb) ? rowb : 0u;
+      const unsigned d0 = role == 0 ? (i >= 1 ? 1u : 0u) : (role == 1 ? dup : (role == 2 ? dt : dr));
+      const unsigned d1 = (role == 0 && i >= 3) ? 3u : 0u;
+      const unsigned l0 = match_len(fbw, i, i - d0, d0 ? maxlen : 0u, x0);
+      if (l0 >= kMinMatch) key = l0 << 16 | (65536u - d0);
+      const unsigned l1 = match_len(fbw, i, i - d1, d1 ? maxlen : 0u, x0);
+      if (l1 >= kMinMatch) key = max(key, l1 << 16 | (65536u - d1));
+    }
+    key = max(key, (unsigned)__shfl_xor((int)key, 1, 64));
+    key = max(key, (unsigned)__shfl_xor((int)key, 2, 64));
+    if (role == 0 && i < n) {
+      const unsigned len = key >> 16, dist = 65536u - (key & 0xffffu);
+      md[i] = (len < kMinMatch || (len == kMinMatch && dist > kFar3)) ? 0u : (len | dist << 16);
+    }
+    pend = ok; pend_h = h; pend_i = i;
+    lds_barrier();
+  }
+  __syncthreads();
+}
+
+// The greedy parse of md[0 .. n) ("after a match of length L at i go on at i + L") without a
+// serial walk: per chunk of kChunk positions, e1 = where the walk from each position leaves
+// its thread's run of kRun (kRun backward steps in the thread), e2 = where it leaves its
+// super-run of kRun runs (kRun steps over e1); one thread then visits the chunk's super-runs,
+// kRun threads the runs of theirs, every thread the positions of its run.  The positions on
+// the walk get kTaken, their symbols go into Z.hist / Z.dhist.  Returns this thread's share of
+// (extra bits, matches).  ent2 / ent1: kRun / kThreads u16 entry lists.
+__device__ void lz_parse(const uint8_t* fb, unsigned* md, unsigned n, LzLds& Z, unsigned short* ent2,
+                         unsigned short* ent1, unsigned long long* extra_bits, unsigned long long* matches) {
+  const int tid = threadIdx.x;
+  unsigned long long extra = 0, nm = 0;
+  unsigned ent = 0;  // first position of the walk at or behind the chunk's base
+  for (unsigned cb = 0; cb < n; cb += kChunk) {
+    const unsigned nloc = min((unsigned)kChunk, n - cb);
+    const unsigned run_end = (unsigned)(tid + 1) * kRun;
+    for (int k = kRun - 1; k >= 0; --k) {
+      const unsigned loc = (unsigned)tid * kRun + (unsigned)k;
+      const unsigned len = loc < nloc ? (md[cb + loc] & 0xffffu) : 0u;
+      const unsigned nx = loc + max(1u, len);
+      Z.u.p.e1[loc] = (unsigned short)(nx >= run_end ? nx : Z.u.p.e1[nx]);
+    }
+    ent1[tid] = 0xFFFF;
+    if (tid < kRun) ent2[tid] = 0xFFFF;
+    __syncthreads();
+    {
+      const unsigned sbase = ((unsigned)tid / kRun) * kSuper, j = (unsigned)tid % kRun, send = sbase + kSuper;
+      for (int r = kRun - 1; r >= 0; --r) {
+        const unsigned loc = sbase + (unsigned)r * kRun + j;
+        const unsigned x = Z.u.p.e1[loc];
+        Z.u.p.e2[loc] = (unsigned short)(x >= send ? x : Z.u.p.e2[x]);
+        __syncthreads();
+      }
+    }
+    if (tid == 0) {
+      unsigned p = ent - cb;
+      while (p < nloc) { ent2[p / kSuper] = (unsigned short)p; p = Z.u.p.e2[p]; }
+      Z.exitp = p;
+    }
+    __syncthreads();
+    if (tid < kRun) {
+      unsigned p = ent2[tid];
+      const unsigned send = (unsigned)(tid + 1) * kSuper;
+      if (p != 0xFFFF)
+        while (p < send && p < nloc) { ent1[p / kRun] = (unsigned short)p; p = Z.u.p.e1[p]; }
+    }
+    __syncthreads();
+    {
+      unsigned p = ent1[tid];
+      if (p != 0xFFFF)
+        while (p < run_end && p < nloc) {
+          const unsigned m = md[cb + p], len = m & 0xffffu;
+          if (len) {
+            unsigned le, de;
+            atomicAdd(&Z.hist[len_code(len, &le)], 1u);
+            atomicAdd(&Z.dhist[dist_code(m >> 16, &de)], 1u);
+            extra += le + de;
+            ++nm;
+          } else {
+            atomicAdd(&Z.hist[fb[cb + p]], 1u);
+          }
+          md[cb + p] = m | kTaken;
+          p += max(1u, len);
+        }
+    }
+    ent = cb + Z.exitp;
+    __syncthreads();
+  }
+  *extra_bits = extra;
+  *matches = nm;
+}
+
+extern __shared__ unsigned long long lz_dyn[];  // match mode LZ: a strip's filtered bytes + kFbSlack, if they fit
+
+template <bool kLz>
 __global__ __launch_bounds__(kThreads) void png_strip_kernel(PngArgs a) {
   __shared__ StripLds L;
+  __shared__ typename std::conditional<kLz, LzLds, LzNone>::type Z;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int s = blockIdx.x, b = blockIdx.y;
   const PngGeom& g = a.g;
@@ -320,6 +610,17 @@ __global__ __launch_bounds__(kThreads) void png_strip_kernel(PngArgs a) {
   uint8_t* slot = sc + (size_t)s * g.cap;
   uint8_t* ftypes = sc + g.off_ftype;
   const bool first = s == 0, last = s == g.ns - 1;
+  uint8_t* fb = nullptr;    // match mode LZ: the strip's filtered bytes and match words
+  unsigned* md = nullptr;
+  // the matcher reads the bytes from LDS when the launch gave it room for a whole strip
+  const bool in_lds = kLz && a.lds_bytes >= (unsigned)(g.rps * g.rowb + kFbSlack);
+  if constexpr (kLz) {
+    fb = sc + g.off_lz + (size_t)s * g.lz_stride;
+    md = (unsigned*)(fb + g.lz_md);
+    for (int k = tid; k < kSymPad; k += kThreads) Z.hist[k] = 0;
+    if (tid < 32) { Z.dhist[tid] = 0; Z.clhist[tid] = 0; }
+    if (tid == 0) { Z.nl = 0; Z.nd = 0; }
+  }
 
   // CRC table and cleared LDS
   {
@@ -377,6 +678,10 @@ __global__ __launch_bounds__(kThreads) void png_strip_kernel(PngArgs a) {
     unsigned prev = 256, run = 0;
     for (; i < end; ++i) {
       const unsigned d = col == 0 ? (unsigned)ft : filt_byte(row, up, col - 1, ft);
+      if constexpr (kLz) {
+        fb[i] = (uint8_t)d;
+        if (in_lds) ((uint8_t*)lz_dyn)[i] = (uint8_t)d;
+      }
       adA += d;
       adB += (unsigned long long)(n - i) * d;
       if (d == prev) ++run;
@@ -423,9 +728,116 @@ __global__ __launch_bounds__(kThreads) void png_strip_kernel(PngArgs a) {
   const unsigned nblk = (n + 65534u) / 65535u;
   const unsigned long long stor_bytes = (unsigned long long)n + 5ull * nblk + 5;
   uint8_t* data = slot + 8;
-  unsigned datalen;
+  unsigned datalen = 0;
 
-  if (huff_bytes < stor_bytes) {
+  // ---- match mode LZ: matches, the greedy parse, its two codes and its size ----
+  bool use_lz = false;
+  if constexpr (kLz) {
+    unsigned short* ent2 = (unsigned short*)(L.stage + kStepTab);
+    unsigned long long extra, nm;
+    if (in_lds) lz_match(lz_dyn, md, n, (unsigned)g.rowb, Z, L.stage);
+    else lz_match((const unsigned long long*)fb, md, n, (unsigned)g.rowb, Z, L.stage);
+    lz_parse(fb, md, n, Z, ent2, ent2 + kRun, &extra, &nm);
+    extra = block_sum_u64(extra, L.red64);
+    nm = block_sum_u64(nm, L.red64);
+    for (int k = tid; k < kStepTab + (kRun + kThreads) / 2; k += kThreads) L.stage[k] = 0;
+    if (tid == 0) Z.hist[256] = 1;
+    __syncthreads();
+    if (nm) {  // uniform; without a match the strip is the literal-only block
+      huff_lengths(Z.hist, kLl, 15, Z.lens, L.hw);
+      huff_lengths(Z.dhist, kDist, 15, Z.dlens, L.hw);
+      for (int k = tid; k < kLl; k += kThreads)
+        if (Z.lens[k]) atomicMax(&Z.nl, (unsigned)k + 1);
+      if (tid < kDist && Z.dlens[tid]) atomicMax(&Z.nd, (unsigned)tid + 1);
+      __syncthreads();
+      const unsigned nl = Z.nl, nd = Z.nd;  // nl >= 257: end-of-block is used
+      for (unsigned k = tid; k < nl + nd; k += kThreads) atomicAdd(&Z.clhist[k < nl ? Z.lens[k] : Z.dlens[k - nl]], 1u);
+      __syncthreads();
+      huff_lengths(Z.clhist, kCl, 7, Z.cllens, L.hw);
+      unsigned long long zb = 0;
+      for (unsigned k = tid; k < nl + nd; k += kThreads) {
+        if (k < nl) zb += Z.cllens[Z.lens[k]] + (unsigned long long)Z.hist[k] * Z.lens[k];
+        else zb += Z.cllens[Z.dlens[k - nl]] + (unsigned long long)Z.dhist[k - nl] * Z.dlens[k - nl];
+      }
+      zb = block_sum_u64(zb, L.red64) + extra + 17 + 3 * kCl + 3;
+      const unsigned long long lz_bytes = ((zb + 7) >> 3) + 4;
+      use_lz = lz_bytes < huff_bytes && lz_bytes < stor_bytes;
+    }
+  }
+
+  if (use_lz) {
+    if constexpr (kLz) {
+      // ---- 3z: block header and code lengths, one entry per filtered byte (nothing for a byte
+      // inside a match), end-of-block and the empty stored block's 3 bits
+      huff_codes(Z.lens, kLl, Z.codes, L.hw);
+      huff_codes(Z.dlens, kDist, Z.dcodes, L.hw);
+      huff_codes(Z.cllens, kCl, Z.clcodes, L.hw);
+      const unsigned nl = Z.nl, nd = Z.nd;
+      const unsigned P = first ? 1u : 0u;
+      unsigned carry = 0, outw = 0;
+      unsigned* dataw = (unsigned*)data;
+      unsigned long long sym[kRun];
+      static_assert(2 + kCl + kLl + kDist <= kChunk, "the header is one chunk");
+#pragma unroll
+      for (int k = 0; k < kRun; ++k) {
+        const unsigned j = (unsigned)tid * kRun + (unsigned)k;
+        unsigned e = 0;
+        if (j < P) e = 0x0178u | (16u << 24);
+        else if (j == P) e = (2u << 1) | ((nl - 257u) << 3) | ((nd - 1u) << 8) | (15u << 13) | (17u << 24);
+        else if (j < P + 1 + kCl) e = Z.cllens[kClOrder[j - P - 1]] | (3u << 24);
+        else if (j < P + 1 + kCl + nl) e = Z.clcodes[Z.lens[j - P - 1 - kCl]];
+        else if (j < P + 1 + kCl + nl + nd) e = Z.clcodes[Z.dlens[j - P - 1 - kCl - nl]];
+        sym[k] = (unsigned long long)(e & 0xffffffu) | (unsigned long long)(e >> 24) << 56;
+      }
+      emit_chunk(sym, L, dataw, carry, outw);
+      for (unsigned base = 0; base < n; base += kChunk) {
+#pragma unroll
+        for (int k = 0; k < kRun; ++k) {
+          const unsigned i = base + (unsigned)tid * kRun + (unsigned)k;
+          unsigned long long v = 0;
+          const unsigned m = i < n ? md[i] : 0u;
+          if (m & kTaken) {
+            const unsigned len = m & (kTaken - 1);
+            if (len) {
+              unsigned le, de;
+              const unsigned dist = m >> 16;
+              const unsigned lc = Z.codes[len_code(len, &le)], dc = Z.dcodes[dist_code(dist, &de)];
+              unsigned c = lc >> 24;
+              v = lc & 0xffffffu;
+              v |= (unsigned long long)((len - 3) & ((1u << le) - 1)) << c;
+              c += le;
+              v |= (unsigned long long)(dc & 0xffffffu) << c;
+              c += dc >> 24;
+              v |= (unsigned long long)((dist - 1) & ((1u << de) - 1)) << c;
+              c += de;
+              v |= (unsigned long long)c << 56;
+            } else {
+              const unsigned lc = Z.codes[fb[i]];
+              v = (unsigned long long)(lc & 0xffffffu) | (unsigned long long)(lc >> 24) << 56;
+            }
+          }
+          sym[k] = v;
+        }
+        emit_chunk(sym, L, dataw, carry, outw);
+      }
+#pragma unroll
+      for (int k = 0; k < kRun; ++k) {
+        unsigned e = 0;
+        if (tid == 0 && k == 0) e = Z.codes[256];
+        if (tid == 0 && k == 1) e = (last ? 1u : 0u) | (3u << 24);
+        sym[k] = (unsigned long long)(e & 0xffffffu) | (unsigned long long)(e >> 24) << 56;
+      }
+      emit_chunk(sym, L, dataw, carry, outw);
+      const unsigned nby = (carry + 7) >> 3;
+      if (tid == 0) {
+        uint8_t* p = data + (size_t)outw * 4;
+        const unsigned cw = L.stage[0];
+        for (unsigned k = 0; k < nby; ++k) p[k] = (uint8_t)(cw >> (8 * k));
+        p[nby] = 0; p[nby + 1] = 0; p[nby + 2] = 0xFF; p[nby + 3] = 0xFF;
+      }
+      datalen = outw * 4 + nby + 4;
+    }
+  } else if (huff_bytes < stor_bytes) {
     // ---- 3: the bit stream.  Symbol space: [zlib header] block header, 19 code-length
     // lengths, 258 coded lengths, n literals, end-of-block, the empty stored block's 3 bits
     const unsigned P = first ? 1u : 0u;
@@ -649,25 +1061,28 @@ __global__ __launch_bounds__(kThreads) void png_gather_kernel(PngArgs a) {
 
 }  // namespace
 
-int png_bound(int H, int W, int rps, size_t* bytes_per_image, size_t* scratch_bytes) {
+int png_bound(int H, int W, int rps, int match, size_t* bytes_per_image, size_t* scratch_bytes) {
   PngGeom g;
-  const int rc = png_geom(H, W, rps, &g);
+  const int rc = png_geom(H, W, rps, match, &g);
   if (rc != kOk) return rc;
   if (bytes_per_image) *bytes_per_image = g.file_bound;
   if (scratch_bytes) *scratch_bytes = g.scratch_image;
   return kOk;
 }
 
-int launch_png_encode(const uint8_t* img, int B, int H, int W, int filter, int rps, uint8_t* out, size_t out_stride,
-                      long long* sizes, uint8_t* scratch, size_t scratch_bytes, hipStream_t st) {
+int launch_png_encode(const uint8_t* img, int B, int H, int W, int filter, int match, int rps, uint8_t* out,
+                      size_t out_stride, long long* sizes, uint8_t* scratch, size_t scratch_bytes, hipStream_t st) {
   PngArgs a;
-  const int rc = png_geom(H, W, rps, &a.g);
+  const int rc = png_geom(H, W, rps, match, &a.g);
   if (rc != kOk) return rc;
   if (out_stride < a.g.file_bound) return kErrArg;
   if (scratch_bytes / (size_t)B < a.g.scratch_image) return kErrWorkspace;
   if (B > 65535 || a.g.ns > 0x7fffffff / 2) return kErrShape;
   a.img = img; a.scratch = scratch; a.out = out; a.sizes = sizes; a.out_stride = out_stride; a.filter = filter;
-  png_strip_kernel<<<dim3(a.g.ns, B), kThreads, 0, st>>>(a);
+  const size_t strip_lds = align_up((size_t)a.g.rps * a.g.rowb + kFbSlack, 16);
+  a.lds_bytes = (match == kMatchLz && strip_lds <= kLzLdsMax) ? (unsigned)strip_lds : 0u;
+  if (match == kMatchLz) png_strip_kernel<true><<<dim3(a.g.ns, B), kThreads, a.lds_bytes, st>>>(a);
+  else png_strip_kernel<false><<<dim3(a.g.ns, B), kThreads, 0, st>>>(a);
   png_layout_kernel<<<dim3(B), kThreads, 0, st>>>(a);
   png_gather_kernel<<<dim3(a.g.ns, B), kThreads, 0, st>>>(a);
   UPR_CHECK_HIP(hipGetLastError());

@@ -2,7 +2,8 @@
 
 Image decode stays on the host (PIL); everything between load and save runs on
 the device.  PNG encode is the host's (PIL, the default) or, with
-png_encoder="device", the device's (upr.png: larger files, no host encode).
+png_encoder="device", the device's (upr.png: larger files, no host encode);
+png_encoder="device_lz" is the device's with LZ77 matching (smaller files).
 Intentional divergences, each a reference bug:
   * enhance_single_image accepts and ignores `adjuster=` so main.py's
     single-file branch works (reference main.py:240-249 vs simple_enhance.py:135
@@ -31,7 +32,9 @@ from utils.letterbox import letterbox_u8_image
 # (os.cpu_count() is the whole machine on a shared box; UPR_PNG_WRITERS overrides).
 # png_encoder="device": the files are encoded on the GPU (upr.png) behind the image's
 # other launches; a writer only waits for them, copies the file's bytes and writes them.
-PNG_ENCODERS = ("host", "device")
+# png_encoder="device_lz": the same with upr.png's matches="lz".
+PNG_ENCODERS = ("host", "device", "device_lz")
+_DEVICE_MATCHES = {"device": "none", "device_lz": "lz"}
 
 
 def _check_encoder(png_encoder):
@@ -110,12 +113,12 @@ def _write_device_pngs(buf, sizes, done, jobs):
         print(f"{msg}: {save_path}")
 
 
-def _emit_device(u8_images, jobs, writer):
+def _emit_device(u8_images, jobs, writer, png_encoder):
     """u8_images: u8 [B,H,W,3] (or [H,W,3]) on the device, jobs: (save_path, msg) per image.
     The encode is queued on the current stream here; the copy and the write happen on the
     writer thread (or right away without one)."""
     from upr import png
-    buf, sizes = png.encode_device(u8_images)
+    buf, sizes = png.encode_device(u8_images, matches=_DEVICE_MATCHES[png_encoder])
     done = torch.cuda.Event()
     done.record(torch.cuda.current_stream(buf.device))
     if writer is None:
@@ -129,8 +132,8 @@ def save_image(tensor, save_path, writer=None, png_encoder="host"):
     _check_encoder(png_encoder)
     if tensor.dim() == 4:
         tensor = tensor.squeeze(0)
-    if png_encoder == "device":
-        _emit_device(_to_u8_hwc_device(tensor), [(save_path, "已保存")], writer)
+    if png_encoder in _DEVICE_MATCHES:
+        _emit_device(_to_u8_hwc_device(tensor), [(save_path, "已保存")], writer, png_encoder)
     else:
         _emit(_to_u8_hwc(tensor), save_path, "已保存", writer)
 
@@ -140,12 +143,12 @@ def create_comparison(img_low, img_enhanced, save_path, writer=None, illu_map=No
     the predictor's 3-panel form [input | enhanced | illumination]
     (reference predictors/predict.py:102-140)."""
     _check_encoder(png_encoder)
-    to_u8 = _to_u8_hwc_device if png_encoder == "device" else _to_u8_hwc
+    to_u8 = _to_u8_hwc_device if png_encoder in _DEVICE_MATCHES else _to_u8_hwc
     panels = [to_u8(img_low.squeeze(0)), to_u8(img_enhanced.squeeze(0))]
     if illu_map is not None:
         panels.append(to_u8(illu_map.squeeze(0)))
-    if png_encoder == "device":  # the panel is joined on the device, along W
-        _emit_device(torch.cat(panels, dim=1), [(save_path, "已保存对比图像")], writer)
+    if png_encoder in _DEVICE_MATCHES:  # the panel is joined on the device, along W
+        _emit_device(torch.cat(panels, dim=1), [(save_path, "已保存对比图像")], writer, png_encoder)
     else:
         _emit(np.concatenate(panels, axis=1), save_path, "已保存对比图像", writer)
 
@@ -155,7 +158,8 @@ def enhance_single_image(model, image_path, output_dir, device, max_size=None, e
                          png_encoder="host"):
     """Enhance one file and write {name}_enhanced/_illumination/_comparison.png (reference :135-199).
     precision="fp16" runs the fp16 storage / fp16-MFMA graph (input cast to half).
-    png_encoder="device" encodes the three files on the GPU (same pixels, larger files)."""
+    png_encoder="device" encodes the three files on the GPU (same pixels, larger files),
+    "device_lz" does so with LZ77 matching (same pixels, smaller files than "device")."""
     _check_encoder(png_encoder)
     print(f"正在处理: {os.path.basename(image_path)}")
     img_low, _ = load_image(image_path, max_size, decoded=_decoded)

@@ -4,8 +4,9 @@
 `--mode enhance` is the hot path: every image runs the fused gfx950 graph
 (libupr.so) and the device-side enhancers.  Additions: --seed (the reference
 never seeds its random init, main.py:229), --precision {fp32,fp16} and
---png_encoder {host,device} (enhance / predict: PIL on the host, the default, or
-the device-side encoder of upr.png -- same pixels, larger files, no host encode).
+--png_encoder {host,device,device_lz} (enhance / predict: PIL on the host, the
+default, or the device-side encoder of upr.png -- same pixels, no host encode;
+device is Huffman-only and writes larger files, device_lz adds LZ77 matching).
 Intentional divergences (reference bugs): a single-file --mode enhance works
 (reference main.py:240-249 raises TypeError); --mode predict unpacks the
 model's 3-tuple (reference predict.py:163 raises ValueError).
@@ -78,8 +79,9 @@ def build_parser():
     # additions
     p.add_argument('--seed', type=int, default=None, help='seed the random init (reproducible outputs)')
     p.add_argument('--precision', choices=['fp32', 'fp16'], default='fp32')
-    p.add_argument('--png_encoder', choices=['host', 'device'], default='host',
-                   help='--mode enhance / predict: who encodes the PNGs (device: lossless, larger files)')
+    p.add_argument('--png_encoder', choices=['host', 'device', 'device_lz'], default='host',
+                   help='--mode enhance / predict: who encodes the PNGs (device: lossless, larger files; '
+                        'device_lz: the device encoder with LZ77 matching)')
     p.add_argument('--reference_dir', type=str, default=None,
                    help='--mode evaluate: ground-truth images, matched by file stem (adds psnr / ssim / mse)')
     return p

@@ -53,6 +53,8 @@ METRIC_NAMES = ("mean_brightness", "contrast", "entropy", "niqe", "saturation", 
 # include/upr.h UPR_PNG_FILTER_*: upr_png_encode's `filter`
 PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "avg": 3, "paeth": 4, "adaptive": 5}
 UPR_PNG_MAX_STRIP_BYTES = 1 << 24
+# include/upr.h UPR_PNG_MATCH_*: upr_png_encode_ex's `match`
+PNG_MATCHES = {"none": 0, "lz": 1}
 
 UPR_OP_CONV_IGEMM = 0
 UPR_OP_OTHER = 1
@@ -110,6 +112,9 @@ SIGNATURES = {
     "upr_png_bound": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
     "upr_png_encode": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
                                c_size_t, c_void_p]),
+    "upr_png_bound_ex": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
+    "upr_png_encode_ex": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
+                                  c_void_p, c_size_t, c_void_p]),
     "upr_lab_tables": (None, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "upr_retinex_decompose": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_void_p]),

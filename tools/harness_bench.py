@@ -3,7 +3,7 @@
 letterbox -> model + CLAHE-in-Lab enhancer -> device u8 -> PNG encode):
 enhance_batch_images over N synthetic low-light PNGs, images/s including IO.
 
-  python tools/harness_bench.py --n 32 --size 512 [--precision fp16] [--png_encoder device]
+  python tools/harness_bench.py --n 32 --size 512 [--precision fp16] [--png_encoder device|device_lz]
 """
 import argparse
 import contextlib
@@ -27,7 +27,7 @@ def main():
     ap.add_argument("--n", type=int, default=32)
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--precision", choices=["fp32", "fp16"], default="fp32")
-    ap.add_argument("--png_encoder", choices=["host", "device"], default="host")
+    ap.add_argument("--png_encoder", choices=["host", "device", "device_lz"], default="host")
     args = ap.parse_args()
     kw = {"png_encoder": args.png_encoder} if args.png_encoder != "host" else {}
     from enhancers.simple_enhance import enhance_batch_images

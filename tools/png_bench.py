@@ -5,7 +5,9 @@ Two sets of 32 images of 512 x 512: the harness bench's synthetic low-light nois
 (tools/harness_bench.py) and the real crop of tests/golden/g4_real_crop.npz tiled to 512 x 512
 (each image of the batch shifted by a few pixels so the files differ).
 
-  python tools/png_bench.py [--n 32] [--size 512] [--reps 50] [--out profiles/png_encode_v1.json]
+  python tools/png_bench.py [--n 32] [--size 512] [--reps 50] [--matches lz] [--out profiles/png_encode_v1.json]
+
+--matches lz measures every set with matches="lz" and, in the same run, with matches="none".
 
 Times are device events around upr.png.encode_device (its three kernels, no copy to the host),
 median of --reps calls after a warm-up.  hbm_floor_ms is (pixels read + file bytes written) over
@@ -45,20 +47,20 @@ def pil_bytes(a, **kw):
     return f.tell()
 
 
-def measure_set(name, imgs, reps, hbm_TBps, filter, rows_per_strip):
+def measure_set(name, imgs, reps, hbm_TBps, filter, rows_per_strip, matches="none"):
     from upr import png
     x = torch.from_numpy(imgs).cuda()
-    files = png.encode(x, filter=filter, rows_per_strip=rows_per_strip)
+    files = png.encode(x, filter=filter, rows_per_strip=rows_per_strip, matches=matches)
     for k in (0, len(files) - 1):  # the decoder is the check
         assert np.array_equal(np.array(Image.open(io.BytesIO(files[k]))), imgs[k]), (name, k)
     for _ in range(5):
-        png.encode_device(x, filter=filter, rows_per_strip=rows_per_strip)
+        png.encode_device(x, filter=filter, rows_per_strip=rows_per_strip, matches=matches)
     torch.cuda.synchronize()
     ms = []
     for _ in range(reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        png.encode_device(x, filter=filter, rows_per_strip=rows_per_strip)
+        png.encode_device(x, filter=filter, rows_per_strip=rows_per_strip, matches=matches)
         e1.record()
         e1.synchronize()
         ms.append(e0.elapsed_time(e1))
@@ -70,7 +72,8 @@ def measure_set(name, imgs, reps, hbm_TBps, filter, rows_per_strip):
     moved = imgs.nbytes + dev_bytes
     floor_ms = moved / (hbm_TBps * 1e12) * 1e3
     med = statistics.median(ms)
-    return {"set": name, "images": int(imgs.shape[0]), "size": int(imgs.shape[1]), "filter": filter,
+    return {"set": name, "matches": matches, "images": int(imgs.shape[0]), "size": int(imgs.shape[1]),
+            "filter": filter,
             "rows_per_strip": rows_per_strip, "encode_ms_median": med, "encode_ms_min": min(ms),
             "encode_ms_max": max(ms), "reps": reps, "images_per_s": imgs.shape[0] / (med * 1e-3),
             "pixel_bytes": int(imgs.nbytes), "device_file_bytes": int(dev_bytes),
@@ -88,6 +91,7 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--filter", default="adaptive")
     ap.add_argument("--rows_per_strip", type=int, default=16)
+    ap.add_argument("--matches", choices=["none", "lz"], default="none")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -96,10 +100,10 @@ def main():
     hbm = calib.measure(torch.device("cuda"), warm_s=0.5)["hbm_copy_TBps"]
     res = {"metric": "device PNG encode (upr.png.encode_device), device-event time per call",
            "hbm_copy_TBps": hbm,
-           "sets": [measure_set("harness_noise", harness_images(args.n, args.size), args.reps, hbm, args.filter,
-                                args.rows_per_strip),
-                    measure_set("real_crop_tiled", real_images(args.n, args.size), args.reps, hbm, args.filter,
-                                args.rows_per_strip)]}
+           "sets": [measure_set(name, imgs, args.reps, hbm, args.filter, args.rows_per_strip, m)
+                    for name, imgs in (("harness_noise", harness_images(args.n, args.size)),
+                                       ("real_crop_tiled", real_images(args.n, args.size)))
+                    for m in (("lz", "none") if args.matches == "lz" else ("none",))]}
     line = json.dumps(res)
     print(line)
     if args.out:
