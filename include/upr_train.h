@@ -525,7 +525,8 @@ int upr_t_loss_pixel_p(const float* low, const float* enh, const float* illu, co
                        float w_col, float w_spa, float w_dec, float w_smooth, int texture,
                        const UprLossParams* params, void* stream);
 /* Perceptual MSE level (F.mse_loss): acc (fp64) += sum (a-b)^2 / n; with
- * g != NULL, g = scale*2*(a-b) (scale = weight/n). */
+ * g != NULL, g = scale*2*(a-b) (scale = weight/n).  n == 0: UPR_OK, acc and g
+ * untouched (upr_t_mse16 likewise). */
 int upr_t_mse(const float* a, const float* b, size_t n, double* acc, float* g, float scale, void* stream);
 /* The same over two fp16 tensors (n % 4 == 0, 8-byte aligned; g 16-byte aligned or NULL), else
  * UPR_ERR_UNSUPPORTED: the frozen VGG's fp16-only features under autocast. */
@@ -534,7 +535,8 @@ int upr_t_mse16(const void* a16, const void* b16, size_t n, double* acc, float* 
 int upr_t_vgg_norm(const float* x, float* y, int B, int H, int W, void* stream);
 int upr_t_vgg_norm_bwd(const float* g_y, float* g_x, int B, int H, int W, void* stream);
 /* FrequencyLoss (:447-487) on complex spectra Ze, Zl (interleaved re/im,
- * [B*3][H][W]): acc[1] += sum w*(|Ze|-|Zl|)^2 with w = 1 (dist > r) / 0.5;
+ * [B*3][H][W]): acc[0] += sum w*(|Ze|-|Zl|)^2 with w = 1 (dist > r) / 0.5
+ * (the caller points acc at the slot it wants);
  * with G != NULL, G = scale*2*w*(|Ze|-|Zl|) * Ze/|Ze| (0 where |Ze| = 0). */
 int upr_t_freq(const float* Ze, const float* Zl, int BC, int H, int W, double* acc, float* G, float scale,
                void* stream);

@@ -80,8 +80,10 @@ __device__ float edge_at(const float* low, size_t base, int H, int W, int y, int
       g[dy + 1][dx + 1] = gray_at(low, base, HW, yy * W + xx);
     }
   }
+  // each tap next to its mirror tap, in gy as in gx: on a 2-sample axis the
+  // reflect pad makes the two equal and the sum cancels exactly, term by term
   const float gx = -g[0][0] + g[0][2] - 2.f * g[1][0] + 2.f * g[1][2] - g[2][0] + g[2][2];
-  const float gy = -g[0][0] - 2.f * g[0][1] - g[0][2] + g[2][0] + 2.f * g[2][1] + g[2][2];
+  const float gy = -g[0][0] + g[2][0] - 2.f * g[0][1] + 2.f * g[2][1] - g[0][2] + g[2][2];
   return sqrtf(gx * gx + gy * gy);
 }
 
@@ -312,7 +314,7 @@ __global__ __launch_bounds__(256) void texture_kernel(const float* __restrict__ 
         }
       }
       const float gx = -g[0][0] + g[0][2] - 2.f * g[1][0] + 2.f * g[1][2] - g[2][0] + g[2][2];
-      const float gy = -g[0][0] - 2.f * g[0][1] - g[0][2] + g[2][0] + 2.f * g[2][1] + g[2][2];
+      const float gy = -g[0][0] + g[2][0] - 2.f * g[0][1] + 2.f * g[2][1] - g[0][2] + g[2][2];  // as edge_at
       const float e = sqrtf(gx * gx + gy * gy);
       if (mode == 0) v[0] += (double)e;
       else v[1] += e > thr ? 1.0 : 0.0;
@@ -734,6 +736,7 @@ int upr_t_mse16(const void* a16, const void* b16, size_t n, double* acc, float* 
 
 int upr_t_mse(const float* a, const float* b, size_t n, double* acc, float* g, float scale, void* stream) {
   if (!a || !b || !acc) return UPR_ERR_ARG;
+  if (n == 0) return UPR_OK;  // the mean of nothing: acc keeps its value (0 / 0 would poison it)
   hipLaunchKernelGGL(mse_kernel, dim3(grid_for((long long)n, 256, 4096)), dim3(256), 0, ST(stream), a, b,
                      (long long)n, acc, g, scale);
   LAUNCH_CHECK();
