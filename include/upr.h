@@ -113,7 +113,13 @@ long long upr_model_forks(const UprModel* model);
  * was built (upr_pack_split_w_f32).  Env UPR_FP32_SPLIT=0, read by
  * upr_model_create, keeps the fp32 MFMA kernels everywhere; UPR_FP32_SPLIT_REGS=0
  * keeps them for the split-in-registers and weights-split-once ops,
- * UPR_FP32_SPLIT_W64=0 for the weights-split-once ops only.  The
+ * UPR_FP32_SPLIT_W64=0 for the weights-split-once ops only.  Of those, the
+ * three 64 -> 64 stride-1 convs (enc1.conv2, dec2.conv.0 / .3) run on a row-ring
+ * kernel that stages every input row once and splits it once, in LDS; the
+ * stride-2 enc1.conv1 runs on a gathered tile that re-stages its rows per tap.
+ * UPR_W64_RING=0 (read by upr_model_create; by upr_conv2d_nhwc_wsplit at every
+ * call) keeps all four on the gathered tile: the same form code (3), results
+ * that differ in rounding only.  The
  * split-in-registers ops convert each element of their LDS row ring to (hi, lo)
  * once, in place: one step before its first reader, beside the MFMAs, or at
  * the top of the step that first reads it, behind a second barrier -- each
@@ -229,14 +235,22 @@ size_t upr_pack_split_f32(const float* w, int Cout, int Cin, int kh, int kw, voi
  * residual / y [B,Ho,Wo,Cout], all fp32 NHWC; blob / blob_bytes from
  * upr_pack_split_w_f32 for the same shape (device copy).  Shapes the kernel
  * does not take, or a blob of another size, return UPR_ERR_UNSUPPORTED (never
- * another kernel).  `overflow` as for upr_conv2d_nhwc_regs.  No reference
- * counterpart. */
+ * another form).  `overflow` as for upr_conv2d_nhwc_regs.  3x3 stride-1 pad-1
+ * ops with Cin = Cout = 64, Ho >= 4, Wo >= 16 (alone, with a residual, or with a
+ * 1x1 stride-2 second segment of 32 channels and no residual) run on the
+ * row-ring kernel unless UPR_W64_RING=0 is set at the call
+ * (UPR_RING_SPLIT_LDS=2 / 3 at the call pick its top-of-step / one-step-ahead
+ * schedule); everything else, on the gathered tile.
+ * upr_conv_wsplit_ran: which kernel the calling thread's latest
+ * upr_conv2d_nhwc_wsplit ran: 0 none (it refused), 1 the gathered tile, 2 the
+ * row ring.  No reference counterpart. */
 size_t upr_pack_split_w_f32(const float* w, int Cout, int Cin, int kh, int kw, const float* w2, int C2, void* out,
                             size_t out_bytes);
 int upr_conv2d_nhwc_wsplit(const void* x, int B, int H, int W, int Cin, const void* blob, size_t blob_bytes,
                            const float* bias, int Cout, int kh, int kw, int stride, int pad, int dil,
                            const void* residual, int relu, void* y, const void* x2, int H2, int W2, int C2,
                            int stride2, unsigned* overflow, void* stream);
+int upr_conv_wsplit_ran(void);
 
 /* float -> uint8 exactly as `(x * 255).astype(np.uint8)` on float32
  * (enhancers/adaptive_params.py:142, letterbox.py:93): truncation, wrap mod

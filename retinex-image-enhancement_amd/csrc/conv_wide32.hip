@@ -754,12 +754,20 @@ __global__ __launch_bounds__(512, 4) void conv_wide32_kernel_wsplit(ConvOp op) {
   q32_epilogue<BM, BN, true>(op, acc, smem, m0, n0, M, HW);
 }
 
+static thread_local int t_wsplit_kernel = 0;
+int conv_last_wsplit_kernel() { return t_wsplit_kernel; }
+void conv_reset_wsplit_kernel() { t_wsplit_kernel = 0; }
+
 // The op in the weights-split-once form or kErrUnsupported (never another
-// kernel).  Takes NHWC stores of N % 64 == 0 channels without pool / per-image
+// form).  Takes NHWC stores of N % 64 == 0 channels without pool / per-image
 // bias, plain segments of C % 32 == 0 channels whose K steps fill Kpad exactly.
+// The 64 -> 64 stride-1 3x3 programs run on the row ring (conv_ring64.hip:
+// every input row staged once, not once per tap) unless ConvOp::w64_tile; what
+// the ring refuses runs on the gathered tile above.
 int launch_conv_wsplit(const ConvOp& op, hipStream_t st) {
   using C = Q32Cfg<256, 64>;
   static_assert(2 * C::LDS <= 160 * 1024, "LDS for two blocks per CU");
+  t_wsplit_kernel = 0;
   if (op.mma16 != 3 || !op.scale || !op.W || !op.out) return kErrUnsupported;
   if (op.nseg < 1 || op.nseg > 4 || op.B <= 0 || op.Ho <= 0 || op.Wo <= 0) return kErrUnsupported;
   if (op.store != kStoreNHWC || op.N <= 0 || op.N % 64 || op.pool || op.img_bias || op.out2 || op.out32) return kErrUnsupported;
@@ -778,6 +786,13 @@ int launch_conv_wsplit(const ConvOp& op, hipStream_t st) {
   if (steps * Q_BK != op.Kpad) return kErrUnsupported;
   const long long M = (long long)op.B * op.Ho * op.Wo;
   if (M > 0x7fffffffll / 64) return kErrUnsupported;  // 32-bit pixel * channel indexing
+  if (!op.w64_tile) {
+    const int rc = launch_conv_ring_w64(op, st);
+    if (rc != kErrUnsupported) {
+      if (rc == kOk) t_wsplit_kernel = 2;
+      return rc;
+    }
+  }
   static bool attr_set = false;
   if (!attr_set) {
     const hipError_t e = hipFuncSetAttribute((const void*)conv_wide32_kernel_wsplit<256, 64>,
@@ -787,7 +802,9 @@ int launch_conv_wsplit(const ConvOp& op, hipStream_t st) {
   }
   const int grid = (int)((M + 255) / 256) * (op.N / 64);
   hipLaunchKernelGGL((conv_wide32_kernel_wsplit<256, 64>), dim3(grid), dim3(512), C::LDS, st, op);
-  return (int)hipGetLastError();
+  const int rc = (int)hipGetLastError();
+  if (rc == kOk) t_wsplit_kernel = 1;
+  return rc;
 }
 
 }  // namespace upr

@@ -472,6 +472,9 @@ struct UprModel {
   // with split_regs on, the ops that got planes at build time (Op::w64_w: the
   // 64-wide convs at half resolution) run in that form (3), same guard word
   int split_w64 = 0;
+  // ConvOp::w64_tile of those ops (env UPR_W64_RING, read at creation: 0 -> 1,
+  // the gathered-tile kernel alone; else the 64 -> 64 ones run on the row ring)
+  int w64_tile = 0;
   std::vector<int> op_forms;
   std::mutex forms_mu;
 };
@@ -1248,6 +1251,7 @@ static int run_forward(UprModel* m, const void* x, int B, int H, int W, void* en
             ConvOp cw = c;
             cw.W = blob + o.w64_w; cw.scale = fptr(o.w64_scale);
             cw.mma16 = 3; cw.ovf = m->ovf_dev;
+            cw.ring_split = m->ring_split; cw.w64_tile = m->w64_tile;
             rc = launch_conv_wsplit(cw, st);
             if (rc == kOk) forms[oi] = 3;
           }
@@ -1477,6 +1481,12 @@ static int ring_split_env() {
   return v == 0 ? 1 : v == 2 || v == 3 ? v : 0;
 }
 
+// ConvOp::w64_tile from UPR_W64_RING as it is set now
+static int w64_tile_env() {
+  const char* e = getenv("UPR_W64_RING");
+  return e && *e && atoi(e) == 0;
+}
+
 }  // namespace upr
 
 // ===========================================================================
@@ -1525,6 +1535,8 @@ int upr_model_create(const UprTensorDesc* params, int n_params, int use_preact, 
   // at half resolution) on the fp32 MFMA kernel alone
   const char* sw = getenv("UPR_FP32_SPLIT_W64");
   m->split_w64 = !(sw && *sw && atoi(sw) == 0);
+  // UPR_W64_RING=0 keeps those ops on the gathered-tile kernel (the same form code)
+  m->w64_tile = w64_tile_env();
   int rc = build_model(m.get(), P);
   if (rc == kOk && m->split_state.load() == 1) {
     hipError_t e = hipMalloc((void**)&m->ovf_dev, 256);
@@ -1770,6 +1782,7 @@ int upr_conv2d_nhwc_wsplit(const void* x, int B, int H, int W, int Cin, const vo
                            const float* bias, int Cout, int kh, int kw, int stride, int pad, int dil,
                            const void* residual, int relu, void* y, const void* x2, int H2, int W2, int C2,
                            int stride2, unsigned* overflow, void* stream) {
+  conv_reset_wsplit_kernel();
   if (!x || !blob || !y || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return UPR_ERR_ARG;
   if (kh <= 0 || kw <= 0 || stride <= 0 || dil <= 0 || pad < 0) return UPR_ERR_ARG;
   if (x2 && (H2 <= 0 || W2 <= 0 || C2 <= 0 || stride2 <= 0)) return UPR_ERR_ARG;
@@ -1798,8 +1811,13 @@ int upr_conv2d_nhwc_wsplit(const void* x, int B, int H, int W, int Cin, const vo
   c.res2 = residual; c.res2_cs = Cout;
   c.out = y; c.out_cs = Cout; c.out_coff = 0; c.store = kStoreNHWC;
   c.mma16 = 3; c.ovf = overflow;
+  // read at the call: one process can run both kernels and both ring schedules
+  c.ring_split = ring_split_env();
+  c.w64_tile = w64_tile_env();
   return launch_conv_wsplit(c, (hipStream_t)stream);
 }
+
+int upr_conv_wsplit_ran(void) { return conv_last_wsplit_kernel(); }
 
 int upr_split_f32(const float* x, void* y, size_t npix, int C, unsigned* overflow, void* stream) {
   if (!x || !y) return UPR_ERR_ARG;

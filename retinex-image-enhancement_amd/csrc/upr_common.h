@@ -153,6 +153,11 @@ struct ConvOp {
   // barrier (UPR_RING_SPLIT_LDS=2); 3: in LDS one step ahead of the first
   // reader, beside the MFMAs, in a 5-group ring (UPR_RING_SPLIT_LDS=3)
   int ring_split;
+  // launch_conv_wsplit: 0 = the 64 -> 64 stride-1 3x3 programs run on the row
+  // ring (conv_ring64.hip) and what it refuses on the gathered tile; 1 = the
+  // tile kernel alone (env UPR_W64_RING=0).  The ring's schedule follows
+  // ring_split (2: top of the step, 3: ahead, else its default)
+  int w64_tile;
 };
 
 // 2^11 / 2^-11: the scale of the lo half of a split-fp16 value (ConvOp::split_out)
@@ -222,8 +227,16 @@ int launch_conv_regs(const ConvOp& op, hipStream_t stream);
 
 int launch_conv_ring32(const ConvOp& op, hipStream_t st);
 // an fp32 op with its weights split once (ConvOp::mma16 == 3; conv_wide32.hip):
-// kOk, or kErrUnsupported -- it never runs another kernel
+// kOk, or kErrUnsupported -- it never runs another form.  Two kernels: the row
+// ring for the ops launch_conv_ring_w64 takes (unless ConvOp::w64_tile), the
+// gathered 256 x 64 tile for the rest
 int launch_conv_wsplit(const ConvOp& op, hipStream_t st);
+// the row-ring kernel of that form alone (conv_ring64.hip): kOk or kErrUnsupported
+int launch_conv_ring_w64(const ConvOp& op, hipStream_t st);
+// the kernel the calling thread's latest launch_conv_wsplit ran: 0 = none (it
+// refused the op), 1 = the gathered tile, 2 = the row ring
+int conv_last_wsplit_kernel();
+void conv_reset_wsplit_kernel();  // an entry point that may refuse before it gets there
 // position of channel c (0..31) of a 32-deep K step within a 32-half weight
 // plane of that form: lane group g = (c % 16) / 4 holds the 8 k-slots 4g..4g+3,
 // 16+4g..16+4g+3, the channels of its two ds_read_b128 of an fp32 A row

@@ -86,6 +86,7 @@ SIGNATURES = {
     "upr_unsplit_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "upr_pack_split_f32": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),
     "upr_pack_split_w_f32": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t]),
+    "upr_conv_wsplit_ran": (c_int, []),
     "upr_conv2d_nhwc_wsplit": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_int, c_int,
                                        c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
                                        c_int, c_int, c_void_p, c_void_p]),

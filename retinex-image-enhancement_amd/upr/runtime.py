@@ -401,6 +401,13 @@ def conv2d_nhwc_wsplit(x, w_blob, cout, bias, kh, kw, stride=1, pad=0, dil=1, re
     return y
 
 
+def last_wsplit_kernel():
+    """The kernel this thread's latest conv2d_nhwc_wsplit ran: "ring" (the row
+    ring: 64 -> 64 stride-1 3x3 ops, unless UPR_W64_RING=0 at the call), "tile"
+    (the gathered 256 x 64 tile) or None (the call was refused)."""
+    return {1: "tile", 2: "ring"}.get(L.lib().upr_conv_wsplit_ran())
+
+
 def split_f32(x, overflow=None):
     """fp32 NHWC [..., C] -> split fp16 [..., 2C] = [hi | lo] (hi + lo * 2^-11 = x to ~2^-22).
 
