@@ -274,6 +274,37 @@ int upr_letterbox(const void* src, int src_kind, int H, int W, int top, int left
  * (np.clip(x, 0, 1) * 255).astype(np.uint8). */
 int upr_to_u8_hwc(const void* x, int C, int H, int W, int dtype, uint8_t* out, void* stream);
 
+/* The letterbox of a whole batch in one launch (the batched directory harness,
+ * utils/letterbox.py letterbox_u8_batch): image b is described by rec_dev[b]
+ * (an array of B records in DEVICE memory) and becomes out[b] of one
+ * [B,3,Ho,Wo] tensor.  The arithmetic is upr_letterbox's for src_kind 0 and
+ * out_kind 0; dtype UPR_F32 writes those floats (bit-identical), UPR_F16 their
+ * fp16 rounding.  Each record must satisfy what upr_letterbox checks of its
+ * arguments (top + nh <= Ho, left + nw <= Wo, tables both set or both NULL,
+ * NULL only when nh == H and nw == W): the records are not read on the host.
+ * src must be 4-byte aligned (the harness aligns every image to 16).
+ * UPR_ERR_ARG for B < 1, a NULL pointer or another dtype; nothing is launched. */
+typedef struct {
+  const uint8_t* src;      /* u8 HWC RGB, H x W, on the device */
+  const int32_t* xtab;     /* [4][nw], NULL when nw == W && nh == H */
+  const int32_t* ytab;     /* [4][nh] */
+  int32_t H, W, top, left, nh, nw;
+} upr_letterbox_rec;
+
+int upr_letterbox_batch(const upr_letterbox_rec* rec_dev, int B, int Ho, int Wo, int color,
+                        void* out /* [B,3,Ho,Wo] */, int dtype, void* stream);
+
+/* The pixels of the harness's three output files for a whole batch in one
+ * pass: x, enh [B,3,H,W] and illu [B,1,H,W] (NULL: none) of one dtype ->
+ * enh_u8 [B,H,W,3], illu_u8 [B,H,W,3] (the map replicated to RGB; NULL: not
+ * written) and cmp_u8 [B,H,cmp_panels*W,3] (NULL: not written): the panels
+ * [x | enh] (cmp_panels 2) or [x | enh | illu] (3) side by side.  Every byte is
+ * upr_to_u8_hwc's.  UPR_ERR_ARG for B < 1, NULL x / enh / enh_u8, an output
+ * that needs illu without it, cmp_panels other than 2 / 3 with cmp_u8. */
+int upr_panels_u8(const void* x, const void* enh, const void* illu /* [B,1,H,W] or NULL */, int B, int H, int W,
+                  int dtype, uint8_t* enh_u8 /* [B,H,W,3] */, uint8_t* illu_u8 /* [B,H,W,3] or NULL */,
+                  uint8_t* cmp_u8 /* [B,H,P*W,3] or NULL */, int cmp_panels /* 2 or 3 */, void* stream);
+
 /* cv2.cvtColor(..., COLOR_RGB2LAB) / (..., COLOR_LAB2RGB) on 8-bit interleaved
  * pixels (adaptive_params.py:142-145, :158-161 — the reference goes through
  * BGR, which is the same arithmetic). */

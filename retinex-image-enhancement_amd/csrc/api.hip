@@ -17,6 +17,10 @@ int launch_quantize(const void* x, uint8_t* out, size_t n, int dtype, hipStream_
 int launch_to_u8_hwc(const void* x, int C, int H, int W, int dtype, uint8_t* out, hipStream_t st);
 int launch_letterbox(const void* src, int src_kind, int H, int W, int top, int left, int nh, int nw, int Ho, int Wo,
                      const int* xtab, const int* ytab, int color, void* out, int out_kind, hipStream_t st);
+int launch_letterbox_batch(const upr_letterbox_rec* recs, int B, int Ho, int Wo, int color, void* out, int dtype,
+                           hipStream_t st);
+int launch_panels_u8(const void* x, const void* enh, const void* illu, int B, int H, int W, int dtype, uint8_t* enh_u8,
+                     uint8_t* illu_u8, uint8_t* cmp_u8, int P, hipStream_t st);
 int launch_gray_hist(const void* img, int* hist, int B, int H, int W, int dtype, hipStream_t st);
 int launch_multiscale(const void* x, const void* enh, void* out, double* sums, double* factor, int B, int H, int W,
                       int dtype, hipStream_t st);
@@ -63,6 +67,22 @@ int upr_to_u8_hwc(const void* x, int C, int H, int W, int dtype, uint8_t* out, v
   if (!x || !out || !dtype_ok(dtype) || (C != 1 && C != 3)) return UPR_ERR_ARG;
   if (H <= 0 || W <= 0) return UPR_ERR_SHAPE;
   return launch_to_u8_hwc(x, C, H, W, dtype, out, (hipStream_t)stream);
+}
+
+int upr_letterbox_batch(const upr_letterbox_rec* rec_dev, int B, int Ho, int Wo, int color, void* out, int dtype,
+                        void* stream) {
+  if (!rec_dev || !out || B < 1 || !dtype_ok(dtype)) return UPR_ERR_ARG;
+  if (Ho <= 0 || Wo <= 0 || B > 65535) return UPR_ERR_SHAPE;
+  return launch_letterbox_batch(rec_dev, B, Ho, Wo, color, out, dtype, (hipStream_t)stream);
+}
+
+int upr_panels_u8(const void* x, const void* enh, const void* illu, int B, int H, int W, int dtype, uint8_t* enh_u8,
+                  uint8_t* illu_u8, uint8_t* cmp_u8, int cmp_panels, void* stream) {
+  if (!x || !enh || !enh_u8 || B < 1 || !dtype_ok(dtype)) return UPR_ERR_ARG;
+  if (illu_u8 && !illu) return UPR_ERR_ARG;
+  if (cmp_u8 && ((cmp_panels != 2 && cmp_panels != 3) || (cmp_panels == 3 && !illu))) return UPR_ERR_ARG;
+  if (H <= 0 || W <= 0 || B > 65535) return UPR_ERR_SHAPE;
+  return launch_panels_u8(x, enh, illu, B, H, W, dtype, enh_u8, illu_u8, cmp_u8, cmp_panels, (hipStream_t)stream);
 }
 
 int upr_rgb2lab_u8(const uint8_t* rgb, uint8_t* lab, size_t npix, void* stream) {

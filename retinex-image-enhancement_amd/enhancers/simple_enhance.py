@@ -10,9 +10,15 @@ Intentional divergences, each a reference bug:
     raises TypeError);
   * enhance_batch_images takes optional use_preact/use_aspp/seed (defaults keep
     the reference behaviour: UP_Retinex() defaults, unseeded init).
+enhance_batch_images(batch_size > 1) and main.py --infer_batch run the batched
+directory path (run_batched): files grouped by letterboxed shape (plan_batches),
+one upload + upr_letterbox_batch, one forward, one CLAHE, one upr_panels_u8 and
+three batched PNG encodes per batch, two batches in flight.
 """
 import os
+from collections import deque
 from concurrent.futures import ThreadPoolExecutor
+import threading
 import time
 
 import numpy as np
@@ -23,7 +29,7 @@ from models.model import UP_Retinex
 from enhancers.adaptive_params import AdaptiveParameterAdjuster
 from enhancers.multi_scale import MultiScaleEnhancer
 from enhancers.content_aware import ContentAwareEnhancer
-from utils.letterbox import letterbox_u8_image
+from utils.letterbox import letterbox_shape, letterbox_u8_batch, letterbox_u8_image
 
 # Writer threads running beside the GPU; 3 files per image.
 # png_encoder="host": each writer runs PIL's PNG encoder (it releases the GIL), ~90 /
@@ -194,10 +200,273 @@ def list_images(input_dir):
     return sorted(files)
 
 
-def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preact=True, use_aspp=True, seed=None,
-                         precision="fp32", png_encoder="host"):
-    """Enhance every image of a directory (reference :202-250)."""
+# ---------------------------------------------------------------------------
+# the batched directory path
+# ---------------------------------------------------------------------------
+MAX_OPEN_BUCKETS = 8
+# CPUs the batched path plans for (a shared machine gives a command 16, whatever os.cpu_count()
+# says): decode threads + writer threads stay within it; the 2 copier threads only wait for an
+# event and for their copies
+_BATCH_CPUS = 16
+_COPIERS = 2
+
+
+def plan_batches(shapes, batch_size):
+    """Batches of file indices for the batched path: shapes[i] is the letterboxed (H, W) of
+    file i in listing order -> list of index lists, each of one shape and at most batch_size
+    long.  One bucket is open per shape; a bucket is emitted when it holds batch_size indices,
+    the rest at the end in order of each bucket's first index.  At most MAX_OPEN_BUCKETS are
+    open: a further shape first emits the bucket with the oldest first index, short.  Every
+    index appears exactly once; pure and deterministic."""
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    open_buckets, out = {}, []
+    for i, shape in enumerate(shapes):
+        shape = tuple(shape)
+        bucket = open_buckets.get(shape)
+        if bucket is None:
+            if len(open_buckets) >= MAX_OPEN_BUCKETS:
+                oldest = min(open_buckets, key=lambda k: open_buckets[k][0])
+                out.append(open_buckets.pop(oldest))
+            bucket = open_buckets[shape] = []
+        bucket.append(i)
+        if len(bucket) == batch_size:
+            out.append(open_buckets.pop(shape))
+    out.extend(sorted(open_buckets.values(), key=lambda b: b[0]))
+    return out
+
+
+def letterboxed_shapes(image_files, max_size=None):
+    """load_image's output (H, W) of every file, from the image headers alone (nothing is decoded)."""
+    shapes = []
+    for path in image_files:
+        with Image.open(path) as im:
+            w, h = im.size
+        shapes.append(letterbox_shape((h, w), max_size if max_size is not None else (h, w), auto=True, scaleup=False))
+    return shapes
+
+
+class _StageClock:
+    """Wall-time sums per pipeline stage, over all threads, into a caller's dict (None: off)."""
+
+    def __init__(self, timings):
+        self.timings, self.lock = timings, threading.Lock()
+
+    def add(self, key, t0):
+        if self.timings is not None:
+            dt = time.perf_counter() - t0
+            with self.lock:
+                self.timings[key] = self.timings.get(key, 0.0) + dt
+
+
+_copy_local = threading.local()
+
+
+def _copy_stream(dev):
+    """A side stream per copier thread: its device-to-host copies do not queue behind the next
+    batch's launches on the main thread's stream."""
+    streams = getattr(_copy_local, "streams", None)
+    if streams is None:
+        streams = _copy_local.streams = {}
+    if dev not in streams:
+        streams[dev] = torch.cuda.Stream(dev)
+    return streams[dev]
+
+
+def _write_file(data, save_path, msg):
+    with open(save_path, "wb") as fh:
+        fh.write(data)
+    print(f"{msg}: {save_path}")
+
+
+class _ImageLines:
+    """enhance mode's closing lines of one image, printed once its last file is written."""
+
+    def __init__(self, n_files):
+        self.left, self.lock = n_files, threading.Lock()
+
+    def written(self, n):
+        with self.lock:
+            self.left -= n
+            last = self.left == 0
+        if last:
+            print("图像增强完成！")
+            print("-" * 50)
+
+
+def _write_image_files(files, clock, lines):
+    t0 = time.perf_counter()
+    for data, save_path, msg, encoded in files:
+        (_write_file if encoded else _write_png)(data, save_path, msg)
+    if lines is not None:
+        lines.written(len(files))
+    clock.add("copy_write", t0)
+
+
+def _finish_batch(job, writer, clock, image_lines):
+    """Copier thread: wait for the batch's event, bring its files (device encoder) or pixels
+    (host encoder) to pinned host memory in one copy per tensor, hand the per-image writes to
+    the writer threads.  Returns their futures."""
+    done, dev, outputs, paths = job
+    t0 = time.perf_counter()
+    done.synchronize()
+    clock.add("event_wait", t0)
+    t0 = time.perf_counter()
+    stream = _copy_stream(dev)
+    host = []
+    with torch.cuda.stream(stream):
+        for msg, u8, buf, sizes in outputs:
+            src = buf if buf is not None else u8
+            h = torch.empty(src.shape, dtype=torch.uint8, pin_memory=True)
+            h.copy_(src, non_blocking=True)
+            hs = None
+            if sizes is not None:
+                hs = torch.empty(sizes.shape, dtype=torch.int64, pin_memory=True)
+                hs.copy_(sizes, non_blocking=True)
+            host.append((msg, h, hs))
+    stream.synchronize()
+    del outputs, job  # (the device tensors are released after the copies, never before)
+    clock.add("copy_write", t0)
+    futs = []
+    for b, per_kind in enumerate(paths):
+        files = []
+        for (msg, h, hs), save_path in zip(host, per_kind):
+            a = h.numpy()
+            if hs is not None:
+                files.append((memoryview(a[b, :int(hs[b])]), save_path, msg, True))
+            else:
+                files.append((a[b], save_path, msg, False))
+        lines = _ImageLines(len(files)) if image_lines else None
+        if host[0][2] is not None:  # encoded already: one task writes the image's files
+            futs.append(writer.submit(_write_image_files, files, clock, lines))
+        else:  # PIL encodes: one task per file
+            futs += [writer.submit(_write_image_files, [f], clock, lines) for f in files]
+    return futs
+
+
+def run_batched(model, image_files, output_dir, device, *, max_size=None, precision="fp32", png_encoder="host",
+                batch_size=8, decode_threads=4, clahe=True, comparison=2, image_lines=True, timings=None):
+    """The batched directory pipeline behind enhance_batch_images(batch_size > 1) and
+    main.py --mode predict --infer_batch: for every file {name}_enhanced.png,
+    {name}_illumination.png and, unless comparison is None, {name}_comparison.png
+    ([input | enhanced] for comparison=2, [input | enhanced | illumination] for 3).
+    clahe: apply_clahe_enhancement after the forward (the enhance mode's default path);
+    image_lines: print enhance mode's per-image lines (predict mode prints the saves only).
+
+    plan_batches groups the files by letterboxed shape.  decode_threads PIL threads decode up
+    to two batches ahead.  Per batch the main thread queues, on its current stream: one
+    staging copy + upr_letterbox_batch in the model's dtype, the forward, CLAHE,
+    upr_panels_u8, with a device encoder three batched PNG encodes, and an event.  A copier
+    thread waits for the event, copies the files (or, host encoder, the pixels) to pinned
+    memory on a side stream and hands the writes (host encoder: PIL encodes) to the writer
+    threads.  Two batches are in flight: batch n is queued before batch n - 1 is written and
+    after batch n - 2 is.  Every batch has its own staging and output tensors (the allocators
+    keep a buffer until the work queued on it has drained); only the PNG scratch is reused,
+    stream-ordered.  timings: an optional dict that receives wall-time sums per stage
+    (decode_wait, launch, drain_wait on the main thread; event_wait, copy_write over the
+    copier and writer threads)."""
+    from upr import png, runtime
     _check_encoder(png_encoder)
+    if comparison not in (None, 2, 3):
+        raise ValueError(f"comparison must be None, 2 or 3, got {comparison!r}")
+    batches = plan_batches(letterboxed_shapes(image_files, max_size), batch_size)
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    dtype = torch.float16 if precision == "fp16" else torch.float32
+    adjuster = AdaptiveParameterAdjuster()
+    clock = _StageClock(timings)
+    decode_threads = max(1, min(int(decode_threads), _BATCH_CPUS - 1))
+    writers = max(1, min(_WRITERS, _BATCH_CPUS - decode_threads))
+    os.makedirs(output_dir, exist_ok=True)
+    kinds = [("enhanced", "已保存"), ("illumination", "已保存")] + ([("comparison", "已保存对比图像")] if comparison else [])
+    n_files, count = len(image_files), 0
+
+    def launch(idxs, images):
+        x = letterbox_u8_batch(images, max_size if max_size is not None else images[0].shape[:2], auto=True,
+                               scaleup=False, device=dev, dtype=dtype)
+        with torch.no_grad():
+            enh, _, illu = model(x)
+        if clahe:
+            enh = adjuster.apply_clahe_enhancement(enh)
+        u8s = runtime.panels_u8(x, enh, illu, comparison)
+        outputs = []
+        for (_, msg), u8 in zip(kinds, u8s):
+            if png_encoder in _DEVICE_MATCHES:
+                buf, sizes = png.encode_device(u8, matches=_DEVICE_MATCHES[png_encoder])
+                outputs.append((msg, None, buf, sizes))
+            else:
+                outputs.append((msg, u8, None, None))
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(dev))
+        names = [os.path.splitext(os.path.basename(image_files[i]))[0] for i in idxs]
+        paths = [[os.path.join(output_dir, f"{n}_{kind}.png") for kind, _ in kinds] for n in names]
+        return done, dev, outputs, paths
+
+    def drain(fut):
+        t0 = time.perf_counter()
+        for w in fut.result():
+            w.result()
+        clock.add("drain_wait", t0)
+
+    pool = ThreadPoolExecutor(max_workers=decode_threads)
+    copier = ThreadPoolExecutor(max_workers=_COPIERS)
+    writer = ThreadPoolExecutor(max_workers=writers)
+    try:
+        todo, decoding, inflight = iter(batches), deque(), deque()
+
+        def decode_ahead():  # the threads work up to two batches ahead of the launches
+            while len(decoding) < 2:
+                idxs = next(todo, None)
+                if idxs is None:
+                    return
+                decoding.append((idxs, [pool.submit(_decode, image_files[i]) for i in idxs]))
+
+        decode_ahead()
+        while decoding:
+            idxs, futs = decoding.popleft()
+            decode_ahead()
+            t0 = time.perf_counter()
+            images = [f.result()[0] for f in futs]
+            clock.add("decode_wait", t0)
+            while len(inflight) >= 2:
+                drain(inflight.popleft())
+            t0 = time.perf_counter()
+            job = launch(idxs, images)
+            dt = time.perf_counter() - t0
+            clock.add("launch", t0)
+            for i in idxs if image_lines else ():
+                count += 1
+                print(f"[{count}/{n_files}]")
+                print(f"正在处理: {os.path.basename(image_files[i])}")
+                print(f"增强耗时: {dt / len(idxs):.4f}s")  # the image's share of queueing its batch (no synchronise)
+            inflight.append(copier.submit(_finish_batch, job, writer, clock, image_lines))
+            del job
+        while inflight:
+            drain(inflight.popleft())
+    finally:
+        pool.shutdown(wait=True, cancel_futures=True)
+        copier.shutdown(wait=True)
+        writer.shutdown(wait=True)
+
+
+def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preact=True, use_aspp=True, seed=None,
+                         precision="fp32", png_encoder="host", batch_size=1, decode_threads=4, timings=None):
+    """Enhance every image of a directory (reference :202-250).
+
+    batch_size=1 (the default) is the reference's one-image-at-a-time loop with a decode
+    prefetch and threaded PNG writes.  batch_size > 1 runs the batched path (run_batched;
+    decode_threads PIL threads): the same three files per image under the same names and the
+    same log lines per image, but the lines come in the order the batches and the writer
+    threads produce them, not in listing order (files are grouped by letterboxed shape).  An
+    image's files are exactly what the model, apply_clahe_enhancement and to_u8_hwc give for
+    the batch tensor the image was placed in (measured on the GPU, no output byte depended on
+    that batch: DESIGN.md 4.5).  timings: see run_batched (batched path only)."""
+    _check_encoder(png_encoder)
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
     print("正在加载模型...")
     if seed is not None:
         torch.manual_seed(seed)
@@ -209,6 +478,13 @@ def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preac
     print(f"找到 {len(image_files)} 个图像文件")
     print("=" * 50)
     total = 0.0
+    if batch_size > 1:
+        t0 = time.time()
+        run_batched(model, image_files, output_dir, device, max_size=max_size, precision=precision,
+                    png_encoder=png_encoder, batch_size=batch_size, decode_threads=decode_threads, clahe=True,
+                    comparison=2, timings=timings)
+        total = time.time() - t0
+        return _print_totals(len(image_files), total)
     # host pipeline around the device work: the next file is decoded on a
     # prefetch thread and the PNG encodes run on writer threads while the GPU
     # enhances the current image (the reference does all three serially)
@@ -224,8 +500,12 @@ def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preac
                                  _writer=writer, png_encoder=png_encoder)
             total += time.time() - t0
             print("-" * 50)
+    _print_totals(len(image_files), total)
+
+
+def _print_totals(n, total):
     print("=" * 50)
-    print(f"总共处理了 {len(image_files)} 张图像")
+    print(f"总共处理了 {n} 张图像")
     print(f"总耗时: {total:.2f}s")
-    print(f"平均每张图像耗时: {total / len(image_files):.4f}s")
+    print(f"平均每张图像耗时: {total / n:.4f}s")
     print("=" * 50)

@@ -10,6 +10,8 @@ device is Huffman-only and writes larger files, device_lz adds LZ77 matching).
 Intentional divergences (reference bugs): a single-file --mode enhance works
 (reference main.py:240-249 raises TypeError); --mode predict unpacks the
 model's 3-tuple (reference predict.py:163 raises ValueError).
+--infer_batch N (an addition, default 1) runs --mode enhance / predict on a
+directory N images at a time (enhancers/simple_enhance.py run_batched).
 --mode train runs trainers.train.train(args): images of --train_dir are decoded
 on host threads, letterboxed and augmented on the device (datasets/dataset.py),
 and every step runs on the HIP path (train_step, losses/loss.py TotalLoss,
@@ -33,7 +35,7 @@ if _HERE not in sys.path:
 
 from models.model import UP_Retinex  # noqa: E402
 from enhancers.simple_enhance import (enhance_single_image, enhance_batch_images, list_images,  # noqa: E402
-                                      load_image, save_image, create_comparison)
+                                      load_image, save_image, create_comparison, run_batched)
 from enhancers.adaptive_params import AdaptiveParameterAdjuster  # noqa: E402
 
 
@@ -82,6 +84,10 @@ def build_parser():
     p.add_argument('--png_encoder', choices=['host', 'device', 'device_lz'], default='host',
                    help='--mode enhance / predict: who encodes the PNGs (device: lossless, larger files; '
                         'device_lz: the device encoder with LZ77 matching)')
+    p.add_argument('--infer_batch', type=int, default=1,
+                   help='--mode enhance / predict on a directory: images per batch (1: one image at a time; '
+                        '> 1: the batched path, files grouped by letterboxed shape, --num_workers decode threads; '
+                        'a single-file input ignores it)')
     p.add_argument('--reference_dir', type=str, default=None,
                    help='--mode evaluate: ground-truth images, matched by file stem (adds psnr / ssim / mse)')
     return p
@@ -216,8 +222,13 @@ def main(argv=None):
         if files is None:
             print(f"错误: 输入路径 '{args.input_path}' 不存在")
             return
-        for f in files:
-            _predict_one(model, f, args)
+        if p.is_dir() and args.infer_batch > 1:
+            run_batched(model, files, args.output_dir, args.device, max_size=args.max_size, precision=args.precision,
+                        png_encoder=args.png_encoder, batch_size=args.infer_batch, decode_threads=args.num_workers,
+                        clahe=False, comparison=None if args.no_comparison else 3, image_lines=False)
+        else:
+            for f in files:
+                _predict_one(model, f, args)
         print("推理完成，结果已保存到:", args.output_dir)
         return
     # enhance
@@ -233,7 +244,8 @@ def main(argv=None):
         # reference: enhance_batch_images builds UP_Retinex() with its defaults (preact + ASPP)
         enhance_batch_images(input_dir=str(p), output_dir=args.output_dir, device=args.device,
                              max_size=args.max_size, seed=args.seed, precision=args.precision,
-                             png_encoder=args.png_encoder)
+                             png_encoder=args.png_encoder, batch_size=args.infer_batch,
+                             decode_threads=args.num_workers)
     else:
         print(f"错误: 输入路径 '{args.input_path}' 不存在")
         return

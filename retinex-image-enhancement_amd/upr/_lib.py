@@ -40,6 +40,13 @@ class UprOpStat(ctypes.Structure):
                 ("bytes", ctypes.c_double)]
 
 
+class UprLetterboxRec(ctypes.Structure):
+    """include/upr.h upr_letterbox_rec (48 bytes)."""
+    _fields_ = [("src", ctypes.c_void_p), ("xtab", ctypes.c_void_p), ("ytab", ctypes.c_void_p),
+                ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("top", ctypes.c_int32), ("left", ctypes.c_int32),
+                ("nh", ctypes.c_int32), ("nw", ctypes.c_int32)]
+
+
 class UprOpForm(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 64),
                 ("form", ctypes.c_int)]
@@ -94,6 +101,9 @@ SIGNATURES = {
     "upr_letterbox": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                               c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "upr_to_u8_hwc": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "upr_letterbox_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "upr_panels_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                              c_int, c_void_p]),
     "upr_rgb2lab_u8": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "upr_lab2rgb_u8": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "upr_clahe_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p]),

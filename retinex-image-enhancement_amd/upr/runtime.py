@@ -262,6 +262,38 @@ def to_u8_hwc(x):
     return out
 
 
+def panels_u8(x, enh, illu=None, comparison=2):
+    """The harness's output pixels for a batch in one launch: x, enh [B,3,H,W] and illu
+    [B,1,H,W] (or None) -> (enh_u8 [B,H,W,3], illu_u8 [B,H,W,3] or None, cmp_u8
+    [B,H,comparison*W,3] or None), u8 on the device.  Image b of each is to_u8_hwc's bytes;
+    the comparison is [x | enh] (comparison=2), [x | enh | illu] (3) or absent (None)."""
+    _require_device(x)
+    _require_device(enh, "enhanced")
+    if comparison not in (None, 2, 3):
+        raise ValueError(f"comparison must be None, 2 or 3, got {comparison!r}")
+    if comparison == 3 and illu is None:
+        raise ValueError("comparison=3 needs the illumination map")
+    if x.dim() != 4 or x.shape[1] != 3 or enh.shape != x.shape or enh.dtype != x.dtype or enh.device != x.device:
+        raise RuntimeError(f"expected x and enh of one shape [B, 3, H, W], dtype and device, got {tuple(x.shape)} "
+                           f"{x.dtype} and {tuple(enh.shape)} {enh.dtype}")
+    B, _, H, W = x.shape
+    if illu is not None:
+        _require_device(illu, "illumination")
+        if tuple(illu.shape) != (B, 1, H, W) or illu.dtype != x.dtype or illu.device != x.device:
+            raise RuntimeError(f"expected illu [{B}, 1, {H}, {W}] {x.dtype}, got {tuple(illu.shape)} {illu.dtype}")
+        illu = illu.contiguous()
+    x, enh = x.contiguous(), enh.contiguous()
+    dev = x.device
+    with torch.cuda.device(dev):
+        enh_u8 = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+        illu_u8 = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev) if illu is not None else None
+        cmp_u8 = torch.empty((B, H, comparison * W, 3), dtype=torch.uint8, device=dev) if comparison else None
+        rc = L.lib().upr_panels_u8(_ptr(x), _ptr(enh), _ptr(illu), B, H, W, dtype_code(x.dtype), _ptr(enh_u8),
+                                   _ptr(illu_u8), _ptr(cmp_u8), comparison or 0, _stream(dev))
+    L.check(rc, "upr_panels_u8")
+    return enh_u8, illu_u8, cmp_u8
+
+
 def rgb2lab_u8(rgb):
     """rgb: [..., 3] uint8 interleaved."""
     _require_device(rgb)

@@ -157,3 +157,75 @@ def letterbox_u8_image(img_u8_hwc, new_shape, color=(114, 114, 114), auto=True, 
     dev = device if device is not None else _device(t)
     t = t.to(dev)
     return _run(t, 0, t.shape[0], t.shape[1], new_shape, color, auto, scale_fill, scaleup, 0, out=out)
+
+
+_ALIGN = 16
+
+
+def letterbox_u8_batch(images_u8, new_shape, *, auto=True, scaleup=False, device=None, dtype=torch.float32,
+                       color=(114, 114, 114)):
+    """B decoded uint8 HWC images (any sizes that letterbox to ONE shape) -> the
+    [B,3,H',W'] batch tensor, float32 (image b bit-identical to
+    letterbox_u8_image's) or float16 (its .half()), in one upload and one launch
+    (upr_letterbox_batch).  The images and their records are laid out in one
+    pinned host buffer, every image at a 16-byte aligned offset, and go to the
+    device in one non-blocking copy on the current stream; the tap tables are
+    _device_taps'.  ValueError (naming the indices) when an image letterboxes to
+    another shape than the first."""
+    import ctypes
+    from upr import runtime
+    images = [np.ascontiguousarray(a) for a in images_u8]
+    if not images:
+        raise ValueError("letterbox_u8_batch needs at least one image")
+    for i, a in enumerate(images):
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"image {i}: expected a uint8 H x W x 3 array, got {a.dtype} {a.shape}")
+    geo = [letterbox_geometry(a.shape[:2], new_shape, auto, False, scaleup) for a in images]
+    shapes = [letterbox_shape(a.shape[:2], new_shape, auto, False, scaleup) for a in images]
+    bad = [i for i, s in enumerate(shapes) if s != shapes[0]]
+    if bad:
+        raise ValueError(f"images {bad} letterbox to {[shapes[i] for i in bad]}, image 0 to {shapes[0]}: "
+                         f"one batch takes one shape")
+    Ho, Wo = shapes[0]
+    code = runtime.dtype_code(dtype)
+    if device is not None:
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+    else:
+        dev = _device(torch.empty(0))
+    if dev.type != "cuda":
+        raise RuntimeError("letterbox runs on ROCm devices only (no CPU fallback)")
+    B = len(images)
+    offs, n = [], 0
+    for a in images:
+        offs.append(n)
+        n = (n + a.size + _ALIGN - 1) // _ALIGN * _ALIGN
+    rec_off = n
+    n += B * ctypes.sizeof(L.UprLetterboxRec)
+    host = torch.empty(n, dtype=torch.uint8, pin_memory=True)
+    hview = host.numpy()
+    with torch.cuda.device(dev):
+        stage = torch.empty(n, dtype=torch.uint8, device=dev)
+        base = stage.data_ptr()
+        recs = (L.UprLetterboxRec * B).from_buffer(hview, rec_off)
+        keep = []  # the batch's tables stay referenced until the launch: _TAPS may evict them meanwhile
+        for i, (a, ((nw, nh), _, _, (top, _b, left, _r))) in enumerate(zip(images, geo)):
+            H, W = a.shape[:2]
+            hview[offs[i]:offs[i] + a.size] = a.reshape(-1)
+            xt = yt = None
+            if (nw, nh) != (W, H):
+                xt, yt = _device_taps(nw, W, dev), _device_taps(nh, H, dev)
+                keep += [xt, yt]
+            r = recs[i]
+            r.src, r.xtab, r.ytab = base + offs[i], (xt.data_ptr() if xt is not None else None), \
+                (yt.data_ptr() if yt is not None else None)
+            r.H, r.W, r.top, r.left, r.nh, r.nw = H, W, top, left, nh, nw
+        del recs, r
+        stage.copy_(host, non_blocking=True)
+        out = torch.empty((B, 3, Ho, Wo), dtype=dtype, device=dev)
+        col = int(color[0]) | (int(color[1]) << 8) | (int(color[2]) << 16)
+        rc = L.lib().upr_letterbox_batch(base + rec_off, B, Ho, Wo, col, out.data_ptr(), code,
+                                         torch.cuda.current_stream(dev).cuda_stream)
+    L.check(rc, "upr_letterbox_batch")
+    return out

@@ -4,6 +4,11 @@ letterbox -> model + CLAHE-in-Lab enhancer -> device u8 -> PNG encode):
 enhance_batch_images over N synthetic low-light PNGs, images/s including IO.
 
   python tools/harness_bench.py --n 32 --size 512 [--precision fp16] [--png_encoder device|device_lz]
+                                [--batch_size 32 [--decode_threads 4]] [--mixed]
+
+--batch_size > 1 runs the batched path and adds its per-stage wall-time sums
+(`stage_seconds`) to the JSON; --mixed writes images of --size and of half of it,
+interleaved, so the batches are formed from two shape buckets.
 """
 import argparse
 import contextlib
@@ -22,35 +27,60 @@ import torch  # noqa: E402
 from PIL import Image  # noqa: E402
 
 
+def write_inputs(src, n, size, mixed=False):
+    os.makedirs(src)
+    rng = np.random.default_rng(0)
+    for k in range(n):
+        s = size // 2 if mixed and k % 2 else size
+        a = (rng.integers(0, 256, (s, s, 3)) * 0.35).astype(np.uint8)
+        Image.fromarray(a).save(os.path.join(src, f"img{k:03d}.png"))
+
+
+def run(src, out, n, size, precision="fp32", png_encoder="host", batch_size=1, decode_threads=4, mixed=False,
+        warm=True):
+    """One timed enhance_batch_images over the files of `src` -> the result dict."""
+    from enhancers.simple_enhance import enhance_batch_images
+    kw = {"png_encoder": png_encoder} if png_encoder != "host" else {}
+    timings = None
+    if batch_size != 1:
+        timings = {}
+        kw.update(batch_size=batch_size, decode_threads=decode_threads)
+    with contextlib.redirect_stdout(io.StringIO()):
+        if warm:  # packing, allocator pools, pinned buffers
+            enhance_batch_images(src, out + "_warm", "cuda", seed=0, precision=precision, **kw)
+        if timings is not None:
+            kw["timings"] = timings
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        enhance_batch_images(src, out, "cuda", seed=0, precision=precision, **kw)
+        torch.cuda.synchronize()
+        el = time.perf_counter() - t0
+    res = {"metric": "enhance harness images/s (decode + letterbox + UP_Retinex preact+ASPP + "
+                     "CLAHE-in-Lab + 3 PNG writes per image)", "value": n / el, "unit": "images/s",
+           "n": n, "size": size, "precision": precision, "png_encoder": png_encoder,
+           "batch_size": batch_size, "mixed": bool(mixed), "seconds": el, "files_written": len(os.listdir(out))}
+    if timings is not None:
+        res["decode_threads"] = decode_threads
+        res["stage_seconds"] = {k: round(v, 6) for k, v in sorted(timings.items())}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=32)
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--precision", choices=["fp32", "fp16"], default="fp32")
     ap.add_argument("--png_encoder", choices=["host", "device", "device_lz"], default="host")
+    ap.add_argument("--batch_size", type=int, default=1)
+    ap.add_argument("--decode_threads", type=int, default=4)
+    ap.add_argument("--mixed", action="store_true")
     args = ap.parse_args()
-    kw = {"png_encoder": args.png_encoder} if args.png_encoder != "host" else {}
-    from enhancers.simple_enhance import enhance_batch_images
     with tempfile.TemporaryDirectory(dir="/tmp") as d:
         src, out = os.path.join(d, "in"), os.path.join(d, "out")
-        os.makedirs(src)
-        rng = np.random.default_rng(0)
-        for k in range(args.n):
-            a = (rng.integers(0, 256, (args.size, args.size, 3)) * 0.35).astype(np.uint8)
-            Image.fromarray(a).save(os.path.join(src, f"img{k:03d}.png"))
-        with contextlib.redirect_stdout(io.StringIO()):
-            enhance_batch_images(src, out + "_warm", "cuda", seed=0, precision=args.precision, **kw)  # warm-up (packing)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            enhance_batch_images(src, out, "cuda", seed=0, precision=args.precision, **kw)
-            torch.cuda.synchronize()
-            el = time.perf_counter() - t0
-        n_out = len(os.listdir(out))
-    print(json.dumps({"metric": "enhance harness images/s (decode + letterbox + UP_Retinex preact+ASPP + "
-                                "CLAHE-in-Lab + 3 PNG writes per image)", "value": args.n / el, "unit": "images/s",
-                      "n": args.n, "size": args.size, "precision": args.precision, "png_encoder": args.png_encoder,
-                      "seconds": el,
-                      "files_written": n_out}))
+        write_inputs(src, args.n, args.size, args.mixed)
+        res = run(src, out, args.n, args.size, args.precision, args.png_encoder, args.batch_size,
+                  args.decode_threads, args.mixed)
+    print(json.dumps(res))
 
 
 if __name__ == "__main__":
