@@ -439,6 +439,40 @@ int upr_png_encode_ex(const uint8_t* hwc_u8, int B, int H, int W, int filter, in
 int upr_png_encode(const uint8_t* hwc_u8, int B, int H, int W, int filter, int rows_per_strip, uint8_t* out,
                    size_t out_stride, int64_t* sizes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Baseline JPEG files written entirely on the device (no reference
+ * counterpart).  Arguments as upr_png_encode: hwc_u8 is B images u8 [H,W,3];
+ * image b's complete file is written at out + b * out_stride and its length to
+ * sizes[b] (device int64).  The file: SOI, APP0 JFIF 1.01, DQT 0 (luma) and 1
+ * (chroma), SOF0 (8-bit, Y/Cb/Cr, every component 1x1: 4:4:4), the four
+ * Annex K Huffman tables (DHT DC0, AC0, DC1, AC1), DRI, SOS, the entropy-coded
+ * data, EOI.  `quality` is 1..100 and scales the Annex K quantisation tables
+ * the libjpeg way (scale = 5000 / Q below 50, else 200 - 2 Q; q = clamp((base
+ * scale + 50) / 100, 1, 255)).  A restart interval is restart_rows rows of 8x8
+ * blocks (clamped to the image; DRI's Ri = ceil(W / 8) restart_rows), RSTm (m
+ * = interval mod 8) behind every interval but the last.  H and W are padded to
+ * multiples of 8 by repeating the last row / column.  Colour conversion, the
+ * forward DCT and the quantisation are integer arithmetic, stated in
+ * the output is a function of the pixels and the arguments
+ * only.  Not built: 4:2:0 or any other subsampling, Huffman tables optimised
+ * per image, grayscale files, progressive scans.
+ * upr_jpeg_bound: the largest file of one H x W image (out_stride must be at
+ * least that) and the scratch bytes per image (upr_jpeg_encode needs B times
+ * that, 16-byte aligned).  The bound comes from the code tables: a block is at
+ * most (longest DC code, 11) + 11 + 63 ((longest AC code, 16) + 10) = 22 + 63
+ * * 26 = 1660 bits; an interval of n blocks (n = 3 ceil(W / 8) times its block
+ * rows) at most 2 ceil(1660 n / 8) + 2 bytes (doubled for the 0x00 behind
+ * every 0xFF, 2 for the marker behind it); the file UPR_JPEG_HEADER_BYTES plus
+ * its intervals: about 6.5 times the raw pixels.
+ * UPR_ERR_SHAPE, with nothing launched, when H or W > 65535, Ri > 65535 or
+ * bytes_per_image would exceed 2^31; UPR_ERR_ARG for a null pointer, B, H, W
+ * or restart_rows <= 0, a quality outside 1..100, an out_stride below
+ * bytes_per_image or a misaligned scratch; UPR_ERR_WORKSPACE for too little
+ * scratch. */
+enum { UPR_JPEG_HEADER_BYTES = 629, UPR_JPEG_MAX_BLOCK_BITS = 1660 };
+int upr_jpeg_bound(int H, int W, int restart_rows, size_t* bytes_per_image, size_t* scratch_bytes);
+int upr_jpeg_encode(const uint8_t* hwc_u8, int B, int H, int W, int quality, int restart_rows, uint8_t* out,
+                    size_t out_stride, int64_t* sizes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Host copies of the 8-bit Lab integer tables (for CPU-side verification):
  * gamma[256], cbrt[3072], yf[512], invgamma[4096] (uint16), rgb2xyz[9], xyz2rgb[9]. */
 void upr_lab_tables(uint16_t* gamma, uint16_t* cbrt, uint16_t* yf, uint16_t* invgamma, int32_t* rgb2xyz,

@@ -4,6 +4,9 @@ Image decode stays on the host (PIL); everything between load and save runs on
 the device.  PNG encode is the host's (PIL, the default) or, with
 png_encoder="device", the device's (upr.png: larger files, no host encode);
 png_encoder="device_lz" is the device's with LZ77 matching (smaller files).
+image_format="jpg" (an addition; the default "png" changes nothing) writes the
+three files as baseline JPEGs of quality jpeg_quality: PIL with the host encoder,
+upr.jpeg (4:4:4, the device's own integer DCT) with either device encoder.
 Intentional divergences, each a reference bug:
   * enhance_single_image accepts and ignores `adjuster=` so main.py's
     single-file branch works (reference main.py:240-249 vs simple_enhance.py:135
@@ -15,6 +18,7 @@ directory path (run_batched): files grouped by letterboxed shape (plan_batches),
 one upload + upr_letterbox_batch, one forward, one CLAHE, one upr_panels_u8 and
 three batched PNG encodes per batch, two batches in flight.
 """
+import functools
 import os
 from collections import deque
 from concurrent.futures import ThreadPoolExecutor
@@ -46,6 +50,16 @@ _DEVICE_MATCHES = {"device": "none", "device_lz": "lz"}
 def _check_encoder(png_encoder):
     if png_encoder not in PNG_ENCODERS:
         raise ValueError(f"png_encoder must be one of {PNG_ENCODERS}, got {png_encoder!r}")
+
+
+IMAGE_FORMATS = ("png", "jpg")
+
+
+def _check_format(image_format, jpeg_quality):
+    if image_format not in IMAGE_FORMATS:
+        raise ValueError(f"image_format must be one of {IMAGE_FORMATS}, got {image_format!r}")
+    if image_format == "jpg" and not 1 <= int(jpeg_quality) <= 100:
+        raise ValueError(f"jpeg_quality must be in 1..100, got {jpeg_quality!r}")
 
 
 def _writer_count():
@@ -100,15 +114,26 @@ def _write_png(arr, save_path, msg):
     print(f"{msg}: {save_path}")
 
 
-def _emit(arr, save_path, msg, writer):
+def _write_jpg(arr, save_path, msg, quality):
+    Image.fromarray(arr).save(save_path, format="JPEG", quality=int(quality), subsampling=0)
+    print(f"{msg}: {save_path}")
+
+
+def _pixel_writer(image_format, jpeg_quality):
+    """The host encoder of a format: f(arr, save_path, msg)."""
+    return _write_png if image_format == "png" else functools.partial(_write_jpg, quality=jpeg_quality)
+
+
+def _emit(arr, save_path, msg, writer, image_format="png", jpeg_quality=95):
+    write = _pixel_writer(image_format, jpeg_quality)
     if writer is None:
-        _write_png(arr, save_path, msg)
-    else:  # PNG encode + file write on the batch harness's writer thread
-        writer.submit(_write_png, arr, save_path, msg)
+        write(arr, save_path, msg)
+    else:  # encode + file write on the batch harness's writer thread
+        writer.submit(write, arr, save_path, msg)
 
 
 def _write_device_pngs(buf, sizes, done, jobs):
-    """Files of one upr.png.encode_device call: wait for it, copy sizes[b] bytes of image b
+    """Files of one upr.png / upr.jpeg encode_device call: wait for it, copy sizes[b] bytes of image b
     and write them (no encoding on the host)."""
     done.synchronize()
     for b, n in enumerate(sizes.tolist()):
@@ -119,12 +144,20 @@ def _write_device_pngs(buf, sizes, done, jobs):
         print(f"{msg}: {save_path}")
 
 
-def _emit_device(u8_images, jobs, writer, png_encoder):
+def _encode_device(u8_images, png_encoder, image_format, jpeg_quality):
+    """(buf, sizes) of the device encoder of a format; queued on the current stream."""
+    if image_format == "jpg":
+        from upr import jpeg
+        return jpeg.encode_device(u8_images, quality=jpeg_quality)
+    from upr import png
+    return png.encode_device(u8_images, matches=_DEVICE_MATCHES[png_encoder])
+
+
+def _emit_device(u8_images, jobs, writer, png_encoder, image_format="png", jpeg_quality=95):
     """u8_images: u8 [B,H,W,3] (or [H,W,3]) on the device, jobs: (save_path, msg) per image.
     The encode is queued on the current stream here; the copy and the write happen on the
     writer thread (or right away without one)."""
-    from upr import png
-    buf, sizes = png.encode_device(u8_images, matches=_DEVICE_MATCHES[png_encoder])
+    buf, sizes = _encode_device(u8_images, png_encoder, image_format, jpeg_quality)
     done = torch.cuda.Event()
     done.record(torch.cuda.current_stream(buf.device))
     if writer is None:
@@ -133,40 +166,48 @@ def _emit_device(u8_images, jobs, writer, png_encoder):
         writer.submit(_write_device_pngs, buf, sizes, done, jobs)
 
 
-def save_image(tensor, save_path, writer=None, png_encoder="host"):
-    """[1,C,H,W] or [C,H,W] -> PNG; 1-channel maps are replicated to RGB (reference :65-99)."""
+def save_image(tensor, save_path, writer=None, png_encoder="host", image_format="png", jpeg_quality=95):
+    """[1,C,H,W] or [C,H,W] -> PNG; 1-channel maps are replicated to RGB (reference :65-99).
+    image_format="jpg": the same pixels as a JPEG of quality jpeg_quality."""
     _check_encoder(png_encoder)
+    _check_format(image_format, jpeg_quality)
     if tensor.dim() == 4:
         tensor = tensor.squeeze(0)
     if png_encoder in _DEVICE_MATCHES:
-        _emit_device(_to_u8_hwc_device(tensor), [(save_path, "已保存")], writer, png_encoder)
+        _emit_device(_to_u8_hwc_device(tensor), [(save_path, "已保存")], writer, png_encoder, image_format,
+                     jpeg_quality)
     else:
-        _emit(_to_u8_hwc(tensor), save_path, "已保存", writer)
+        _emit(_to_u8_hwc(tensor), save_path, "已保存", writer, image_format, jpeg_quality)
 
 
-def create_comparison(img_low, img_enhanced, save_path, writer=None, illu_map=None, png_encoder="host"):
+def create_comparison(img_low, img_enhanced, save_path, writer=None, illu_map=None, png_encoder="host",
+                      image_format="png", jpeg_quality=95):
     """[input | enhanced] side by side (reference :102-132); with `illu_map`
     the predictor's 3-panel form [input | enhanced | illumination]
     (reference predictors/predict.py:102-140)."""
     _check_encoder(png_encoder)
+    _check_format(image_format, jpeg_quality)
     to_u8 = _to_u8_hwc_device if png_encoder in _DEVICE_MATCHES else _to_u8_hwc
     panels = [to_u8(img_low.squeeze(0)), to_u8(img_enhanced.squeeze(0))]
     if illu_map is not None:
         panels.append(to_u8(illu_map.squeeze(0)))
     if png_encoder in _DEVICE_MATCHES:  # the panel is joined on the device, along W
-        _emit_device(torch.cat(panels, dim=1), [(save_path, "已保存对比图像")], writer, png_encoder)
+        _emit_device(torch.cat(panels, dim=1), [(save_path, "已保存对比图像")], writer, png_encoder,
+                     image_format, jpeg_quality)
     else:
-        _emit(np.concatenate(panels, axis=1), save_path, "已保存对比图像", writer)
+        _emit(np.concatenate(panels, axis=1), save_path, "已保存对比图像", writer, image_format, jpeg_quality)
 
 
 def enhance_single_image(model, image_path, output_dir, device, max_size=None, enable_multi_scale=False,
                          enable_content_aware=False, adjuster=None, precision="fp32", _decoded=None, _writer=None,
-                         png_encoder="host"):
-    """Enhance one file and write {name}_enhanced/_illumination/_comparison.png (reference :135-199).
+                         png_encoder="host", image_format="png", jpeg_quality=95):
+    """Enhance one file and write {name}_enhanced/_illumination/_comparison.png (reference :135-199;
+    .jpg with image_format="jpg", quality jpeg_quality).
     precision="fp16" runs the fp16 storage / fp16-MFMA graph (input cast to half).
     png_encoder="device" encodes the three files on the GPU (same pixels, larger files),
     "device_lz" does so with LZ77 matching (same pixels, smaller files than "device")."""
     _check_encoder(png_encoder)
+    _check_format(image_format, jpeg_quality)
     print(f"正在处理: {os.path.basename(image_path)}")
     img_low, _ = load_image(image_path, max_size, decoded=_decoded)
     if precision == "fp16":
@@ -186,10 +227,11 @@ def enhance_single_image(model, image_path, output_dir, device, max_size=None, e
     print(f"增强耗时: {time.time() - start:.4f}s")
     os.makedirs(output_dir, exist_ok=True)
     name = os.path.splitext(os.path.basename(image_path))[0]
-    save_image(img_enhanced, os.path.join(output_dir, f"{name}_enhanced.png"), _writer, png_encoder)
-    save_image(illu_map, os.path.join(output_dir, f"{name}_illumination.png"), _writer, png_encoder)
-    create_comparison(img_low, img_enhanced, os.path.join(output_dir, f"{name}_comparison.png"), _writer,
-                      png_encoder=png_encoder)
+    fmt = dict(image_format=image_format, jpeg_quality=jpeg_quality)
+    save_image(img_enhanced, os.path.join(output_dir, f"{name}_enhanced.{image_format}"), _writer, png_encoder, **fmt)
+    save_image(illu_map, os.path.join(output_dir, f"{name}_illumination.{image_format}"), _writer, png_encoder, **fmt)
+    create_comparison(img_low, img_enhanced, os.path.join(output_dir, f"{name}_comparison.{image_format}"), _writer,
+                      png_encoder=png_encoder, **fmt)
     print("图像增强完成！")
     return img_enhanced, illu_map
 
@@ -295,19 +337,21 @@ class _ImageLines:
             print("-" * 50)
 
 
-def _write_image_files(files, clock, lines):
+def _write_image_files(files, clock, lines, write_pixels=_write_png):
     t0 = time.perf_counter()
     for data, save_path, msg, encoded in files:
-        (_write_file if encoded else _write_png)(data, save_path, msg)
+        (_write_file if encoded else write_pixels)(data, save_path, msg)
     if lines is not None:
         lines.written(len(files))
     clock.add("copy_write", t0)
 
 
-def _finish_batch(job, writer, clock, image_lines):
+def _finish_batch(job, writer, clock, image_lines, write_pixels=_write_png, trim=False):
     """Copier thread: wait for the batch's event, bring its files (device encoder) or pixels
     (host encoder) to pinned host memory in one copy per tensor, hand the per-image writes to
-    the writer threads.  Returns their futures."""
+    the writer threads.  Returns their futures.  trim (the device JPEG encoder, whose buffer is
+    sized by a bound several times the files): the sizes come first, then only the columns up
+    to the longest file."""
     done, dev, outputs, paths = job
     t0 = time.perf_counter()
     done.synchronize()
@@ -318,10 +362,15 @@ def _finish_batch(job, writer, clock, image_lines):
     with torch.cuda.stream(stream):
         for msg, u8, buf, sizes in outputs:
             src = buf if buf is not None else u8
+            hs = None
+            if sizes is not None and trim:
+                hs = torch.empty(sizes.shape, dtype=torch.int64, pin_memory=True)
+                hs.copy_(sizes, non_blocking=True)
+                stream.synchronize()
+                src = src[:, :int(hs.max())]
             h = torch.empty(src.shape, dtype=torch.uint8, pin_memory=True)
             h.copy_(src, non_blocking=True)
-            hs = None
-            if sizes is not None:
+            if sizes is not None and not trim:
                 hs = torch.empty(sizes.shape, dtype=torch.int64, pin_memory=True)
                 hs.copy_(sizes, non_blocking=True)
             host.append((msg, h, hs))
@@ -341,16 +390,18 @@ def _finish_batch(job, writer, clock, image_lines):
         if host[0][2] is not None:  # encoded already: one task writes the image's files
             futs.append(writer.submit(_write_image_files, files, clock, lines))
         else:  # PIL encodes: one task per file
-            futs += [writer.submit(_write_image_files, [f], clock, lines) for f in files]
+            futs += [writer.submit(_write_image_files, [f], clock, lines, write_pixels) for f in files]
     return futs
 
 
 def run_batched(model, image_files, output_dir, device, *, max_size=None, precision="fp32", png_encoder="host",
-                batch_size=8, decode_threads=4, clahe=True, comparison=2, image_lines=True, timings=None):
+                batch_size=8, decode_threads=4, clahe=True, comparison=2, image_lines=True, timings=None,
+                image_format="png", jpeg_quality=95):
     """The batched directory pipeline behind enhance_batch_images(batch_size > 1) and
     main.py --mode predict --infer_batch: for every file {name}_enhanced.png,
     {name}_illumination.png and, unless comparison is None, {name}_comparison.png
-    ([input | enhanced] for comparison=2, [input | enhanced | illumination] for 3).
+    ([input | enhanced] for comparison=2, [input | enhanced | illumination] for 3); .jpg files of
+    quality jpeg_quality with image_format="jpg" (host encoder: PIL, device encoders: upr.jpeg).
     clahe: apply_clahe_enhancement after the forward (the enhance mode's default path);
     image_lines: print enhance mode's per-image lines (predict mode prints the saves only).
 
@@ -366,8 +417,9 @@ def run_batched(model, image_files, output_dir, device, *, max_size=None, precis
     stream-ordered.  timings: an optional dict that receives wall-time sums per stage
     (decode_wait, launch, drain_wait on the main thread; event_wait, copy_write over the
     copier and writer threads)."""
-    from upr import png, runtime
+    from upr import runtime
     _check_encoder(png_encoder)
+    _check_format(image_format, jpeg_quality)
     if comparison not in (None, 2, 3):
         raise ValueError(f"comparison must be None, 2 or 3, got {comparison!r}")
     batches = plan_batches(letterboxed_shapes(image_files, max_size), batch_size)
@@ -394,14 +446,14 @@ def run_batched(model, image_files, output_dir, device, *, max_size=None, precis
         outputs = []
         for (_, msg), u8 in zip(kinds, u8s):
             if png_encoder in _DEVICE_MATCHES:
-                buf, sizes = png.encode_device(u8, matches=_DEVICE_MATCHES[png_encoder])
+                buf, sizes = _encode_device(u8, png_encoder, image_format, jpeg_quality)
                 outputs.append((msg, None, buf, sizes))
             else:
                 outputs.append((msg, u8, None, None))
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(dev))
         names = [os.path.splitext(os.path.basename(image_files[i]))[0] for i in idxs]
-        paths = [[os.path.join(output_dir, f"{n}_{kind}.png") for kind, _ in kinds] for n in names]
+        paths = [[os.path.join(output_dir, f"{n}_{kind}.{image_format}") for kind, _ in kinds] for n in names]
         return done, dev, outputs, paths
 
     def drain(fut):
@@ -441,7 +493,8 @@ def run_batched(model, image_files, output_dir, device, *, max_size=None, precis
                 print(f"[{count}/{n_files}]")
                 print(f"正在处理: {os.path.basename(image_files[i])}")
                 print(f"增强耗时: {dt / len(idxs):.4f}s")  # the image's share of queueing its batch (no synchronise)
-            inflight.append(copier.submit(_finish_batch, job, writer, clock, image_lines))
+            inflight.append(copier.submit(_finish_batch, job, writer, clock, image_lines,
+                                          _pixel_writer(image_format, jpeg_quality), image_format == "jpg"))
             del job
         while inflight:
             drain(inflight.popleft())
@@ -452,7 +505,8 @@ def run_batched(model, image_files, output_dir, device, *, max_size=None, precis
 
 
 def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preact=True, use_aspp=True, seed=None,
-                         precision="fp32", png_encoder="host", batch_size=1, decode_threads=4, timings=None):
+                         precision="fp32", png_encoder="host", batch_size=1, decode_threads=4, timings=None,
+                         image_format="png", jpeg_quality=95):
     """Enhance every image of a directory (reference :202-250).
 
     batch_size=1 (the default) is the reference's one-image-at-a-time loop with a decode
@@ -462,8 +516,10 @@ def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preac
     threads produce them, not in listing order (files are grouped by letterboxed shape).  An
     image's files are exactly what the model, apply_clahe_enhancement and to_u8_hwc give for
     the batch tensor the image was placed in (measured on the GPU, no output byte depended on
-    that batch: DESIGN.md 4.5).  timings: see run_batched (batched path only)."""
+    that batch: DESIGN.md 4.5).  timings: see run_batched (batched path only).  image_format="jpg"
+    writes the three files as .jpg of quality jpeg_quality."""
     _check_encoder(png_encoder)
+    _check_format(image_format, jpeg_quality)
     batch_size = int(batch_size)
     if batch_size < 1:
         raise ValueError(f"batch_size must be >= 1, got {batch_size}")
@@ -482,7 +538,7 @@ def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preac
         t0 = time.time()
         run_batched(model, image_files, output_dir, device, max_size=max_size, precision=precision,
                     png_encoder=png_encoder, batch_size=batch_size, decode_threads=decode_threads, clahe=True,
-                    comparison=2, timings=timings)
+                    comparison=2, timings=timings, image_format=image_format, jpeg_quality=jpeg_quality)
         total = time.time() - t0
         return _print_totals(len(image_files), total)
     # host pipeline around the device work: the next file is decoded on a
@@ -497,7 +553,8 @@ def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preac
             if i < len(image_files):
                 nxt = reader.submit(_decode, image_files[i])
             enhance_single_image(model, path, output_dir, device, max_size, precision=precision, _decoded=decoded,
-                                 _writer=writer, png_encoder=png_encoder)
+                                 _writer=writer, png_encoder=png_encoder, image_format=image_format,
+                                 jpeg_quality=jpeg_quality)
             total += time.time() - t0
             print("-" * 50)
     _print_totals(len(image_files), total)

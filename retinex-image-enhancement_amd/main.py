@@ -7,6 +7,9 @@ never seeds its random init, main.py:229), --precision {fp32,fp16} and
 --png_encoder {host,device,device_lz} (enhance / predict: PIL on the host, the
 default, or the device-side encoder of upr.png -- same pixels, no host encode;
 device is Huffman-only and writes larger files, device_lz adds LZ77 matching).
+--image_format {png,jpg} and --jpeg_quality Q (additions, default png / 95):
+jpg writes the enhance / predict outputs as baseline 4:4:4 JPEGs, PIL's with
+--png_encoder host, the device encoder's (upr.jpeg) with device or device_lz.
 Intentional divergences (reference bugs): a single-file --mode enhance works
 (reference main.py:240-249 raises TypeError); --mode predict unpacks the
 model's 3-tuple (reference predict.py:163 raises ValueError).
@@ -37,6 +40,13 @@ from models.model import UP_Retinex  # noqa: E402
 from enhancers.simple_enhance import (enhance_single_image, enhance_batch_images, list_images,  # noqa: E402
                                       load_image, save_image, create_comparison, run_batched)
 from enhancers.adaptive_params import AdaptiveParameterAdjuster  # noqa: E402
+
+
+def _jpeg_quality(text):
+    q = int(text)
+    if not 1 <= q <= 100:
+        raise argparse.ArgumentTypeError(f"must be in 1..100, got {text}")
+    return q
 
 
 def build_parser():
@@ -84,6 +94,11 @@ def build_parser():
     p.add_argument('--png_encoder', choices=['host', 'device', 'device_lz'], default='host',
                    help='--mode enhance / predict: who encodes the PNGs (device: lossless, larger files; '
                         'device_lz: the device encoder with LZ77 matching)')
+    p.add_argument('--image_format', choices=['png', 'jpg'], default='png',
+                   help='--mode enhance / predict: format of the output files (jpg: baseline 4:4:4 JPEG; '
+                        '--png_encoder chooses PIL or the device encoder for it as well)')
+    p.add_argument('--jpeg_quality', type=_jpeg_quality, default=95,
+                   help='--image_format jpg: quality 1..100, as PIL\'s `quality`')
     p.add_argument('--infer_batch', type=int, default=1,
                    help='--mode enhance / predict on a directory: images per batch (1: one image at a time; '
                         '> 1: the batched path, files grouped by letterboxed shape, --num_workers decode threads; '
@@ -105,6 +120,10 @@ def _place(model, args):
     return model.to(args.device).eval()
 
 
+def _output_format(args):
+    return dict(png_encoder=args.png_encoder, image_format=args.image_format, jpeg_quality=args.jpeg_quality)
+
+
 def _predict_one(model, path, args):
     """predictors/predict.py:144-191 predict_single_image: enhanced, illumination
     and the 3-panel [input | enhanced | illumination] comparison (:102-140; the
@@ -117,12 +136,11 @@ def _predict_one(model, path, args):
         enh, _, illu = model(x)
     os.makedirs(args.output_dir, exist_ok=True)
     name = os.path.splitext(os.path.basename(path))[0]
-    enc = args.png_encoder
-    save_image(enh, os.path.join(args.output_dir, f"{name}_enhanced.png"), png_encoder=enc)
-    save_image(illu, os.path.join(args.output_dir, f"{name}_illumination.png"), png_encoder=enc)
+    enc, ext = _output_format(args), args.image_format
+    save_image(enh, os.path.join(args.output_dir, f"{name}_enhanced.{ext}"), **enc)
+    save_image(illu, os.path.join(args.output_dir, f"{name}_illumination.{ext}"), **enc)
     if not args.no_comparison:
-        create_comparison(x, enh, os.path.join(args.output_dir, f"{name}_comparison.png"), illu_map=illu,
-                          png_encoder=enc)
+        create_comparison(x, enh, os.path.join(args.output_dir, f"{name}_comparison.{ext}"), illu_map=illu, **enc)
 
 
 def _reference_stems(reference_dir):
@@ -224,8 +242,8 @@ def main(argv=None):
             return
         if p.is_dir() and args.infer_batch > 1:
             run_batched(model, files, args.output_dir, args.device, max_size=args.max_size, precision=args.precision,
-                        png_encoder=args.png_encoder, batch_size=args.infer_batch, decode_threads=args.num_workers,
-                        clahe=False, comparison=None if args.no_comparison else 3, image_lines=False)
+                        batch_size=args.infer_batch, decode_threads=args.num_workers, clahe=False,
+                        comparison=None if args.no_comparison else 3, image_lines=False, **_output_format(args))
         else:
             for f in files:
                 _predict_one(model, f, args)
@@ -239,13 +257,12 @@ def main(argv=None):
         enhance_single_image(model=model, image_path=str(p), output_dir=args.output_dir, device=args.device,
                              max_size=args.max_size, adjuster=AdaptiveParameterAdjuster(),
                              enable_multi_scale=args.multi_scale, enable_content_aware=args.content_aware,
-                             precision=args.precision, png_encoder=args.png_encoder)
+                             precision=args.precision, **_output_format(args))
     elif p.is_dir():
         # reference: enhance_batch_images builds UP_Retinex() with its defaults (preact + ASPP)
         enhance_batch_images(input_dir=str(p), output_dir=args.output_dir, device=args.device,
                              max_size=args.max_size, seed=args.seed, precision=args.precision,
-                             png_encoder=args.png_encoder, batch_size=args.infer_batch,
-                             decode_threads=args.num_workers)
+                             batch_size=args.infer_batch, decode_threads=args.num_workers, **_output_format(args))
     else:
         print(f"错误: 输入路径 '{args.input_path}' 不存在")
         return

@@ -62,6 +62,9 @@ PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "avg": 3, "paeth": 4, "adaptive": 5
 UPR_PNG_MAX_STRIP_BYTES = 1 << 24
 # include/upr.h UPR_PNG_MATCH_*: upr_png_encode_ex's `match`
 PNG_MATCHES = {"none": 0, "lz": 1}
+# include/upr.h UPR_JPEG_*: the fixed parts of upr_jpeg_bound's formula
+UPR_JPEG_HEADER_BYTES = 629
+UPR_JPEG_MAX_BLOCK_BITS = 1660
 
 UPR_OP_CONV_IGEMM = 0
 UPR_OP_OTHER = 1
@@ -126,6 +129,9 @@ SIGNATURES = {
     "upr_png_bound_ex": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
     "upr_png_encode_ex": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
                                   c_void_p, c_size_t, c_void_p]),
+    "upr_jpeg_bound": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
+    "upr_jpeg_encode": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                                c_size_t, c_void_p]),
     "upr_lab_tables": (None, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "upr_retinex_decompose": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_void_p]),

@@ -5,10 +5,13 @@ enhance_batch_images over N synthetic low-light PNGs, images/s including IO.
 
   python tools/harness_bench.py --n 32 --size 512 [--precision fp16] [--png_encoder device|device_lz]
                                 [--batch_size 32 [--decode_threads 4]] [--mixed]
+                                [--image_format jpg [--jpeg_quality 95]]
 
 --batch_size > 1 runs the batched path and adds its per-stage wall-time sums
 (`stage_seconds`) to the JSON; --mixed writes images of --size and of half of it,
-interleaved, so the batches are formed from two shape buckets.
+interleaved, so the batches are formed from two shape buckets.  --image_format jpg
+writes the three output files per image as JPEGs (PIL with the host encoder, upr.jpeg
+with a device encoder) and adds the bytes written to the JSON.
 """
 import argparse
 import contextlib
@@ -37,10 +40,12 @@ def write_inputs(src, n, size, mixed=False):
 
 
 def run(src, out, n, size, precision="fp32", png_encoder="host", batch_size=1, decode_threads=4, mixed=False,
-        warm=True):
+        warm=True, image_format="png", jpeg_quality=95):
     """One timed enhance_batch_images over the files of `src` -> the result dict."""
     from enhancers.simple_enhance import enhance_batch_images
     kw = {"png_encoder": png_encoder} if png_encoder != "host" else {}
+    if image_format != "png":
+        kw.update(image_format=image_format, jpeg_quality=jpeg_quality)
     timings = None
     if batch_size != 1:
         timings = {}
@@ -58,7 +63,11 @@ def run(src, out, n, size, precision="fp32", png_encoder="host", batch_size=1, d
     res = {"metric": "enhance harness images/s (decode + letterbox + UP_Retinex preact+ASPP + "
                      "CLAHE-in-Lab + 3 PNG writes per image)", "value": n / el, "unit": "images/s",
            "n": n, "size": size, "precision": precision, "png_encoder": png_encoder,
-           "batch_size": batch_size, "mixed": bool(mixed), "seconds": el, "files_written": len(os.listdir(out))}
+           "batch_size": batch_size, "mixed": bool(mixed), "seconds": el, "files_written": len(os.listdir(out)),
+           "image_format": image_format,
+           "output_bytes": sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out))}
+    if image_format == "jpg":
+        res["jpeg_quality"] = jpeg_quality
     if timings is not None:
         res["decode_threads"] = decode_threads
         res["stage_seconds"] = {k: round(v, 6) for k, v in sorted(timings.items())}
@@ -74,12 +83,14 @@ def main():
     ap.add_argument("--batch_size", type=int, default=1)
     ap.add_argument("--decode_threads", type=int, default=4)
     ap.add_argument("--mixed", action="store_true")
+    ap.add_argument("--image_format", choices=["png", "jpg"], default="png")
+    ap.add_argument("--jpeg_quality", type=int, default=95)
     args = ap.parse_args()
     with tempfile.TemporaryDirectory(dir="/tmp") as d:
         src, out = os.path.join(d, "in"), os.path.join(d, "out")
         write_inputs(src, args.n, args.size, args.mixed)
         res = run(src, out, args.n, args.size, args.precision, args.png_encoder, args.batch_size,
-                  args.decode_threads, args.mixed)
+                  args.decode_threads, args.mixed, image_format=args.image_format, jpeg_quality=args.jpeg_quality)
     print(json.dumps(res))
 
 

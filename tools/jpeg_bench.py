@@ -1,0 +1,120 @@
+#!/usr/bin/env python3
+"""Device JPEG encoder (upr.jpeg): encode time, file size against PIL, bytes over the HBM rate,
+and the device PNG encoder's time on the same images in the same run as the yardstick.
+
+Two sets of 32 images of 512 x 512, the ones of tools/png_bench.py: the harness bench's synthetic
+low-light noise and the real crop of tests/golden/g4_real_crop.npz tiled to 512 x 512.
+
+  python tools/jpeg_bench.py [--n 32] [--size 512] [--reps 50] [--quality 95] [--restart_rows 1]
+                             [--out profiles/jpeg_encode_v1.json]
+
+Times are device events around upr.jpeg.encode_device (its three kernels, no copy to the host),
+median of --reps calls after a warm-up.  hbm_floor_ms is (pixels read + file bytes written) over
+the copy rate upr.calib measures: a floor for the format, not for this implementation.
+"""
+import argparse
+import io
+import json
+import os
+import statistics
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "retinex-image-enhancement_amd"))
+sys.path.insert(0, os.path.join(REPO, "tools"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from PIL import Image  # noqa: E402
+
+from png_bench import harness_images, real_images  # noqa: E402
+
+
+def pil_bytes(a, quality):
+    f = io.BytesIO()
+    Image.fromarray(a).save(f, format="JPEG", quality=quality, subsampling=0)
+    return f.tell()
+
+
+def event_ms(fn, reps):
+    for _ in range(5):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return ms
+
+
+def psnr(a, b):
+    return float(10 * np.log10(255.0 ** 2 / np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)))
+
+
+def measure_set(name, imgs, reps, hbm_TBps, quality, restart_rows):
+    from upr import jpeg, png
+    x = torch.from_numpy(imgs).cuda()
+    files = jpeg.encode(x, quality=quality, restart_rows=restart_rows)
+    decoded = {}
+    for k in (0, len(files) - 1):  # the decoder is the check
+        im = Image.open(io.BytesIO(files[k]))
+        assert im.mode == "RGB" and im.size == (imgs.shape[2], imgs.shape[1]), (name, k)
+        decoded[k] = np.array(im)
+    ms = event_ms(lambda: jpeg.encode_device(x, quality=quality, restart_rows=restart_rows), reps)
+    png_ms = event_ms(lambda: png.encode_device(x), reps)
+    png_lz_ms = event_ms(lambda: png.encode_device(x, matches="lz"), reps)
+    dev_bytes = sum(len(f) for f in files)
+    sample = range(0, len(imgs), max(1, len(imgs) // 4))  # PIL on a few images is enough for a ratio
+    pil = sum(pil_bytes(imgs[k], quality) for k in sample)
+    dev_sample = sum(len(files[k]) for k in sample)
+    f0 = io.BytesIO()
+    Image.fromarray(imgs[0]).save(f0, format="JPEG", quality=quality, subsampling=0)
+    moved = imgs.nbytes + dev_bytes
+    floor_ms = moved / (hbm_TBps * 1e12) * 1e3
+    med = statistics.median(ms)
+    bound, scratch = jpeg.bound(imgs.shape[1], imgs.shape[2], restart_rows)
+    return {"set": name, "images": int(imgs.shape[0]), "size": int(imgs.shape[1]), "quality": quality,
+            "restart_rows": restart_rows, "encode_ms_median": med, "encode_ms_min": min(ms), "encode_ms_max": max(ms),
+            "reps": reps, "images_per_s": imgs.shape[0] / (med * 1e-3),
+            "png_device_encode_ms_median": statistics.median(png_ms), "png_device_encode_ms_min": min(png_ms),
+            "png_device_encode_ms_max": max(png_ms), "png_device_lz_encode_ms_median": statistics.median(png_lz_ms),
+            "pixel_bytes": int(imgs.nbytes), "device_file_bytes": int(dev_bytes),
+            "device_bytes_per_image": dev_bytes / imgs.shape[0], "pil_bytes_per_image": pil / len(sample),
+            "device_over_pil": dev_sample / pil, "device_over_raw": dev_bytes / imgs.nbytes,
+            "psnr_db_image0": psnr(decoded[0], imgs[0]),
+            "pil_psnr_db_image0": psnr(np.array(Image.open(io.BytesIO(f0.getvalue()))), imgs[0]),
+            "bound_bytes_per_image": bound, "scratch_bytes_per_image": scratch,
+            "hbm_floor_ms": floor_ms, "encode_ms_over_hbm_floor": med / floor_ms}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=32)
+    ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--quality", type=int, default=95)
+    ap.add_argument("--restart_rows", type=int, default=1)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("jpeg_bench needs a ROCm device")
+    from upr import calib
+    hbm = calib.measure(torch.device("cuda"), warm_s=0.5)["hbm_copy_TBps"]
+    res = {"metric": "device JPEG encode (upr.jpeg.encode_device), device-event time per call",
+           "hbm_copy_TBps": hbm,
+           "sets": [measure_set(name, imgs, args.reps, hbm, args.quality, args.restart_rows)
+                    for name, imgs in (("harness_noise", harness_images(args.n, args.size)),
+                                       ("real_crop_tiled", real_images(args.n, args.size)))]}
+    print(json.dumps(res))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(json.dumps(res, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
