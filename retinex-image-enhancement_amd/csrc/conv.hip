@@ -387,7 +387,6 @@ static int launch_t(const ConvOp& op, hipStream_t stream) {
 
 int launch_conv_halo(const ConvOp& op, int dtype, hipStream_t st);
 int launch_conv_ring(const ConvOp& op, hipStream_t st);
-int launch_conv_ring32(const ConvOp& op, hipStream_t st);
 int launch_conv_wide32(const ConvOp& op, hipStream_t st);
 int launch_conv_t2(const ConvOp& op, int dtype, hipStream_t st);
 
@@ -418,20 +417,16 @@ int launch_conv_out32(const ConvOp& op, hipStream_t stream) {
   return launch_conv_halo(op, kF16, stream);
 }
 
-static thread_local int t_last_form = 0;
-int conv_last_form() { return t_last_form; }
-void conv_set_last_form(int form) { t_last_form = form; }
-
-int launch_conv_regs(const ConvOp& op, hipStream_t stream) {
-  t_last_form = 0;
+int launch_conv_regs(const ConvOp& op, hipStream_t stream, int* form) {
+  if (form) *form = kFormExact;
   if (op.nseg != 1 || op.B <= 0 || op.Ho <= 0 || op.Wo <= 0 || op.out32 || op.out2 || !op.seg[0].src) return kErrArg;
   ConvOp c = op;
-  c.mma16 = 2;
-  return launch_conv_ring32(c, stream);
+  c.mma16 = kMma16Only;
+  return launch_conv_ring32(c, stream, form);
 }
 
-int launch_conv(const ConvOp& op, int dtype, hipStream_t stream) {
-  t_last_form = 0;
+int launch_conv(const ConvOp& op, int dtype, hipStream_t stream, int* form) {
+  if (form) *form = kFormExact;
   if (op.nseg < 1 || op.nseg > 4 || op.B <= 0 || op.Ho <= 0 || op.Wo <= 0) return kErrArg;
   if (op.out32 || op.out_s2) return kErrArg;  // launch_conv_out32
   if (op.out2) {
@@ -465,11 +460,11 @@ int launch_conv(const ConvOp& op, int dtype, hipStream_t stream) {
       // ring with its filter in registers first (measured 2.80 -> 2.53 ms at
       // 512^2 bs 32 against the wide32 tile)
       const bool ring_first = op.nseg == 1 && op.seg[0].C == 32 && op.N == 64 && !op.res1 && !op.res2;
-      int rc = ring_first ? launch_conv_ring32(op, stream) : launch_conv_t2(op, dtype, stream);
+      int rc = ring_first ? launch_conv_ring32(op, stream, form) : launch_conv_t2(op, dtype, stream);
       if (rc != kErrUnsupported) return rc;
       rc = launch_conv_wide32(op, stream);
       if (rc != kErrUnsupported) return rc;
-      rc = launch_conv_ring32(op, stream);
+      rc = launch_conv_ring32(op, stream, form);
       if (rc != kErrUnsupported) return rc;
     }
     const int rc = launch_conv_halo(op, dtype, stream);

@@ -1686,38 +1686,39 @@ int launch_conv_ring(const ConvOp& op, hipStream_t st) {
 }
 
 // ConvOp::mma16: the split-in-registers program of the same configuration
-// where its filter is register resident, else the exact fp32 program
+// where its filter is register resident, else the exact fp32 program; *ran
+// (nullable) becomes kFormRegs when the split program was launched
 template <int MODE, int NB, int FL>
-static int ring32_form(const ConvOp& op, hipStream_t st) {
+static int ring32_form(const ConvOp& op, hipStream_t st, int* ran) {
   if constexpr (Ring32Cfg<MODE, NB, FL>::WREG) {
     if (op.mma16) {
       // ConvOp::ring_split: where the activations are split (the results are
-      // bit-equal).  0 = the form that measured faster for the program
+      // bit-equal).  kRingSplitDefault = the form that measured faster for the program
       // (DESIGN.md 4.3): converted ahead for the plain 32 -> 32 convs (+-
       // residual), at the top of the step for the head, 32 -> 64, dilation-2 and
       // x / maxpool programs
       constexpr bool AHEAD = MODE == kRingConv && NB == 32 && !(FL & (kRingDil2 | kRingXPool));
-      const int form = op.ring_split ? op.ring_split : AHEAD ? 3 : 2;
-      const int rc = form == 1   ? launch_ring32_cfg<MODE, NB, FL | kRingMma16>(op, st)
-                     : form == 2 ? launch_ring32_cfg<MODE, NB, FL | kRingMma16 | kRingLds | kRingLdsTop>(op, st)
-                                 : launch_ring32_cfg<MODE, NB, FL | kRingMma16 | kRingLds>(op, st);
-      if (rc == kOk) conv_set_last_form(2);
+      const int form = op.ring_split != kRingSplitDefault ? op.ring_split : AHEAD ? kRingSplitAhead : kRingSplitTop;
+      const int rc = form == kRingSplitTap   ? launch_ring32_cfg<MODE, NB, FL | kRingMma16>(op, st)
+                     : form == kRingSplitTop ? launch_ring32_cfg<MODE, NB, FL | kRingMma16 | kRingLds | kRingLdsTop>(op, st)
+                                             : launch_ring32_cfg<MODE, NB, FL | kRingMma16 | kRingLds>(op, st);
+      if (rc == kOk && ran) *ran = kFormRegs;
       return rc;
     }
   }
-  if (op.mma16 == 2) return kErrUnsupported;  // that form or nothing
+  if (op.mma16 == kMma16Only) return kErrUnsupported;  // that form or nothing
   return launch_ring32_cfg<MODE, NB, FL>(op, st);
 }
 
 template <int MODE, int NB, int FL>
-static int ring32_relu(const ConvOp& op, hipStream_t st) {
-  return op.relu ? ring32_form<MODE, NB, FL | kRingRelu>(op, st) : ring32_form<MODE, NB, FL>(op, st);
+static int ring32_relu(const ConvOp& op, hipStream_t st, int* ran) {
+  return op.relu ? ring32_form<MODE, NB, FL | kRingRelu>(op, st, ran) : ring32_form<MODE, NB, FL>(op, st, ran);
 }
 
 // fp32: stride-1 3x3 over 32 channels (-> 32 / 64, head), and the split
 // EnhancedFAM fusion's 3x3 parts (N 32: dilation 1 or 2, a pre-ReLU residual,
 // per-image pool sums); kErrUnsupported otherwise
-int launch_conv_ring32(const ConvOp& op, hipStream_t st) {
+int launch_conv_ring32(const ConvOp& op, hipStream_t st, int* form) {
   if (op.Ho < 4 || op.Wo < 16) return kErrUnsupported;
   const ConvSeg& s = op.seg[0];
   if (op.nseg == 3) {
@@ -1736,7 +1737,7 @@ int launch_conv_ring32(const ConvOp& op, hipStream_t st) {
     if (x1.pre != kPreNone || x2.pre != kPreMaxPool3 || x1.kbase != 288 || x2.kbase != 320 || x1.cs % 4 ||
         x1.coff % 4 || (uintptr_t)x1.src % 16)
       return kErrUnsupported;
-    return ring32_form<kRingConv, 32, kRingXPool>(op, st);
+    return ring32_form<kRingConv, 32, kRingXPool>(op, st, form);
   }
   if (op.nseg != 1) return kErrUnsupported;
   if (op.img_bias || op.scale || op.Kpad != 288 || (op.res1 && op.res2)) return kErrUnsupported;
@@ -1747,8 +1748,8 @@ int launch_conv_ring32(const ConvOp& op, hipStream_t st) {
     if (op.store != kStoreNHWC || op.N != 32 || op.res2 || !op.res1 || !op.relu || op.res1_cs % 4 || op.out_cs % 4 ||
         op.out_coff % 4)
       return kErrUnsupported;
-    return op.pool ? ring32_form<kRingConv, 32, kRingDil2 | kRingRes | kRingResPre | kRingRelu | kRingPool>(op, st)
-                   : ring32_form<kRingConv, 32, kRingDil2 | kRingRes | kRingResPre | kRingRelu>(op, st);
+    return op.pool ? ring32_form<kRingConv, 32, kRingDil2 | kRingRes | kRingResPre | kRingRelu | kRingPool>(op, st, form)
+                   : ring32_form<kRingConv, 32, kRingDil2 | kRingRes | kRingResPre | kRingRelu>(op, st, form);
   }
   if (!ring_seg_ok(s)) return kErrUnsupported;
   if (op.res1) {
@@ -1760,13 +1761,13 @@ int launch_conv_ring32(const ConvOp& op, hipStream_t st) {
   if (op.pool) return kErrUnsupported;
   if (op.store == kStoreHeadIllu) {
     if (op.N != 32 || op.res2 || op.illu_f16 || op.Wo % 8) return kErrUnsupported;
-    return ring32_form<kRingHead, 32, 0>(op, st);
+    return ring32_form<kRingHead, 32, 0>(op, st, form);
   }
   if (op.store != kStoreNHWC || op.out_cs % 4 || op.out_coff % 4) return kErrUnsupported;
   if (op.res2 && op.res2_cs % 4) return kErrUnsupported;
   const bool res = op.res2 != nullptr;
-  if (op.N == 32) return res ? ring32_relu<kRingConv, 32, kRingRes>(op, st) : ring32_relu<kRingConv, 32, 0>(op, st);
-  if (op.N == 64) return res ? ring32_relu<kRingConv, 64, kRingRes>(op, st) : ring32_relu<kRingConv, 64, 0>(op, st);
+  if (op.N == 32) return res ? ring32_relu<kRingConv, 32, kRingRes>(op, st, form) : ring32_relu<kRingConv, 32, 0>(op, st, form);
+  if (op.N == 64) return res ? ring32_relu<kRingConv, 64, kRingRes>(op, st, form) : ring32_relu<kRingConv, 64, 0>(op, st, form);
   return kErrUnsupported;
 }
 

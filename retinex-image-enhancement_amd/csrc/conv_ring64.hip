@@ -1,6 +1,6 @@
 // Row-ring streaming convolution for the fp32 64 -> 64 channel stride-1 3x3
 // convs at half resolution (dec2.conv.0, dec2.conv.3, enc1.conv2 with its
-// projecting shortcut) in the weights-split-once form (ConvOp::mma16 == 3):
+// projecting shortcut) in the weights-split-once form (ConvOp::mma16 == kMma16WSplit):
 // the structure of conv_ring.hip's fp32 ring (persistent blocks walking column
 // strips top to bottom, every input row staged once by LDS-DMA, one barrier
 // per step, constant vmcnt waits) with the arithmetic of conv_wide32.hip's
@@ -12,7 +12,7 @@
 //   (256 bytes per pixel); a ring group is 2 rows of the 34-pixel strip.
 // * Four waves = 2 rows x 2 halves of N.  A wave keeps (W_hi, W_lo) of its 32
 //   output channels for all 18 K slices in registers (288), read as they
-//   stand from model.hip pack_split_w's blob, and accumulates hi W_hi + hi
+//   stand from split_pack.hip pack_split_w's blob, and accumulates hi W_hi + hi
 //   W_lo and lo W_hi (two sets of 2 pixel groups x 2 tiles) on
 //   v_mfma_f32_16x16x32_f16: 216 MFMAs per wave and step.
 // * The activations are split once per ring element, in LDS, in the blob's
@@ -40,7 +40,7 @@ namespace upr {
 typedef float f32x4_w __attribute__((ext_vector_type(4)));
 
 enum W64Flags : int { kW64Res = 1, kW64Sc = 2, kW64Ahead = 4 };
-// the schedule ConvOp::ring_split == 0 takes
+// the schedule ConvOp::ring_split == kRingSplitDefault takes
 constexpr bool kW64DefaultAhead = true;
 
 template <int FL>
@@ -419,16 +419,16 @@ static int launch_w64_cfg(const ConvOp& op, hipStream_t st) {
 // (2: top of the step, 3: ahead; otherwise the one that measured faster)
 template <int FL>
 static int w64_form(const ConvOp& op, hipStream_t st) {
-  const bool ahead = op.ring_split == 3 || (op.ring_split != 2 && kW64DefaultAhead);
+  const bool ahead = op.ring_split == kRingSplitAhead || (op.ring_split != kRingSplitTop && kW64DefaultAhead);
   return ahead ? launch_w64_cfg<FL | kW64Ahead>(op, st) : launch_w64_cfg<FL>(op, st);
 }
 
-// A weights-split-once op (ConvOp::mma16 == 3, already validated by
+// A weights-split-once op (ConvOp::mma16 == kMma16WSplit, already validated by
 // launch_conv_wsplit) on the row ring: 3x3 stride 1 pad 1, 64 -> 64, NHWC, with
 // ReLU / a residual after the ReLU / the 1x1 stride-2 shortcut segment over 32
 // channels; kErrUnsupported for every other op
 int launch_conv_ring_w64(const ConvOp& op, hipStream_t st) {
-  if (op.mma16 != 3 || !op.scale || !op.W || !op.out) return kErrUnsupported;
+  if (op.mma16 != kMma16WSplit || !op.scale || !op.W || !op.out) return kErrUnsupported;
   if (op.Ho < 4 || op.Wo < 16 || op.N != 64 || op.store != kStoreNHWC) return kErrUnsupported;
   if (op.res1 || op.pool || op.img_bias || op.out2 || op.out32) return kErrUnsupported;
   if (op.out_cs % 4 || op.out_coff % 4 || (uintptr_t)op.out % 16 || (uintptr_t)op.W % 16) return kErrUnsupported;

@@ -39,7 +39,7 @@
 //
 // The gathered kernel also computes fp32 convs from split-fp16 operands
 // (ConvOp::split_out, upr_common.h; weights and K-segments from pack_split in
-// model.hip): same main loop over 3x the K, and SPLIT instances of the two
+// split_pack.hip): same main loop over 3x the K, and SPLIT instances of the two
 // epilogues that keep every value in fp32 until it is stored as hi / lo halves.
 #include <cstdlib>
 #include <cstring>

@@ -578,12 +578,12 @@ int launch_conv_wide32(const ConvOp& op, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------
-// Weights split once (ConvOp::mma16 == 3): the 256 x 64 gathered tile on
+// Weights split once (ConvOp::mma16 == kMma16WSplit): the 256 x 64 gathered tile on
 // v_mfma_f32_16x16x32_f16.
 //
 // A is the path above unchanged (fp32 tensors, 128-byte rows by LDS-DMA, the
 // XOR swizzle, Q32Cursor: stride 2 and a second K-segment come with it).  B
-// arrives already split: model.hip pack_split_w stores, per output channel and
+// arrives already split: split_pack.hip pack_split_w stores, per output channel and
 // 32-deep K step, 32 fp16 of W_hi = fp16(w s_n) then 32 of W_lo = fp16(w s_n -
 // W_hi) -- the 128 bytes an fp32 weight row has per step, so the DMA, its
 // swizzle and the 2 x (32 + 8) KB of LDS are those of the fp32 kernel.  Within
@@ -754,21 +754,17 @@ __global__ __launch_bounds__(512, 4) void conv_wide32_kernel_wsplit(ConvOp op) {
   q32_epilogue<BM, BN, true>(op, acc, smem, m0, n0, M, HW);
 }
 
-static thread_local int t_wsplit_kernel = 0;
-int conv_last_wsplit_kernel() { return t_wsplit_kernel; }
-void conv_reset_wsplit_kernel() { t_wsplit_kernel = 0; }
-
 // The op in the weights-split-once form or kErrUnsupported (never another
 // form).  Takes NHWC stores of N % 64 == 0 channels without pool / per-image
 // bias, plain segments of C % 32 == 0 channels whose K steps fill Kpad exactly.
 // The 64 -> 64 stride-1 3x3 programs run on the row ring (conv_ring64.hip:
 // every input row staged once, not once per tap) unless ConvOp::w64_tile; what
 // the ring refuses runs on the gathered tile above.
-int launch_conv_wsplit(const ConvOp& op, hipStream_t st) {
+int launch_conv_wsplit(const ConvOp& op, hipStream_t st, int* kernel) {
   using C = Q32Cfg<256, 64>;
   static_assert(2 * C::LDS <= 160 * 1024, "LDS for two blocks per CU");
-  t_wsplit_kernel = 0;
-  if (op.mma16 != 3 || !op.scale || !op.W || !op.out) return kErrUnsupported;
+  if (kernel) *kernel = kWSplitNone;
+  if (op.mma16 != kMma16WSplit || !op.scale || !op.W || !op.out) return kErrUnsupported;
   if (op.nseg < 1 || op.nseg > 4 || op.B <= 0 || op.Ho <= 0 || op.Wo <= 0) return kErrUnsupported;
   if (op.store != kStoreNHWC || op.N <= 0 || op.N % 64 || op.pool || op.img_bias || op.out2 || op.out32) return kErrUnsupported;
   if (op.Kpad % 32 || ((uintptr_t)op.W % 16) || ((uintptr_t)op.scale % 4)) return kErrUnsupported;
@@ -789,7 +785,7 @@ int launch_conv_wsplit(const ConvOp& op, hipStream_t st) {
   if (!op.w64_tile) {
     const int rc = launch_conv_ring_w64(op, st);
     if (rc != kErrUnsupported) {
-      if (rc == kOk) t_wsplit_kernel = 2;
+      if (rc == kOk && kernel) *kernel = kWSplitRing;
       return rc;
     }
   }
@@ -803,7 +799,7 @@ int launch_conv_wsplit(const ConvOp& op, hipStream_t st) {
   const int grid = (int)((M + 255) / 256) * (op.N / 64);
   hipLaunchKernelGGL((conv_wide32_kernel_wsplit<256, 64>), dim3(grid), dim3(512), C::LDS, st, op);
   const int rc = (int)hipGetLastError();
-  if (rc == kOk) t_wsplit_kernel = 1;
+  if (rc == kOk && kernel) *kernel = kWSplitTile;
   return rc;
 }
 

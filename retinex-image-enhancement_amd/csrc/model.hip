@@ -28,7 +28,7 @@
 #include <string>
 #include <vector>
 
-#include "upr_common.h"
+#include "split_pack.h"
 #include "../../include/upr.h"
 
 namespace upr {
@@ -123,15 +123,6 @@ static bool bn_fold(ParamSet& P, const std::string& p, int C, BNFold& out) {
 // ---------------------------------------------------------------------------
 // packed layers
 // ---------------------------------------------------------------------------
-struct SegSpec {
-  int src;       // buffer id
-  int C, coff, cs;
-  int kh, kw, stride, pad, dil;
-  int pre;
-  size_t pre_scale = 0, pre_shift = 0;  // float offsets (bytes) in blob
-  int kbase;
-};
-
 struct GemmLayer {
   int N = 0, Kpad = 0;
   size_t w = 0;                 // bytes offset of [N][Kpad] T
@@ -163,13 +154,6 @@ struct Blob {
   }
 };
 
-// A K-segment's weights before packing: w[n][c][r][s] (row-major), already
-// multiplied by any per-output-channel fold.
-struct SegWeights {
-  SegSpec spec;
-  std::vector<double> w;  // N * C * kh * kw
-};
-
 static GemmLayer pack_gemm(Blob& blob, int dtype, int N, std::vector<SegWeights>& segs,
                            const std::vector<double>& bias) {
   GemmLayer L;
@@ -194,118 +178,6 @@ static GemmLayer pack_gemm(Blob& blob, int dtype, int N, std::vector<SegWeights>
   L.w = blob.add_t(W, dtype);
   if (!bias.empty()) L.bias = blob.add_f32(bias);
   return L;
-}
-
-// ---------------------------------------------------------------------------
-// Split-fp16 form of an fp32 GEMM (the fp16 wide-tile kernel computing an fp32
-// conv, ConvOp::split_out).  Activations: v = hi + lo * 2^-11, both fp16.
-// Weights, per output channel n: a power of two s_n puts max|w| in [2^14,
-// 2^15) (exact), W_hi = fp16(w s), W_lo = fp16(w s - W_hi).  Then
-//   x w s ~= hi W_hi + lo (W_hi 2^-11) + hi W_lo        (fp32 accumulate)
-// and the dropped lo W_lo term is ~2^-22 relative.  Each logical segment (src,
-// C, taps) becomes two K-segments over the same [hi | lo] source of pixel
-// stride 2C: A reads all 2C channels against [W_hi | W_hi 2^-11] per tap, B
-// reads the C hi channels against W_lo.  scale[n] = 1 / s_n (the epilogue
-// applies it before the bias).  Scaling the weights up keeps W_lo and the lo
-// products clear of the fp16 subnormal range; storing lo scaled by 2^11 does
-// the same for the activations.
-// ---------------------------------------------------------------------------
-struct SplitPack {
-  int N = 0, Kpad = 0;
-  std::vector<_Float16> W;     // [N][Kpad]
-  std::vector<float> scale;    // [N]
-  std::vector<SegSpec> segs;   // 2 per logical segment
-};
-
-// segs: plain segments (coff 0, cs == C, C % 64 == 0, no prologue); false otherwise
-static bool pack_split(int N, const std::vector<SegWeights>& segs, SplitPack& out) {
-  if (segs.empty() || segs.size() > 2) return false;
-  out = SplitPack();
-  out.N = N;
-  int K = 0;
-  for (const auto& s : segs) {
-    const SegSpec& sp = s.spec;
-    if (sp.coff != 0 || sp.cs != sp.C || sp.C % 64 || sp.pre != kPreNone) return false;
-    const int taps = sp.kh * sp.kw;
-    SegSpec a = sp, b = sp;
-    a.C = 2 * sp.C; a.cs = 2 * sp.C; a.kbase = K;
-    K += taps * 2 * sp.C;
-    b.C = sp.C; b.cs = 2 * sp.C; b.kbase = K;
-    K += taps * sp.C;
-    out.segs.push_back(a);
-    out.segs.push_back(b);
-  }
-  out.Kpad = (int)align_up(K, 32);
-  out.W.assign((size_t)N * out.Kpad, (_Float16)0.f);
-  out.scale.assign(N, 1.f);
-  for (int n = 0; n < N; ++n) {
-    double mx = 0.0;
-    for (const auto& s : segs) {
-      const size_t per = (size_t)s.spec.C * s.spec.kh * s.spec.kw;
-      for (size_t i = 0; i < per; ++i) mx = std::max(mx, std::fabs(s.w[n * per + i]));
-    }
-    int e = 15;  // mx = f 2^e, f in [0.5, 1): mx 2^(15 - e) is in [2^14, 2^15)
-    if (mx > 0.0 && std::isfinite(mx)) (void)std::frexp(mx, &e);
-    const int sh = std::min(std::max(15 - e, -100), 100);
-    const double sc = std::ldexp(1.0, sh);
-    out.scale[n] = (float)std::ldexp(1.0, -sh);
-    for (size_t si = 0; si < segs.size(); ++si) {
-      const SegSpec& sp = segs[si].spec;
-      const int C = sp.C, kh = sp.kh, kw = sp.kw;
-      _Float16* rowA = out.W.data() + (size_t)n * out.Kpad + out.segs[2 * si].kbase;
-      _Float16* rowB = out.W.data() + (size_t)n * out.Kpad + out.segs[2 * si + 1].kbase;
-      for (int c = 0; c < C; ++c)
-        for (int r = 0; r < kh; ++r)
-          for (int q = 0; q < kw; ++q) {
-            const double w = segs[si].w[(((size_t)n * C + c) * kh + r) * kw + q] * sc;
-            const _Float16 hi = (_Float16)w;
-            const int t = r * kw + q;
-            rowA[t * 2 * C + c] = hi;
-            rowA[t * 2 * C + C + c] = (_Float16)((double)hi * (1.0 / 2048.0));
-            rowB[t * C + c] = (_Float16)(w - (double)hi);
-          }
-    }
-  }
-  return true;
-}
-
-// ---------------------------------------------------------------------------
-// Weights split once (ConvOp::mma16 == 3, conv_wide32.hip): the fp32 tensors
-// stay as they are and the kernel splits its activation fragments in
-// registers; only the weights are prepared here.  w: the packed fp32 [N][K]
-// rows of pack_gemm (K-segments of C % 32 == 0 channels, so every 32
-// consecutive k are 32 channels of one tap).  Per row n: s_n from
-// split_row_shift over the row (the rule of pack_split and of the ring's
-// prologue), W_hi = fp16(w s_n), W_lo = fp16(w s_n - W_hi), stored per 32-deep
-// K step as [W_hi(32) | W_lo(32)] in k-slot order (wsplit_kslot); scale[n] =
-// 1 / s_n.  A row takes 4 K bytes, as the fp32 row does.
-// ---------------------------------------------------------------------------
-struct SplitWPack {
-  std::vector<_Float16> W;   // [N][K / 32][2][32]
-  std::vector<float> scale;  // [N]
-};
-
-static bool pack_split_w(int N, int K, const float* w, SplitWPack& out) {
-  if (!w || N <= 0 || N % 64 || K <= 0 || K % 32) return false;
-  out.W.assign((size_t)N * K * 2, (_Float16)0.f);
-  out.scale.assign(N, 1.f);
-  for (int n = 0; n < N; ++n) {
-    const float* row = w + (size_t)n * K;
-    float mx = 0.f;
-    for (int k = 0; k < K; ++k) mx = std::max(mx, std::fabs(row[k]));
-    const int sh = split_row_shift(mx);
-    const float s = std::ldexp(1.f, sh);
-    out.scale[n] = std::ldexp(1.f, -sh);
-    _Float16* dst = out.W.data() + (size_t)n * K * 2;
-    for (int k = 0; k < K; ++k) {
-      const float ws = row[k] * s;
-      const _Float16 hi = (_Float16)ws;
-      _Float16* step = dst + (size_t)(k / 32) * 64;
-      step[wsplit_kslot(k % 32)] = hi;
-      step[32 + wsplit_kslot(k % 32)] = (_Float16)(ws - (float)hi);
-    }
-  }
-  return true;
 }
 
 // Conv weight [N][C][kh][kw] from a HostTensor, rows scaled by mul (optional).
@@ -338,14 +210,6 @@ static std::vector<double> cols(const std::vector<double>& A, int rows, int ncol
   for (int r = 0; r < rows; ++r)
     for (int c = 0; c < n; ++c) out[(size_t)r * n + c] = A[(size_t)r * ncols + c0 + c];
   return out;
-}
-
-static SegSpec seg(int src, int C, int cs, int coff, int k, int stride, int pad, int dil, int pre = kPreNone) {
-  SegSpec s;
-  s.src = src; s.C = C; s.cs = cs; s.coff = coff;
-  s.kh = k; s.kw = k; s.stride = stride; s.pad = pad; s.dil = dil;
-  s.pre = pre; s.kbase = 0;
-  return s;
 }
 
 // ---------------------------------------------------------------------------
@@ -449,32 +313,23 @@ struct UprModel {
   unsigned long long side_clock = 0;
   std::mutex sides_mu;
   std::atomic<long long> forks{0};  // forwards that ran the two-stream schedule (upr_model_forks)
-  // Split-fp16 region of the plain fp32 graph (env UPR_FP32_SPLIT, read at
-  // creation): 0 off, 1 active, 2 disabled for good after a region activation
-  // left the fp16 range.  ovf_dev: the sticky device word the split epilogues
-  // set; copied (asynchronously) into the pinned ovf_host at the end of every
-  // split forward and looked at when the next forward starts.
+  // The switches of the split forms as upr_model_create read them (split_pack.h).
+  // sw.region decides split_state; in state 1, sw.regs offers every fp32 conv
+  // outside the region to its kernel split in registers (ConvOp::mma16; the
+  // 32-channel row-ring programs take it), and with it sw.w64 runs the ops
+  // that got planes at build time (Op::w64_w: the 64-wide convs at half
+  // resolution) with their weights split once; sw.ring_split / sw.w64_tile go
+  // into those ops as they are.
+  upr::SplitSwitches sw{};
+  // Split-fp16 region of the plain fp32 graph: 0 off, 1 active, 2 disabled for
+  // good after a region activation left the fp16 range.  ovf_dev: the sticky
+  // device word the split epilogues (of all three forms) set; copied
+  // (asynchronously) into the pinned ovf_host at the end of every split
+  // forward and looked at when the next forward starts.
   std::atomic<int> split_state{0};
   unsigned* ovf_dev = nullptr;
   volatile unsigned* ovf_host = nullptr;
-  // Split in registers (ConvOp::mma16; env UPR_FP32_SPLIT_REGS, read at
-  // creation): in state 1 every fp32 conv outside the region is offered to its
-  // kernel in that form (the 32-channel row-ring programs take it), guarded by
-  // the same ovf word.  op_forms: the form each op of the latest forward ran in
-  // (upr_model_op_forms)
-  int split_regs = 0;
-  // ConvOp::ring_split of those ops (env UPR_RING_SPLIT_LDS, read at creation:
-  // unset / 1 -> 0, the split once per ring element in LDS, each program in
-  // its faster form; 0 -> 1, once per tap in registers; 2 / 3 -> every program
-  // converts at the top of the step / one step ahead)
-  int ring_split = 0;
-  // Weights split once (env UPR_FP32_SPLIT_W64, read at creation): in state 1,
-  // with split_regs on, the ops that got planes at build time (Op::w64_w: the
-  // 64-wide convs at half resolution) run in that form (3), same guard word
-  int split_w64 = 0;
-  // ConvOp::w64_tile of those ops (env UPR_W64_RING, read at creation: 0 -> 1,
-  // the gathered-tile kernel alone; else the 64 -> 64 ones run on the row ring)
-  int w64_tile = 0;
+  // the form each op of the latest forward ran in (upr_model_op_forms)
   std::vector<int> op_forms;
   std::mutex forms_mu;
 };
@@ -973,7 +828,7 @@ static int build_model(UprModel* m, ParamSet& P) {
   bd.upblock(ie + ".dec2", B_D3, B_U2, B_V2, B_D2, 128, 64, 2, B_X2);
   bd.upblock(ie + ".dec1", B_D2, B_U1, B_V1, B_D1, 64, 32, 1, B_X1);
   // the four 64-wide convs at half resolution: weights split once (form 3)
-  if (bd.ok && m->split_state.load() == 1 && m->split_regs && m->split_w64)
+  if (bd.ok && m->split_state.load() == 1 && m->sw.regs && m->sw.w64)
     bd.make_w64({ie + ".enc1.conv1", ie + ".enc1.conv2", ie + ".dec2.conv.0", ie + ".dec2.conv.3"});
   // residual head + illumination (models/model.py:324-328, :351-358)
   {
@@ -1128,10 +983,10 @@ static int run_forward(UprModel* m, const void* x, int B, int H, int W, void* en
     m->cur_bytes.assign(nops, 0.0);
   }
   const double elt = dt == kF16 ? 2.0 : 4.0;
-  // The split-fp16 form of a region op (Op::split_layer): its K-segments over the
-  // [hi | lo] tensors, residuals in split form, output split or (exit) plain fp32
-  auto split_op = [&](const Op& o, int ho, int wo) {
-    const GemmLayer& L = m->layers[o.split_layer];
+  // What an op's two forms share: layer L of op o at (ho, wo) output pixels --
+  // segments, geometry, weights, scale and bias, residual pointers, ReLU, store
+  // mode.  The residual strides and the output are the form's.
+  auto layer_op = [&](const Op& o, const GemmLayer& L, int ho, int wo) {
     ConvOp c;
     memset(&c, 0, sizeof(c));
     c.nseg = (int)L.segs.size();
@@ -1140,19 +995,31 @@ static int run_forward(UprModel* m, const void* x, int B, int H, int W, void* en
       ConvSeg& cs = c.seg[i];
       cs.src = buf(s.src);
       cs.C = s.C; cs.cs = s.cs; cs.coff = s.coff;
+      // source resolution: stride-2 segments read the level above
       cs.Hin = ho * s.stride; cs.Win = wo * s.stride;
       cs.kh = s.kh; cs.kw = s.kw; cs.stride = s.stride; cs.pad = s.pad; cs.dil = s.dil;
-      cs.pre = kPreNone; cs.kbase = s.kbase;
+      cs.pre = s.pre;
+      cs.pre_scale = s.pre == kPreAffineRelu ? fptr(s.pre_scale) : nullptr;
+      cs.pre_shift = s.pre == kPreAffineRelu ? fptr(s.pre_shift) : nullptr;
+      cs.kbase = s.kbase;
     }
     c.B = B; c.Ho = ho; c.Wo = wo; c.N = L.N; c.Kpad = L.Kpad;
     c.W = blob + L.w;
-    c.scale = fptr(L.scale);
+    c.scale = L.scale != SIZE_MAX ? fptr(L.scale) : nullptr;
     c.bias = L.bias != SIZE_MAX ? fptr(L.bias) : nullptr;
-    c.res1 = o.res1 >= 0 ? buf(o.res1) : nullptr; c.res1_cs = 2 * o.res1_cs;
-    c.res2 = o.res2 >= 0 ? buf(o.res2) : nullptr; c.res2_cs = 2 * o.res2_cs;
-    c.split_res = c.res1 || c.res2;
+    c.res1 = o.res1 >= 0 ? buf(o.res1) : nullptr;
+    c.res2 = o.res2 >= 0 ? buf(o.res2) : nullptr;
     c.relu = o.relu;
     c.store = o.store;
+    return c;
+  };
+  // The split-fp16 form of a region op (Op::split_layer): its K-segments over the
+  // [hi | lo] tensors (plain ones: pack_split), residuals in split form, output
+  // split or (exit) plain fp32
+  auto split_op = [&](const Op& o, int ho, int wo) {
+    ConvOp c = layer_op(o, m->layers[o.split_layer], ho, wo);
+    c.res1_cs = 2 * o.res1_cs; c.res2_cs = 2 * o.res2_cs;
+    c.split_res = c.res1 || c.res2;
     if (o.split_exit) { c.out_f32 = (float*)buf(o.out); c.out_f32_cs = o.out_cs; }
     else { c.split_out = buf(o.out); c.split_cs = 2 * o.out_cs; c.split_lo = o.out_cs; }
     c.ovf = m->ovf_dev;
@@ -1167,7 +1034,7 @@ static int run_forward(UprModel* m, const void* x, int B, int H, int W, void* en
     if (m->ovf_host && *m->ovf_host) {
       if (m->split_state.compare_exchange_strong(one, 2))
         fprintf(stderr, "upr: an fp32 activation left the fp16 range; this model now runs its exact fp32 plan "
-                      "(UPR_FP32_SPLIT=0 selects it from the start)\n");
+                      "(%s=0 selects it from the start)\n", kSwitchRegion);
     } else {
       split_now = true;
       for (const Op& o : m->ops)
@@ -1179,9 +1046,9 @@ static int run_forward(UprModel* m, const void* x, int B, int H, int W, void* en
     }
   }
   // split in registers: decided per forward from the handle's state alone (not
-  // from the region's probe); state 2 and UPR_FP32_SPLIT=0 run every op exact
-  const bool regs_now = m->split_regs && m->ovf_dev && m->split_state.load() == 1 && !(m->ovf_host && *m->ovf_host);
-  std::vector<int> forms(nops, 0);
+  // from the region's probe); states 2 and 0 run every op exact
+  const bool regs_now = m->sw.regs && m->ovf_dev && m->split_state.load() == 1 && !(m->ovf_host && *m->ovf_host);
+  std::vector<int> forms(nops, kFormExact);
   // launch op oi on stream st (the caller's stream or the multi-scale side stream)
   auto run_op = [&](size_t oi, hipStream_t st) -> int {
     const Op& o = m->ops[oi];
@@ -1201,34 +1068,11 @@ static int run_forward(UprModel* m, const void* x, int B, int H, int W, void* en
       }
       case OP_GEMM: {
         const GemmLayer& L = m->layers[o.layer];
-        ConvOp c;
-        memset(&c, 0, sizeof(c));
-        c.nseg = (int)L.segs.size();
         int ho, wo;
         lvl_dims(o.level, ho, wo);
-        for (int i = 0; i < c.nseg; ++i) {
-          const SegSpec& s = L.segs[i];
-          ConvSeg& cs = c.seg[i];
-          cs.src = buf(s.src);
-          cs.C = s.C; cs.cs = s.cs; cs.coff = s.coff;
-          // source resolution: stride-2 segments read the level above
-          int hi = ho * s.stride, wi = wo * s.stride;
-          cs.Hin = hi; cs.Win = wi;
-          cs.kh = s.kh; cs.kw = s.kw; cs.stride = s.stride; cs.pad = s.pad; cs.dil = s.dil;
-          cs.pre = s.pre;
-          cs.pre_scale = s.pre == kPreAffineRelu ? fptr(s.pre_scale) : nullptr;
-          cs.pre_shift = s.pre == kPreAffineRelu ? fptr(s.pre_shift) : nullptr;
-          cs.kbase = s.kbase;
-        }
-        c.B = B; c.Ho = ho; c.Wo = wo; c.N = L.N; c.Kpad = L.Kpad;
-        c.W = blob + L.w;
-        c.scale = nullptr;
-        c.bias = L.bias != SIZE_MAX ? fptr(L.bias) : nullptr;
+        ConvOp c = layer_op(o, L, ho, wo);
         c.img_bias = o.img_bias ? ib : nullptr;
-        c.res1 = o.res1 >= 0 ? buf(o.res1) : nullptr; c.res1_cs = o.res1_cs;
-        c.relu = o.relu;
-        c.res2 = o.res2 >= 0 ? buf(o.res2) : nullptr; c.res2_cs = o.res2_cs;
-        c.store = o.store;
+        c.res1_cs = o.res1_cs; c.res2_cs = o.res2_cs;
         if (o.store == kStoreHeadIllu) {
           c.head_w = fptr(o.head_w); c.head_b = o.head_b;
           c.x_nchw = (const float*)x; c.x_f16 = dt == kF16;
@@ -1244,21 +1088,20 @@ static int run_forward(UprModel* m, const void* x, int B, int H, int W, void* en
         }
         if (split_now && o.split_layer >= 0) {
           rc = launch_conv_wide(split_op(o, ho, wo), st);
-          forms[oi] = 1;
+          forms[oi] = kFormRegion;
         } else {
           rc = kErrUnsupported;
           if (regs_now && dt == kF32 && o.w64_w != SIZE_MAX) {
             ConvOp cw = c;
             cw.W = blob + o.w64_w; cw.scale = fptr(o.w64_scale);
-            cw.mma16 = 3; cw.ovf = m->ovf_dev;
-            cw.ring_split = m->ring_split; cw.w64_tile = m->w64_tile;
+            cw.mma16 = kMma16WSplit; cw.ovf = m->ovf_dev;
+            cw.ring_split = m->sw.ring_split; cw.w64_tile = m->sw.w64_tile;
             rc = launch_conv_wsplit(cw, st);
-            if (rc == kOk) forms[oi] = 3;
+            if (rc == kOk) forms[oi] = kFormWSplit;
           }
           if (rc == kErrUnsupported) {
-            if (regs_now && dt == kF32) { c.mma16 = 1; c.ovf = m->ovf_dev; c.ring_split = m->ring_split; }
-            rc = launch_conv(c, dt, st);
-            forms[oi] = conv_last_form();
+            if (regs_now && dt == kF32) { c.mma16 = kMma16Offer; c.ovf = m->ovf_dev; c.ring_split = m->sw.ring_split; }
+            rc = launch_conv(c, dt, st, &forms[oi]);
           }
         }
         if (m->prof) {
@@ -1294,7 +1137,7 @@ static int run_forward(UprModel* m, const void* x, int B, int H, int W, void* en
         lvl_dims(o.level, h, w);
         const int C = buf_geom(o.in, m->use_aspp).C;
         rc = launch_split_f32((const float*)buf(o.in), buf(o.out), (size_t)B * h * w, C, m->ovf_dev, st);
-        forms[oi] = 1;
+        forms[oi] = kFormRegion;
         if (m->prof) m->cur_bytes[oi] = 2.0 * B * h * w * C * 4.0;
         break;
       }
@@ -1413,80 +1256,6 @@ int launch_cast_f32_to_f16(const float* a, void* b, size_t n, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-// fp32 NHWC <-> split fp16 ([hi(C) | lo(C)] per pixel, ConvOp::split_out):
-// one thread per 8 channels of a pixel, 16-byte accesses
-__global__ void split_f32_kernel(const float* __restrict__ x, half_t* __restrict__ y, size_t n8, int C8,
-                                 unsigned* __restrict__ ovf) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n8) return;
-  const size_t pix = i / C8;
-  const int c = (int)(i - pix * C8) * 8;
-  const f4 a = *(const f4*)(x + i * 8), b = *(const f4*)(x + i * 8 + 4);
-  const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  h8 h, l;
-  bool bad = false;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    h[e] = (half_t)v[e];
-    l[e] = (half_t)((v[e] - (float)h[e]) * kSplitLoScale);
-    bad = bad || !(__builtin_fabsf(v[e]) <= 65504.f);
-  }
-  half_t* d = y + pix * (size_t)(16 * C8) + c;
-  *(h8*)d = h;
-  *(h8*)(d + 8 * C8) = l;
-  if (bad && ovf) *ovf = 1u;
-}
-__global__ void unsplit_f32_kernel(const half_t* __restrict__ x, float* __restrict__ y, size_t n8, int C8) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n8) return;
-  const size_t pix = i / C8;
-  const int c = (int)(i - pix * C8) * 8;
-  const half_t* sp = x + pix * (size_t)(16 * C8) + c;
-  const h8 h = *(const h8*)sp, l = *(const h8*)(sp + 8 * C8);
-  f4 a, b;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    a[e] = (float)h[e] + (float)l[e] * kSplitLoInv;
-    b[e] = (float)h[e + 4] + (float)l[e + 4] * kSplitLoInv;
-  }
-  *(f4*)(y + i * 8) = a;
-  *(f4*)(y + i * 8 + 4) = b;
-}
-int launch_split_f32(const float* x, void* y, size_t npix, int C, unsigned* ovf, hipStream_t st) {
-  if (C <= 0 || C % 8 || ((uintptr_t)x | (uintptr_t)y) % 16) return kErrArg;
-  const size_t n8 = npix * (size_t)(C / 8);
-  if (n8 == 0) return kOk;
-  if ((n8 + 255) / 256 > 0x7fffffffull) return kErrShape;
-  hipLaunchKernelGGL(split_f32_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, x, (half_t*)y, n8, C / 8, ovf);
-  return (int)hipGetLastError();
-}
-int launch_unsplit_f32(const void* x, float* y, size_t npix, int C, hipStream_t st) {
-  if (C <= 0 || C % 8 || ((uintptr_t)x | (uintptr_t)y) % 16) return kErrArg;
-  const size_t n8 = npix * (size_t)(C / 8);
-  if (n8 == 0) return kOk;
-  if ((n8 + 255) / 256 > 0x7fffffffull) return kErrShape;
-  hipLaunchKernelGGL(unsplit_f32_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, (const half_t*)x, y, n8, C / 8);
-  return (int)hipGetLastError();
-}
-
-// ConvOp::ring_split from UPR_RING_SPLIT_LDS as it is set now
-static int ring_split_env() {
-  const char* e = getenv("UPR_RING_SPLIT_LDS");
-  if (!e || !*e) return 0;
-  const int v = atoi(e);
-  return v == 0 ? 1 : v == 2 || v == 3 ? v : 0;
-}
-
-// ConvOp::w64_tile from UPR_W64_RING as it is set now
-static int w64_tile_env() {
-  const char* e = getenv("UPR_W64_RING");
-  return e && *e && atoi(e) == 0;
-}
-
 }  // namespace upr
 
 // ===========================================================================
@@ -1517,26 +1286,12 @@ int upr_model_create(const UprTensorDesc* params, int n_params, int use_preact, 
   }
   std::unique_ptr<UprModel> m(new UprModel());
   m->dtype = dtype; m->use_preact = use_preact ? 1 : 0; m->use_aspp = use_aspp ? 1 : 0; m->flags = flags;
-  // the split-fp16 region exists in the plain fp32 IENet only; UPR_FP32_SPLIT=0
-  // (read here, per handle) keeps the fp32 MFMA kernels everywhere
-  const char* se = getenv("UPR_FP32_SPLIT");
-  const bool split_env = !(se && *se && atoi(se) == 0);
+  m->sw = read_split_switches();  // read here, per handle
+  // the split-fp16 region exists in the plain fp32 IENet only
   // (a head-only handle has no region op, but its FAM convs run split in
   // registers in state 1, as the full model's do: multi_scale_enhance stays
   // bit-equal to the fused forward)
-  if (split_env && dtype == UPR_F32 && !m->use_preact && !m->use_aspp) m->split_state.store(1);
-  // UPR_FP32_SPLIT_REGS=0 keeps the split-in-registers ops on the fp32 MFMA
-  // kernels while the region stays split
-  const char* sr = getenv("UPR_FP32_SPLIT_REGS");
-  m->split_regs = !(sr && *sr && atoi(sr) == 0);
-  // UPR_RING_SPLIT_LDS=0 keeps those ops' per-tap split (the same bits)
-  m->ring_split = ring_split_env();
-  // UPR_FP32_SPLIT_W64=0 keeps the weights-split-once ops (the 64-wide convs
-  // at half resolution) on the fp32 MFMA kernel alone
-  const char* sw = getenv("UPR_FP32_SPLIT_W64");
-  m->split_w64 = !(sw && *sw && atoi(sw) == 0);
-  // UPR_W64_RING=0 keeps those ops on the gathered-tile kernel (the same form code)
-  m->w64_tile = w64_tile_env();
+  if (m->sw.region && dtype == UPR_F32 && !m->use_preact && !m->use_aspp) m->split_state.store(1);
   int rc = build_model(m.get(), P);
   if (rc == kOk && m->split_state.load() == 1) {
     hipError_t e = hipMalloc((void**)&m->ovf_dev, 256);
@@ -1652,181 +1407,6 @@ const char* upr_status_string(int status) {
     case UPR_ERR_UNSUPPORTED: return "unsupported configuration";
     default: return status > 0 ? hipGetErrorString((hipError_t)status) : "unknown error";
   }
-}
-
-int upr_conv2d_nhwc(const void* x, int B, int H, int W, int Cin, const void* w, const float* bias, int Cout, int kh,
-                    int kw, int stride, int pad, int dil, const void* residual, int relu, void* y, int dtype,
-                    void* stream) {
-  if (!x || !w || !y || B <= 0 || H <= 0 || W <= 0 || Cin % 32 || Cout % 32 || Cin <= 0 || Cout <= 0) return UPR_ERR_ARG;
-  if (kh <= 0 || kw <= 0 || stride <= 0 || dil <= 0 || pad < 0) return UPR_ERR_ARG;
-  if (dtype == UPR_F32_SPLIT_REGS)
-    return upr_conv2d_nhwc_regs(x, B, H, W, Cin, w, bias, Cout, kh, kw, stride, pad, dil, residual, relu, y, nullptr,
-                                stream);
-  if (dtype != UPR_F32 && dtype != UPR_F16 && dtype != UPR_F32_SPLIT) return UPR_ERR_ARG;
-  const int Ho = (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1;
-  const int Wo = (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
-  if (Ho <= 0 || Wo <= 0) return UPR_ERR_SHAPE;
-  ConvOp c;
-  memset(&c, 0, sizeof(c));
-  if (dtype == UPR_F32_SPLIT) {
-    // x / residual / y are split tensors, w is upr_pack_split_f32's blob: the
-    // two K-segments of pack_split over x, then the per-channel scale
-    if (Cin % 64 || Cout % 128) return UPR_ERR_UNSUPPORTED;
-    const int taps = kh * kw;
-    c.nseg = 2;
-    for (int i = 0; i < 2; ++i) {
-      ConvSeg& s = c.seg[i];
-      s.src = x; s.C = i == 0 ? 2 * Cin : Cin; s.cs = 2 * Cin; s.coff = 0; s.Hin = H; s.Win = W;
-      s.kh = kh; s.kw = kw; s.stride = stride; s.pad = pad; s.dil = dil; s.pre = kPreNone;
-      s.kbase = i == 0 ? 0 : taps * 2 * Cin;
-    }
-    c.B = B; c.Ho = Ho; c.Wo = Wo; c.N = Cout; c.Kpad = (int)align_up((size_t)3 * taps * Cin, 32);
-    c.W = w;
-    c.scale = (const float*)((const uint8_t*)w + align_up((size_t)Cout * c.Kpad * 2, 256));
-    c.bias = bias; c.relu = relu;
-    if (relu) { c.res1 = residual; c.res1_cs = 2 * Cout; }
-    else { c.res2 = residual; c.res2_cs = 2 * Cout; }
-    c.split_res = residual != nullptr;
-    c.split_out = y; c.split_cs = 2 * Cout; c.split_lo = Cout; c.store = kStoreNHWC;
-    return launch_conv_wide(c, (hipStream_t)stream);
-  }
-  c.nseg = 1;
-  ConvSeg& s = c.seg[0];
-  s.src = x; s.C = Cin; s.cs = Cin; s.coff = 0; s.Hin = H; s.Win = W;
-  s.kh = kh; s.kw = kw; s.stride = stride; s.pad = pad; s.dil = dil; s.pre = kPreNone; s.kbase = 0;
-  c.B = B; c.Ho = Ho; c.Wo = Wo; c.N = Cout; c.Kpad = kh * kw * Cin;
-  c.W = w; c.bias = bias; c.relu = relu;
-  // without ReLU, "added before" and "added after" coincide: use the post-ReLU
-  // slot, which every kernel family takes
-  if (relu) { c.res1 = residual; c.res1_cs = Cout; }
-  else { c.res2 = residual; c.res2_cs = Cout; }
-  c.out = y; c.out_cs = Cout; c.out_coff = 0; c.store = kStoreNHWC;
-  return launch_conv(c, dtype, (hipStream_t)stream);
-}
-
-int upr_conv2d_nhwc_regs(const void* x, int B, int H, int W, int Cin, const void* w, const float* bias, int Cout,
-                         int kh, int kw, int stride, int pad, int dil, const void* residual, int relu, void* y,
-                         unsigned* overflow, void* stream) {
-  if (!x || !w || !y || B <= 0 || H <= 0 || W <= 0 || Cin % 32 || Cout % 32 || Cin <= 0 || Cout <= 0) return UPR_ERR_ARG;
-  if (kh <= 0 || kw <= 0 || stride <= 0 || dil <= 0 || pad < 0) return UPR_ERR_ARG;
-  const int Ho = (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1;
-  const int Wo = (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
-  if (Ho <= 0 || Wo <= 0) return UPR_ERR_SHAPE;
-  // the UPR_F32 op of upr_conv2d_nhwc, offered in the split-in-registers form to
-  // the kernels that have it and to nothing else
-  ConvOp c;
-  memset(&c, 0, sizeof(c));
-  c.nseg = 1;
-  ConvSeg& s = c.seg[0];
-  s.src = x; s.C = Cin; s.cs = Cin; s.coff = 0; s.Hin = H; s.Win = W;
-  s.kh = kh; s.kw = kw; s.stride = stride; s.pad = pad; s.dil = dil; s.pre = kPreNone; s.kbase = 0;
-  c.B = B; c.Ho = Ho; c.Wo = Wo; c.N = Cout; c.Kpad = kh * kw * Cin;
-  c.W = w; c.bias = bias; c.relu = relu;
-  // (the row ring adds its residual after the ReLU; with a ReLU its pre-ReLU
-  // residual program is the dilation-2 FAM part, which this entry does not offer)
-  if (relu && residual) return UPR_ERR_UNSUPPORTED;
-  c.res2 = residual; c.res2_cs = Cout;
-  c.out = y; c.out_cs = Cout; c.out_coff = 0; c.store = kStoreNHWC;
-  c.mma16 = 1; c.ovf = overflow;
-  c.ring_split = ring_split_env();  // read at the call: one process can run both programs
-  return launch_conv_regs(c, (hipStream_t)stream);
-}
-
-size_t upr_pack_split_f32(const float* w, int Cout, int Cin, int kh, int kw, void* out, size_t out_bytes) {
-  if (!w || Cout <= 0 || Cin <= 0 || Cin % 64 || kh <= 0 || kw <= 0) return 0;
-  std::vector<SegWeights> segs(1);
-  segs[0].spec = seg(/*src=*/0, Cin, Cin, 0, kh, 1, 0, 1);
-  segs[0].spec.kw = kw;
-  segs[0].w.assign(w, w + (size_t)Cout * Cin * kh * kw);
-  SplitPack sp;
-  if (!pack_split(Cout, segs, sp)) return 0;
-  const size_t wbytes = align_up(sp.W.size() * 2, 256), need = wbytes + sp.scale.size() * 4;
-  if (out && out_bytes >= need) {
-    memset(out, 0, need);
-    memcpy(out, sp.W.data(), sp.W.size() * 2);
-    memcpy((uint8_t*)out + wbytes, sp.scale.data(), sp.scale.size() * 4);
-  }
-  return need;
-}
-
-// bytes of upr_pack_split_w_f32's blob: the planes (4 bytes per weight), then 1 / s_n
-static size_t split_w_bytes(int Cout, int K, size_t* scale_off) {
-  const size_t wbytes = align_up((size_t)Cout * K * 4, 256);
-  if (scale_off) *scale_off = wbytes;
-  return wbytes + (size_t)Cout * 4;
-}
-
-size_t upr_pack_split_w_f32(const float* w, int Cout, int Cin, int kh, int kw, const float* w2, int C2, void* out,
-                            size_t out_bytes) {
-  if (!w || Cout <= 0 || Cout % 64 || Cin <= 0 || Cin % 32 || kh <= 0 || kw <= 0) return 0;
-  if ((w2 != nullptr) != (C2 > 0) || C2 < 0 || C2 % 32) return 0;
-  const int K1 = kh * kw * Cin, K = K1 + C2;
-  std::vector<float> rows((size_t)Cout * K);
-  for (int n = 0; n < Cout; ++n) {
-    memcpy(rows.data() + (size_t)n * K, w + (size_t)n * K1, (size_t)K1 * 4);
-    if (w2) memcpy(rows.data() + (size_t)n * K + K1, w2 + (size_t)n * C2, (size_t)C2 * 4);
-  }
-  SplitWPack sp;
-  if (!pack_split_w(Cout, K, rows.data(), sp)) return 0;
-  size_t soff = 0;
-  const size_t need = split_w_bytes(Cout, K, &soff);
-  if (out && out_bytes >= need) {
-    memset(out, 0, need);
-    memcpy(out, sp.W.data(), sp.W.size() * 2);
-    memcpy((uint8_t*)out + soff, sp.scale.data(), sp.scale.size() * 4);
-  }
-  return need;
-}
-
-int upr_conv2d_nhwc_wsplit(const void* x, int B, int H, int W, int Cin, const void* blob, size_t blob_bytes,
-                           const float* bias, int Cout, int kh, int kw, int stride, int pad, int dil,
-                           const void* residual, int relu, void* y, const void* x2, int H2, int W2, int C2,
-                           int stride2, unsigned* overflow, void* stream) {
-  conv_reset_wsplit_kernel();
-  if (!x || !blob || !y || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return UPR_ERR_ARG;
-  if (kh <= 0 || kw <= 0 || stride <= 0 || dil <= 0 || pad < 0) return UPR_ERR_ARG;
-  if (x2 && (H2 <= 0 || W2 <= 0 || C2 <= 0 || stride2 <= 0)) return UPR_ERR_ARG;
-  const int Ho = (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1;
-  const int Wo = (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
-  if (Ho <= 0 || Wo <= 0) return UPR_ERR_SHAPE;
-  if (x2 && ((H2 - 1) / stride2 + 1 != Ho || (W2 - 1) / stride2 + 1 != Wo)) return UPR_ERR_SHAPE;
-  if (Cin % 32 || Cout % 64 || (x2 && C2 % 32)) return UPR_ERR_UNSUPPORTED;
-  const int K1 = kh * kw * Cin, K = K1 + (x2 ? C2 : 0);
-  size_t soff = 0;
-  if (blob_bytes != split_w_bytes(Cout, K, &soff)) return UPR_ERR_UNSUPPORTED;  // packed for another shape
-  ConvOp c;
-  memset(&c, 0, sizeof(c));
-  c.nseg = x2 ? 2 : 1;
-  ConvSeg& s = c.seg[0];
-  s.src = x; s.C = Cin; s.cs = Cin; s.coff = 0; s.Hin = H; s.Win = W;
-  s.kh = kh; s.kw = kw; s.stride = stride; s.pad = pad; s.dil = dil; s.pre = kPreNone; s.kbase = 0;
-  if (x2) {
-    ConvSeg& t = c.seg[1];
-    t.src = x2; t.C = C2; t.cs = C2; t.coff = 0; t.Hin = H2; t.Win = W2;
-    t.kh = 1; t.kw = 1; t.stride = stride2; t.pad = 0; t.dil = 1; t.pre = kPreNone; t.kbase = K1;
-  }
-  c.B = B; c.Ho = Ho; c.Wo = Wo; c.N = Cout; c.Kpad = K;
-  c.W = blob; c.scale = (const float*)((const uint8_t*)blob + soff);
-  c.bias = bias; c.relu = relu;
-  c.res2 = residual; c.res2_cs = Cout;
-  c.out = y; c.out_cs = Cout; c.out_coff = 0; c.store = kStoreNHWC;
-  c.mma16 = 3; c.ovf = overflow;
-  // read at the call: one process can run both kernels and both ring schedules
-  c.ring_split = ring_split_env();
-  c.w64_tile = w64_tile_env();
-  return launch_conv_wsplit(c, (hipStream_t)stream);
-}
-
-int upr_conv_wsplit_ran(void) { return conv_last_wsplit_kernel(); }
-
-int upr_split_f32(const float* x, void* y, size_t npix, int C, unsigned* overflow, void* stream) {
-  if (!x || !y) return UPR_ERR_ARG;
-  return launch_split_f32(x, y, npix, C, overflow, (hipStream_t)stream);
-}
-
-int upr_unsplit_f32(const void* x, float* y, size_t npix, int C, void* stream) {
-  if (!x || !y) return UPR_ERR_ARG;
-  return launch_unsplit_f32(x, y, npix, C, (hipStream_t)stream);
 }
 
 }  // extern "C"

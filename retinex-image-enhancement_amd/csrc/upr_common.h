@@ -118,7 +118,7 @@ struct ConvOp {
   // Split-fp16 form of an fp32 conv (launch_conv_wide only).  A split tensor
   // stores C fp32 channels per pixel as 2C fp16: [hi(C) | lo(C)], hi = (half)v,
   // lo = (half)((v - hi) * 2^11), v = hi + lo * 2^-11.  The segments and packed
-  // weights carry the split operands (model.hip pack_split); here only the
+  // weights carry the split operands (split_pack.hip pack_split); here only the
   // epilogue differs: every value is taken from the fp32 accumulator, never
   // from its fp16 rounding.
   // split_out (nullable): hi at split_out[pix * split_cs + ch], lo split_lo
@@ -133,32 +133,53 @@ struct ConvOp {
   // tensors, DMA and LDS stay fp32, each 8-channel fragment is split into (hi,
   // lo) fp16 after its LDS read (split_f32x8) and the products run on the fp16
   // MFMA unit as hi W_hi + hi W_lo + (lo W_hi) 2^-11 with per-output-channel
-  // power-of-two weight scales.  1: a kernel that does not take the op in this
-  // form runs its exact fp32 form (conv_last_form tells which ran); 2: it
-  // answers kErrUnsupported instead (launch_conv_regs).  ovf as above: set
-  // when an accumulator is not finite (an input left the fp16 range).
-  // 3 (launch_conv_wsplit only): the weights were split once on the host -- W
-  // is the fp16 plane blob of model.hip pack_split_w ([N][Kpad / 32][W_hi(32) |
-  // W_lo(32)], as many bytes per row as the fp32 weights), scale the 1 / s_n
-  // vector; only the activation fragments are split in the kernel.
+  // power-of-two weight scales.  kMma16Offer: a kernel that does not take the
+  // op in this form runs its exact fp32 form (launch_conv's `form` tells which
+  // ran); kMma16Only: it answers kErrUnsupported instead (launch_conv_regs).
+  // ovf as above: set when an accumulator is not finite (an input left the
+  // fp16 range).  kMma16WSplit (launch_conv_wsplit only): the weights were
+  // split once on the host -- W is the fp16 plane blob of split_pack.hip
+  // pack_split_w ([N][Kpad / 32][W_hi(32) | W_lo(32)], as many bytes per row as
+  // the fp32 weights), scale the 1 / s_n vector; only the activation fragments
+  // are split in the kernel.
   // (placed in the padding before ovf: the struct, and with it every kernel
   // argument block, keeps its layout)
   int mma16;
   unsigned* ovf;
-  // Where the row ring's split-in-registers programs (mma16 1 / 2) split their
-  // activations; every choice gives the same bits.  0: once per ring element,
-  // in LDS, in the form (2 or 3) that measured faster for the program; 1: once
-  // per tap, in registers after the LDS read (env UPR_RING_SPLIT_LDS=0); 2: in
-  // LDS at the top of the step that first reads the group, behind a second
-  // barrier (UPR_RING_SPLIT_LDS=2); 3: in LDS one step ahead of the first
-  // reader, beside the MFMAs, in a 5-group ring (UPR_RING_SPLIT_LDS=3)
+  // Where the row ring's split-in-registers programs (kMma16Offer / Only)
+  // split their activations; every choice gives the same bits.
+  // kRingSplitDefault: once per ring element, in LDS, in the form (Top or
+  // Ahead) that measured faster for the program; kRingSplitTap: once per tap,
+  // in registers after the LDS read; kRingSplitTop: in LDS at the top of the
+  // step that first reads the group, behind a second barrier; kRingSplitAhead:
+  // in LDS one step ahead of the first reader, beside the MFMAs, in a 5-group
+  // ring.  (The switches that set this and w64_tile: split_pack.h.)
   int ring_split;
   // launch_conv_wsplit: 0 = the 64 -> 64 stride-1 3x3 programs run on the row
   // ring (conv_ring64.hip) and what it refuses on the gathered tile; 1 = the
-  // tile kernel alone (env UPR_W64_RING=0).  The ring's schedule follows
-  // ring_split (2: top of the step, 3: ahead, else its default)
+  // tile kernel alone.  The ring's schedule follows ring_split (Top, Ahead,
+  // else its default)
   int w64_tile;
 };
+
+// ConvOp::mma16
+enum : int {
+  kMma16Off = 0,
+  kMma16Offer = 1,   // split in registers where a kernel has the form, else the exact program
+  kMma16Only = 2,    // split in registers or kErrUnsupported
+  kMma16WSplit = 3,  // weights split once on the host
+};
+// ConvOp::ring_split
+enum : int { kRingSplitDefault = 0, kRingSplitTap = 1, kRingSplitTop = 2, kRingSplitAhead = 3 };
+// The form an op ran in (upr_model_op_forms, include/upr.h UprOpForm::form)
+enum : int {
+  kFormExact = 0,   // the model dtype's own kernels
+  kFormRegion = 1,  // split-fp16 region (ConvOp::split_out)
+  kFormRegs = 2,    // split in registers
+  kFormWSplit = 3,  // weights split once
+};
+// The kernel launch_conv_wsplit ran (upr_conv_wsplit_ran)
+enum : int { kWSplitNone = 0, kWSplitTile = 1, kWSplitRing = 2 };
 
 // 2^11 / 2^-11: the scale of the lo half of a split-fp16 value (ConvOp::split_out)
 constexpr float kSplitLoScale = 2048.f;
@@ -202,7 +223,7 @@ __host__ __device__ inline int split_row_shift(float mx) {
   return sh;
 }
 
-// fp32 NHWC [npix][C] <-> split fp16 [npix][2C] (C % 8 == 0; model.hip)
+// fp32 NHWC [npix][C] <-> split fp16 [npix][2C] (C % 8 == 0; split_pack.hip)
 int launch_split_f32(const float* x, void* y, size_t npix, int C, unsigned* ovf, hipStream_t st);
 int launch_unsplit_f32(const void* x, float* y, size_t npix, int C, hipStream_t st);
 
@@ -215,28 +236,21 @@ int launch_conv_s2dg(const ConvOp& op, hipStream_t stream, bool probe = false);
 // fp16 1x1 streaming convs (conv_pw.hip); probe: only answer kOk / kErrUnsupported
 int launch_conv_pw(const ConvOp& op, hipStream_t stream, bool probe = false);
 
-int launch_conv(const ConvOp& op, int dtype, hipStream_t stream);
-// the form the calling thread's latest launch_conv ran in: 0 = the dtype's own
-// kernels, 2 = split in registers (ConvOp::mma16)
-// (3, weights split once, is set by the caller of launch_conv_wsplit)
-int conv_last_form();
-void conv_set_last_form(int form);
-// an fp32 op in the split-in-registers form only (sets mma16 = 2): kOk, or
-// kErrUnsupported when no kernel takes it in that form
-int launch_conv_regs(const ConvOp& op, hipStream_t stream);
+// form (nullable): the form the op ran in, kFormExact or kFormRegs (ConvOp::mma16)
+int launch_conv(const ConvOp& op, int dtype, hipStream_t stream, int* form = nullptr);
+// an fp32 op in the split-in-registers form only (sets mma16 = kMma16Only):
+// kOk, or kErrUnsupported when no kernel takes it in that form
+int launch_conv_regs(const ConvOp& op, hipStream_t stream, int* form = nullptr);
 
-int launch_conv_ring32(const ConvOp& op, hipStream_t st);
-// an fp32 op with its weights split once (ConvOp::mma16 == 3; conv_wide32.hip):
-// kOk, or kErrUnsupported -- it never runs another form.  Two kernels: the row
-// ring for the ops launch_conv_ring_w64 takes (unless ConvOp::w64_tile), the
-// gathered 256 x 64 tile for the rest
-int launch_conv_wsplit(const ConvOp& op, hipStream_t st);
+int launch_conv_ring32(const ConvOp& op, hipStream_t st, int* form = nullptr);
+// an fp32 op with its weights split once (ConvOp::mma16 == kMma16WSplit;
+// conv_wide32.hip): kOk, or kErrUnsupported -- it never runs another form.  Two
+// kernels: the row ring for the ops launch_conv_ring_w64 takes (unless
+// ConvOp::w64_tile), the gathered 256 x 64 tile for the rest; kernel
+// (nullable): which one ran, kWSplitNone when the op was refused
+int launch_conv_wsplit(const ConvOp& op, hipStream_t st, int* kernel = nullptr);
 // the row-ring kernel of that form alone (conv_ring64.hip): kOk or kErrUnsupported
 int launch_conv_ring_w64(const ConvOp& op, hipStream_t st);
-// the kernel the calling thread's latest launch_conv_wsplit ran: 0 = none (it
-// refused the op), 1 = the gathered tile, 2 = the row ring
-int conv_last_wsplit_kernel();
-void conv_reset_wsplit_kernel();  // an entry point that may refuse before it gets there
 // position of channel c (0..31) of a 32-deep K step within a 32-half weight
 // plane of that form: lane group g = (c % 16) / 4 holds the 8 k-slots 4g..4g+3,
 // 16+4g..16+4g+3, the channels of its two ds_read_b128 of an fp32 A row

@@ -336,17 +336,26 @@ def pack_conv_weight(w):
     return w.permute(0, 2, 3, 1).reshape(co, kh * kw * ci).contiguous()
 
 
-def conv2d_nhwc(x, w_packed, bias, kh, kw, stride=1, pad=0, dil=1, residual=None, relu=False):
-    """x [B,H,W,Cin] -> y [B,Ho,Wo,Cout] through the implicit-GEMM MFMA kernel."""
+def _conv_io(x, residual, ychan, kh, kw, stride, pad, dil, f32_only=None, ydtype=None):
+    """What the conv wrappers share: x on a device (float32 for the wrapper that
+    f32_only names), x and residual contiguous, an empty NHWC output of ychan
+    channels -> (x, residual, y)."""
     _require_device(x)
+    if f32_only and x.dtype != torch.float32:
+        raise ValueError(f"{f32_only} expects float32 tensors")
     x = x.contiguous()
-    B, H, W, Cin = x.shape
-    Cout = w_packed.shape[0]
+    B, H, W, _ = x.shape
     Ho = (H + 2 * pad - dil * (kh - 1) - 1) // stride + 1
     Wo = (W + 2 * pad - dil * (kw - 1) - 1) // stride + 1
-    y = torch.empty((B, Ho, Wo, Cout), dtype=x.dtype, device=x.device)
-    if residual is not None:
-        residual = residual.contiguous()
+    y = torch.empty((B, Ho, Wo, ychan), dtype=ydtype or x.dtype, device=x.device)
+    return x, None if residual is None else residual.contiguous(), y
+
+
+def conv2d_nhwc(x, w_packed, bias, kh, kw, stride=1, pad=0, dil=1, residual=None, relu=False):
+    """x [B,H,W,Cin] -> y [B,Ho,Wo,Cout] through the implicit-GEMM MFMA kernel."""
+    Cout = w_packed.shape[0]
+    x, residual, y = _conv_io(x, residual, Cout, kh, kw, stride, pad, dil)
+    B, H, W, Cin = x.shape
     with torch.cuda.device(x.device):
         rc = L.lib().upr_conv2d_nhwc(_ptr(x), B, H, W, Cin, _ptr(w_packed.contiguous()), _ptr(bias), Cout, kh, kw,
                                      stride, pad, dil, _ptr(residual), int(bool(relu)), _ptr(y),
@@ -362,17 +371,9 @@ def conv2d_nhwc_regs(x, w_packed, bias, kh, kw, stride=1, pad=0, dil=1, residual
 
     overflow: optional int32 device tensor of one element, set to 1 when an
     input was outside the fp16 range (the output is then void)."""
-    _require_device(x)
-    if x.dtype != torch.float32:
-        raise ValueError("conv2d_nhwc_regs expects float32 tensors")
-    x = x.contiguous()
-    B, H, W, Cin = x.shape
     Cout = w_packed.shape[0]
-    Ho = (H + 2 * pad - dil * (kh - 1) - 1) // stride + 1
-    Wo = (W + 2 * pad - dil * (kw - 1) - 1) // stride + 1
-    y = torch.empty((B, Ho, Wo, Cout), dtype=x.dtype, device=x.device)
-    if residual is not None:
-        residual = residual.contiguous()
+    x, residual, y = _conv_io(x, residual, Cout, kh, kw, stride, pad, dil, f32_only="conv2d_nhwc_regs")
+    B, H, W, Cin = x.shape
     with torch.cuda.device(x.device):
         rc = L.lib().upr_conv2d_nhwc_regs(_ptr(x), B, H, W, Cin, _ptr(w_packed.contiguous()), _ptr(bias), Cout, kh, kw,
                                           stride, pad, dil, _ptr(residual), int(bool(relu)), _ptr(y), _ptr(overflow),
@@ -411,16 +412,8 @@ def conv2d_nhwc_wsplit(x, w_blob, cout, bias, kh, kw, stride=1, pad=0, dil=1, re
 
     overflow: optional int32 device tensor of one element, set to 1 when an
     input was outside the fp16 range (the output is then void)."""
-    _require_device(x)
-    if x.dtype != torch.float32:
-        raise ValueError("conv2d_nhwc_wsplit expects float32 tensors")
-    x = x.contiguous()
+    x, residual, y = _conv_io(x, residual, cout, kh, kw, stride, pad, dil, f32_only="conv2d_nhwc_wsplit")
     B, H, W, Cin = x.shape
-    Ho = (H + 2 * pad - dil * (kh - 1) - 1) // stride + 1
-    Wo = (W + 2 * pad - dil * (kw - 1) - 1) // stride + 1
-    y = torch.empty((B, Ho, Wo, cout), dtype=x.dtype, device=x.device)
-    if residual is not None:
-        residual = residual.contiguous()
     H2 = W2 = C2 = 0
     if x2 is not None:
         x2 = x2.contiguous()
@@ -488,14 +481,8 @@ def pack_split_weight(w):
 def conv2d_split(x, w_blob, cout, bias, kh, kw, stride=1, pad=0, dil=1, residual=None, relu=False):
     """conv2d_nhwc on split tensors: x [B,H,W,2Cin] and residual [B,Ho,Wo,2Cout] fp16
     split, w_blob from pack_split_weight (on the device) -> y [B,Ho,Wo,2Cout] split."""
-    _require_device(x)
-    x = x.contiguous()
+    x, residual, y = _conv_io(x, residual, 2 * cout, kh, kw, stride, pad, dil, ydtype=torch.float16)
     B, H, W, C2 = x.shape
-    Ho = (H + 2 * pad - dil * (kh - 1) - 1) // stride + 1
-    Wo = (W + 2 * pad - dil * (kw - 1) - 1) // stride + 1
-    y = torch.empty((B, Ho, Wo, 2 * cout), dtype=torch.float16, device=x.device)
-    if residual is not None:
-        residual = residual.contiguous()
     with torch.cuda.device(x.device):
         rc = L.lib().upr_conv2d_nhwc(_ptr(x), B, H, W, C2 // 2, _ptr(w_blob), _ptr(bias), cout, kh, kw, stride, pad,
                                      dil, _ptr(residual), int(bool(relu)), _ptr(y), L.UPR_F32_SPLIT,

@@ -14,11 +14,9 @@ import pytest
 import torch
 
 from conftest import has_gpu
-from test_gpu_split_regs import RING_CASES, fwd, make_handle, make_sd, ring_inputs
+from split_cases import DEV, RING_CASES, fwd, make_handle, make_sd, ring_inputs
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs a ROCm device")]
-
-DEV = "cuda:0"
 LDS_FORMS = ["1", "2", "3"]  # UPR_RING_SPLIT_LDS: the shipped choice, and each LDS form for every program
 
 
@@ -101,7 +99,7 @@ def test_overflow_word_in_every_form(mode, monkeypatch):
 def make(sd, mode, monkeypatch):
     """UPR_RING_SPLIT_LDS is read when the handle is created."""
     monkeypatch.setenv("UPR_RING_SPLIT_LDS", mode)
-    return make_handle(sd, False, False, True, True, monkeypatch)
+    return make_handle(sd, False, False, monkeypatch, split=True, regs=True)
 
 
 @pytest.mark.parametrize("shape", [(3, 48, 80), (1, 96, 64)])

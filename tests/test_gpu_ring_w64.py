@@ -19,14 +19,11 @@ whole tensors; the gate's `coff % 4` line refuses it for model graphs).
 """
 import pytest
 import torch
-import torch.nn.functional as F
 
 from conftest import has_gpu
-from oracle import net as onet
+from split_cases import DEV, WsplitCases, fwd, make_handle, make_sd, oracle_f64
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs a ROCm device")]
-
-DEV = "cuda:0"
 
 # B, H, W, Cin, Cout, stride, pad, dil, relu, residual (after the ReLU), second segment (H2, W2, C2, stride2)
 RING = {
@@ -54,87 +51,8 @@ TILE = {
 }
 CASES = {**RING, **TILE}
 
-_INPUTS = {}
-
-
-def inputs(name, scale=1.0):
-    """Seeded tensors and the float64 reference of one case (computed once, never changed)."""
-    if (name, scale) in _INPUTS:
-        return _INPUTS[(name, scale)]
-    B, H, W, Cin, Cout, stride, pad, dil, relu, res, seg2 = CASES[name]
-    g = torch.Generator().manual_seed(4099 + 3 * H + 5 * W + Cin + 7 * Cout + 11 * B)
-    x = F.relu(torch.randn(B, Cin, H, W, generator=g)) * scale
-    w = torch.randn(Cout, Cin, 3, 3, generator=g) / (Cin * 9) ** 0.5
-    b = torch.randn(Cout, generator=g) * scale
-    ref = F.conv2d(x.double(), w.double(), b.double(), stride, pad, dil)
-    x2 = w2 = None
-    if seg2 is not None:
-        H2, W2, C2, s2 = seg2
-        x2 = F.relu(torch.randn(B, C2, H2, W2, generator=g)) * scale
-        w2 = torch.randn(Cout, C2, generator=g) / C2 ** 0.5
-        ref = ref + F.conv2d(x2.double(), w2.double().view(Cout, C2, 1, 1), None, s2, 0)
-    if relu:
-        ref = F.relu(ref)
-    r = None
-    if res:
-        r = torch.randn(ref.shape, generator=g) * scale
-        ref = ref + r.double()
-    _INPUTS[(name, scale)] = (x, w, b, r, x2, w2, ref.permute(0, 2, 3, 1).contiguous())
-    return _INPUTS[(name, scale)]
-
-
-def nhwc(t):
-    return None if t is None else t.permute(0, 2, 3, 1).contiguous().to(DEV)
-
-
-def run_wsplit(name, scale=1.0, ovf=None, poke=None):
-    """One upr_conv2d_nhwc_wsplit call (UPR_W64_RING / UPR_RING_SPLIT_LDS are read at the
-    call) -> (y, the kernel that ran)."""
-    from upr import runtime
-    _, _, _, _, Cout, stride, pad, dil, relu, _, seg2 = CASES[name]
-    x, w, b, r, x2, w2, _ = inputs(name, scale)
-    xd = nhwc(x)
-    if poke is not None:
-        xd[poke] = 70000.0
-    blob = runtime.pack_split_w(runtime.pack_conv_weight(w), 3, 3, w2).to(DEV)
-    y = runtime.conv2d_nhwc_wsplit(xd, blob, Cout, b.to(DEV), 3, 3, stride, pad, dil, residual=nhwc(r), relu=relu,
-                                   x2=nhwc(x2), stride2=seg2[3] if seg2 else 1, overflow=ovf)
-    return y, runtime.last_wsplit_kernel()
-
-
-def run_exact(name, scale=1.0):
-    """The same op on the exact fp32 kernels: the conv (+ bias, ReLU when there is
-    no second segment), the 1x1 segment as its own conv, the rest in torch."""
-    from upr import runtime
-    _, _, _, _, _, stride, pad, dil, relu, _, seg2 = CASES[name]
-    x, w, b, r, x2, w2, _ = inputs(name, scale)
-    wd, bd = runtime.pack_conv_weight(w).to(DEV), b.to(DEV)
-    if seg2 is None:
-        y = runtime.conv2d_nhwc(nhwc(x), wd, bd, 3, 3, stride, pad, dil, relu=relu)
-    else:
-        y = runtime.conv2d_nhwc(nhwc(x), wd, bd, 3, 3, stride, pad, dil)
-        y = y + runtime.conv2d_nhwc(nhwc(x2), w2.contiguous().to(DEV), None, 1, 1, seg2[3], 0, 1)
-        if relu:
-            y = F.relu(y)
-    if r is not None:
-        y = y + nhwc(r)
-    return y
-
-
-def errors(name, scale, kernel):
-    refn = inputs(name, scale)[-1]
-    ovf = torch.zeros(1, dtype=torch.int32, device=DEV)
-    y16, ran = run_wsplit(name, scale, ovf)
-    y32 = run_exact(name, scale)
-    torch.cuda.synchronize()
-    assert ran == kernel, f"{name}: ran on {ran}, expected {kernel}"
-    assert int(ovf.item()) == 0
-    assert y16.shape == refn.shape
-    e32 = (y32.double().cpu() - refn).abs().max().item()
-    e16 = (y16.double().cpu() - refn).abs().max().item()
-    print(f"w64 {kernel} {name} x{scale:g}: max|y| {refn.abs().max().item():.4g}  fp32 err {e32:.3e}  "
-          f"wsplit err {e16:.3e}  ratio {e16 / max(e32, 1e-300):.2f}")
-    return e16, e32
+_W = WsplitCases(CASES, lambda B, H, W, Cin, Cout: 4099 + 3 * H + 5 * W + Cin + 7 * Cout + 11 * B, "w64")
+inputs, run_wsplit, run_exact, errors = _W.inputs, _W.run_wsplit, _W.run_exact, _W.errors
 
 
 @pytest.mark.parametrize("name", list(RING))
@@ -220,26 +138,21 @@ def test_switch_keeps_the_tile_kernel(monkeypatch):
 # ---------------------------------------------------------------------------
 # model level
 # ---------------------------------------------------------------------------
-from test_gpu_split_w64 import fwd, make_handle, make_sd  # noqa: E402
-
-
 @pytest.mark.parametrize("shape", [(2, 64, 64), (3, 48, 80)])
 def test_model_ring_on_and_off(shape, monkeypatch):
     """UPR_W64_RING is read when the handle is created."""
     B, H, W = shape
     sd = make_sd(False, False)
     x = torch.rand(B, 3, H, W, generator=torch.Generator().manual_seed(11))
-    sd64 = {k: (v.double() if torch.is_floating_point(v) else v) for k, v in sd.items()}
-    with torch.no_grad():
-        ref = [o.double() for o in onet.forward(sd64, x.double(), False, False)]
+    ref = oracle_f64(sd, x, False, False, shape)
     xd = x.to(DEV)
     monkeypatch.delenv("UPR_RING_SPLIT_LDS", raising=False)
     monkeypatch.setenv("UPR_W64_RING", "1")
-    h_on = make_handle(sd, True, True, monkeypatch)
+    h_on = make_handle(sd, False, False, monkeypatch, split=True, regs=True, w64=True)
     monkeypatch.setenv("UPR_W64_RING", "0")
-    h_tile = make_handle(sd, True, True, monkeypatch)
+    h_tile = make_handle(sd, False, False, monkeypatch, split=True, regs=True, w64=True)
     monkeypatch.delenv("UPR_W64_RING")
-    h_exact = make_handle(sd, False, True, monkeypatch)
+    h_exact = make_handle(sd, False, False, monkeypatch, split=False, regs=True, w64=True)
     on, tile, exact = fwd(h_on, xd), fwd(h_tile, xd), fwd(h_exact, xd)
     for name, a, t, e, r in zip(("enhanced", "reflectance", "illumination"), on, tile, exact, ref):
         e_on = (a.double().cpu() - r).abs().max().item()

@@ -7,18 +7,14 @@ multiple of the fp32 MFMA path's error on the same inputs (4x: a CPU proxy of
 the arithmetic gives <= 1.7x, and 2-3x if fp16 subnormal operands were flushed;
 a broken split is off by 2^-11 relative, i.e. thousands of times).
 """
-import os
-
 import pytest
 import torch
 import torch.nn.functional as F
 
 from conftest import has_gpu
-from oracle import net as onet
+from split_cases import DEV, fwd, make_handle, make_sd, oracle_f64
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs a ROCm device")]
-
-DEV = "cuda:0"
 
 
 # ---------------------------------------------------------------------------
@@ -107,36 +103,6 @@ def test_split_round_trip_and_overflow_word():
 # ---------------------------------------------------------------------------
 # model level
 # ---------------------------------------------------------------------------
-def make_sd(pre, aspp, seed=0):
-    from models.model import UP_Retinex
-    torch.manual_seed(seed)
-    return {k: v.detach().clone() for k, v in UP_Retinex(use_preact=pre, use_aspp=aspp).eval().state_dict().items()}
-
-
-def make_handle(sd, pre, aspp, split, monkeypatch):
-    """UPR_FP32_SPLIT is read when the handle is created."""
-    from upr.runtime import ModelHandle
-    monkeypatch.setenv("UPR_FP32_SPLIT", "1" if split else "0")
-    return ModelHandle(sd, pre, aspp, torch.float32, torch.device(DEV))
-
-
-def fwd(h, x):
-    out = h.forward(x)
-    torch.cuda.synchronize()
-    return [o.clone() for o in out]
-
-
-_F64 = {}
-
-
-def oracle_f64(sd, x, pre, aspp, key):
-    if key not in _F64:
-        sd64 = {k: (v.double() if torch.is_floating_point(v) else v) for k, v in sd.items()}
-        with torch.no_grad():
-            _F64[key] = [o.double() for o in onet.forward(sd64, x.double(), pre, aspp)]
-    return _F64[key]
-
-
 @pytest.mark.parametrize("shape", [(3, 48, 80), (2, 64, 64)])
 def test_model_split_vs_exact(shape, monkeypatch):
     B, H, W = shape
@@ -144,8 +110,8 @@ def test_model_split_vs_exact(shape, monkeypatch):
     x = torch.rand(B, 3, H, W, generator=torch.Generator().manual_seed(11))
     ref = oracle_f64(sd, x, False, False, shape)
     xd = x.to(DEV)
-    h_on = make_handle(sd, False, False, True, monkeypatch)
-    h_off = make_handle(sd, False, False, False, monkeypatch)
+    h_on = make_handle(sd, False, False, monkeypatch, split=True)
+    h_off = make_handle(sd, False, False, monkeypatch, split=False)
     assert h_on.split_state() == 1 and h_off.split_state() == 0
     on = fwd(h_on, xd)
     off = fwd(h_off, xd)
@@ -171,8 +137,8 @@ def test_model_split_vs_exact(shape, monkeypatch):
 def test_preact_model_keeps_exact_path(monkeypatch):
     sd = make_sd(True, False, seed=3)
     xd = torch.rand(2, 3, 64, 64, generator=torch.Generator().manual_seed(12)).to(DEV)
-    h_on = make_handle(sd, True, False, True, monkeypatch)
-    h_off = make_handle(sd, True, False, False, monkeypatch)
+    h_on = make_handle(sd, True, False, monkeypatch, split=True)
+    h_off = make_handle(sd, True, False, monkeypatch, split=False)
     assert h_on.split_state() == 0 and h_off.split_state() == 0
     for a, b in zip(fwd(h_on, xd), fwd(h_off, xd)):
         assert torch.equal(a, b)
@@ -186,8 +152,8 @@ def test_overflow_switches_to_exact_plan(monkeypatch):
     sd = make_sd(False, False, seed=4)
     sd["ie_net.enc2.bn1.weight"] = sd["ie_net.enc2.bn1.weight"] * 1.0e7
     xd = torch.rand(2, 3, 64, 64, generator=torch.Generator().manual_seed(13)).to(DEV)
-    h_on = make_handle(sd, False, False, True, monkeypatch)
-    h_off = make_handle(sd, False, False, False, monkeypatch)
+    h_on = make_handle(sd, False, False, monkeypatch, split=True)
+    h_off = make_handle(sd, False, False, monkeypatch, split=False)
     assert h_on.split_state() == 1
     fwd(h_on, xd)
     second = fwd(h_on, xd)

@@ -11,44 +11,17 @@ relative, thousands of times; flushed fp16 subnormals show at scale 2^-12).
 """
 import pytest
 import torch
-import torch.nn.functional as F
 
 from conftest import has_gpu
-from oracle import net as onet
+from split_cases import DEV, REGION, RING_CASES, fwd, make_handle, make_sd, oracle_f64, regs_ops, ring_inputs
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs a ROCm device")]
-
-DEV = "cuda:0"
 
 
 # ---------------------------------------------------------------------------
 # op level: the row ring (3x3, stride 1, pad 1, Cin 32)
 # ---------------------------------------------------------------------------
-RING_CASES = [
-    # B, H, W, Cout, relu, residual
-    (1, 4, 16, 32, False, False),   # the smallest unit the ring takes
-    (2, 6, 40, 32, True, False),    # partial last step, partial second strip, image boundary
-    (2, 9, 72, 64, True, False),    # four channel tiles (W_lo from LDS), three strips
-    (2, 8, 48, 32, False, True),    # residual landing zone
-]
-SCALED = [(RING_CASES[1], 2.0 ** -12), (RING_CASES[1], 300.0)]
-
-
-def ring_inputs(case, scale):
-    B, H, W, Cout, relu, res = case
-    Cin = 32
-    g = torch.Generator().manual_seed(4321 + 7 * Cout + H + 3 * W)
-    x = F.relu(torch.randn(B, Cin, H, W, generator=g)) * scale
-    w = torch.randn(Cout, Cin, 3, 3, generator=g) / (Cin * 9) ** 0.5
-    b = torch.randn(Cout, generator=g) * scale
-    ref = F.conv2d(x.double(), w.double(), b.double(), 1, 1)
-    r = None
-    if res:
-        r = torch.randn(ref.shape, generator=g) * scale
-        ref = ref + r.double()
-    if relu:
-        ref = F.relu(ref)
-    return x, w, b, r, ref.permute(0, 2, 3, 1)
+SCALED = [(RING_CASES[1], 2.0 ** -12), (RING_CASES[1], 300.0)]  # (the table: split_cases.RING_CASES)
 
 
 def run_ring_case(case, scale):
@@ -140,65 +113,16 @@ def test_regs_overflow_word():
 # ---------------------------------------------------------------------------
 # model level
 # ---------------------------------------------------------------------------
-REGION = ["ie_net." + n for n in (
-    "enc2.conv1", "enc2.conv2", "enc3.conv1", "enc3.conv2", "bottleneck.0.conv1", "bottleneck.0.conv2",
-    "bottleneck.1.conv1", "bottleneck.1.conv2", "dec3.up", "dec3.conv.0", "dec3.conv.3")]
-
-
-def regs_ops(H, W):
-    """The ops that run split in registers at an H x W input: the row ring takes
-    outputs of at least 4 rows and 16 columns (the FAM scales are H, H/4, H/16)."""
-    names = ["ie_net.dec1.conv.0", "ie_net.dec1.conv.3", "ie_net.residual_head"]
-    for p, sh in (("scale1.2", 0), ("scale2.3", 2), ("scale3.3", 4)):
-        h, w = H, W
-        for _ in range(sh // 2):
-            h, w = (h // 2) // 2, (w // 2) // 2
-        if h >= 4 and w >= 16:
-            names += [p + ".branch34_conv1", p + ".fusion.h3x", p + ".fusion.h4"]
-    return sorted(names)
-
-
-def make_sd(pre, aspp, seed=0):
-    from models.model import UP_Retinex
-    torch.manual_seed(seed)
-    return {k: v.detach().clone() for k, v in UP_Retinex(use_preact=pre, use_aspp=aspp).eval().state_dict().items()}
-
-
-def make_handle(sd, pre, aspp, split, regs, monkeypatch, dtype=torch.float32):
-    """UPR_FP32_SPLIT and UPR_FP32_SPLIT_REGS are read when the handle is created."""
-    from upr.runtime import ModelHandle
-    monkeypatch.setenv("UPR_FP32_SPLIT", "1" if split else "0")
-    monkeypatch.setenv("UPR_FP32_SPLIT_REGS", "1" if regs else "0")
-    return ModelHandle(sd, pre, aspp, dtype, torch.device(DEV))
-
-
-def fwd(h, x):
-    out = h.forward(x)
-    torch.cuda.synchronize()
-    return [o.clone() for o in out]
-
-
-_F64 = {}
-
-
-def oracle_f64(sd, x, key):
-    if key not in _F64:
-        sd64 = {k: (v.double() if torch.is_floating_point(v) else v) for k, v in sd.items()}
-        with torch.no_grad():
-            _F64[key] = [o.double() for o in onet.forward(sd64, x.double(), False, False)]
-    return _F64[key]
-
-
 @pytest.mark.parametrize("shape", [(3, 48, 80), (2, 64, 64)])
 def test_model_regs_vs_exact(shape, monkeypatch):
     B, H, W = shape
     sd = make_sd(False, False)
     x = torch.rand(B, 3, H, W, generator=torch.Generator().manual_seed(11))
-    ref = oracle_f64(sd, x, shape)
+    ref = oracle_f64(sd, x, False, False, shape)
     xd = x.to(DEV)
-    h_on = make_handle(sd, False, False, True, True, monkeypatch)
-    h_noregs = make_handle(sd, False, False, True, False, monkeypatch)
-    h_off = make_handle(sd, False, False, False, True, monkeypatch)
+    h_on = make_handle(sd, False, False, monkeypatch, split=True, regs=True)
+    h_noregs = make_handle(sd, False, False, monkeypatch, split=True, regs=False)
+    h_off = make_handle(sd, False, False, monkeypatch, split=False, regs=True)
     assert h_on.split_state() == 1 and h_noregs.split_state() == 1 and h_off.split_state() == 0
     assert h_on.op_forms() == []
     on = fwd(h_on, xd)
@@ -239,8 +163,8 @@ def test_overflow_in_a_regs_op_switches_to_exact_plan(monkeypatch):
     sd = make_sd(False, False, seed=4)
     sd["ie_net.dec1.conv.1.weight"] = sd["ie_net.dec1.conv.1.weight"] * 1.0e7
     xd = torch.rand(2, 3, 64, 64, generator=torch.Generator().manual_seed(13)).to(DEV)
-    h_on = make_handle(sd, False, False, True, True, monkeypatch)
-    h_off = make_handle(sd, False, False, False, True, monkeypatch)
+    h_on = make_handle(sd, False, False, monkeypatch, split=True, regs=True)
+    h_off = make_handle(sd, False, False, monkeypatch, split=False, regs=True)
     assert h_on.split_state() == 1
     fwd(h_on, xd)
     second = fwd(h_on, xd)
@@ -255,8 +179,8 @@ def test_other_models_untouched(pre, dtype, monkeypatch):
     """PreAct and fp16 models are bit-equal with the switch on and off and run every op in form 0."""
     sd = make_sd(pre, False, seed=3)
     xd = torch.rand(2, 3, 64, 64, generator=torch.Generator().manual_seed(12)).to(DEV).to(dtype)
-    h_on = make_handle(sd, pre, False, True, True, monkeypatch, dtype)
-    h_off = make_handle(sd, pre, False, True, False, monkeypatch, dtype)
+    h_on = make_handle(sd, pre, False, monkeypatch, dtype, split=True, regs=True)
+    h_off = make_handle(sd, pre, False, monkeypatch, dtype, split=True, regs=False)
     for a, b in zip(fwd(h_on, xd), fwd(h_off, xd)):
         assert torch.equal(a, b)
     assert set(dict(h_on.op_forms()).values()) == {0}

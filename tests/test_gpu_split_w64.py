@@ -13,14 +13,11 @@ subnormals show at scale 2^-12).
 """
 import pytest
 import torch
-import torch.nn.functional as F
 
 from conftest import has_gpu
-from oracle import net as onet
+from split_cases import DEV, REGION, WsplitCases, fwd, make_handle, make_sd, oracle_f64, regs_ops
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs a ROCm device")]
-
-DEV = "cuda:0"
 
 # ---------------------------------------------------------------------------
 # op level: each shape is the smallest that reaches one hazard of a 256-pixel x
@@ -35,83 +32,12 @@ CASES = {
     "two_n_tiles": (1, 8, 16, 64, 128, 1, False, False, None),
 }
 
-_INPUTS = {}
-
-
-def inputs(name, scale):
-    """Seeded tensors and the float64 reference of one case (computed once)."""
-    if (name, scale) in _INPUTS:
-        return _INPUTS[(name, scale)]
-    B, H, W, Cin, Cout, stride, relu, res, seg2 = CASES[name]
-    g = torch.Generator().manual_seed(977 + 3 * H + 5 * W + Cin + 7 * Cout)
-    x = F.relu(torch.randn(B, Cin, H, W, generator=g)) * scale
-    w = torch.randn(Cout, Cin, 3, 3, generator=g) / (Cin * 9) ** 0.5
-    b = torch.randn(Cout, generator=g) * scale
-    ref = F.conv2d(x.double(), w.double(), b.double(), stride, 1)
-    x2 = w2 = None
-    if seg2 is not None:
-        H2, W2, C2, s2 = seg2
-        x2 = F.relu(torch.randn(B, C2, H2, W2, generator=g)) * scale
-        w2 = torch.randn(Cout, C2, generator=g) / C2 ** 0.5
-        ref = ref + F.conv2d(x2.double(), w2.double().view(Cout, C2, 1, 1), None, s2, 0)
-    if relu:
-        ref = F.relu(ref)
-    r = None
-    if res:
-        r = torch.randn(ref.shape, generator=g) * scale
-        ref = ref + r.double()
-    _INPUTS[(name, scale)] = (x, w, b, r, x2, w2, ref.permute(0, 2, 3, 1).contiguous())
-    return _INPUTS[(name, scale)]
-
-
-def nhwc(t):
-    return None if t is None else t.permute(0, 2, 3, 1).contiguous().to(DEV)
+_W = WsplitCases(CASES, lambda B, H, W, Cin, Cout: 977 + 3 * H + 5 * W + Cin + 7 * Cout, "wsplit conv")
+errors = _W.errors
 
 
 def run_wsplit(name, scale, ovf=None, poke=None):
-    from upr import runtime
-    _, _, _, _, Cout, stride, relu, _, seg2 = CASES[name]
-    x, w, b, r, x2, w2, _ = inputs(name, scale)
-    xd = nhwc(x)
-    if poke is not None:
-        xd[poke] = 70000.0
-    blob = runtime.pack_split_w(runtime.pack_conv_weight(w), 3, 3, w2).to(DEV)
-    return runtime.conv2d_nhwc_wsplit(xd, blob, Cout, b.to(DEV), 3, 3, stride, 1, 1, residual=nhwc(r), relu=relu,
-                                      x2=nhwc(x2), stride2=seg2[3] if seg2 else 1, overflow=ovf)
-
-
-def run_exact(name, scale):
-    """The same op on the exact fp32 kernels: the conv (+ bias, ReLU when there is
-    no second segment), the 1x1 segment as its own conv, the rest in torch."""
-    from upr import runtime
-    _, _, _, _, _, stride, relu, _, seg2 = CASES[name]
-    x, w, b, r, x2, w2, _ = inputs(name, scale)
-    wd, bd = runtime.pack_conv_weight(w).to(DEV), b.to(DEV)
-    if seg2 is None:
-        y = runtime.conv2d_nhwc(nhwc(x), wd, bd, 3, 3, stride, 1, 1, relu=relu)
-    else:
-        y = runtime.conv2d_nhwc(nhwc(x), wd, bd, 3, 3, stride, 1, 1)
-        y = y + runtime.conv2d_nhwc(nhwc(x2), w2.contiguous().to(DEV), None, 1, 1, seg2[3], 0, 1)
-        if relu:
-            y = F.relu(y)
-    if r is not None:
-        y = y + nhwc(r)
-    return y
-
-
-def errors(name, scale):
-    refn = inputs(name, scale)[-1]
-    ovf = torch.zeros(1, dtype=torch.int32, device=DEV)
-    y16 = run_wsplit(name, scale, ovf)
-    y32 = run_exact(name, scale)
-    torch.cuda.synchronize()
-    assert int(ovf.item()) == 0
-    assert y16.shape == refn.shape
-    e32 = (y32.double().cpu() - refn).abs().max().item()
-    e16 = (y16.double().cpu() - refn).abs().max().item()
-    print(f"wsplit conv {name} x{scale:g}: max|y| {refn.abs().max().item():.4g}  fp32 err {e32:.3e}  "
-          f"wsplit err {e16:.3e}  ratio {e16 / max(e32, 1e-300):.2f}")
-    return e16, e32
+    return _W.run_wsplit(name, scale, ovf, poke)[0]
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -164,30 +90,7 @@ def test_wsplit_refuses_what_its_kernel_does_not_take():
 # ---------------------------------------------------------------------------
 # model level
 # ---------------------------------------------------------------------------
-from test_gpu_split_regs import REGION, regs_ops  # noqa: E402  (the pinned sets of form-1 and form-2 ops)
-
 W64 = ["ie_net." + n for n in ("enc1.conv1", "enc1.conv2", "dec2.conv.0", "dec2.conv.3")]
-
-
-def make_sd(pre, aspp, seed=0):
-    from models.model import UP_Retinex
-    torch.manual_seed(seed)
-    return {k: v.detach().clone() for k, v in UP_Retinex(use_preact=pre, use_aspp=aspp).eval().state_dict().items()}
-
-
-def make_handle(sd, split, w64, monkeypatch, regs=True):
-    """UPR_FP32_SPLIT, UPR_FP32_SPLIT_REGS and UPR_FP32_SPLIT_W64 are read when the handle is created."""
-    from upr.runtime import ModelHandle
-    monkeypatch.setenv("UPR_FP32_SPLIT", "1" if split else "0")
-    monkeypatch.setenv("UPR_FP32_SPLIT_REGS", "1" if regs else "0")
-    monkeypatch.setenv("UPR_FP32_SPLIT_W64", "1" if w64 else "0")
-    return ModelHandle(sd, False, False, torch.float32, torch.device(DEV))
-
-
-def fwd(h, x):
-    out = h.forward(x)
-    torch.cuda.synchronize()
-    return [o.clone() for o in out]
 
 
 @pytest.mark.parametrize("shape", [(3, 48, 80), (2, 64, 64)])
@@ -195,14 +98,12 @@ def test_model_w64_vs_exact(shape, monkeypatch):
     B, H, W = shape
     sd = make_sd(False, False)
     x = torch.rand(B, 3, H, W, generator=torch.Generator().manual_seed(11))
-    sd64 = {k: (v.double() if torch.is_floating_point(v) else v) for k, v in sd.items()}
-    with torch.no_grad():
-        ref = [o.double() for o in onet.forward(sd64, x.double(), False, False)]
+    ref = oracle_f64(sd, x, False, False, shape)
     xd = x.to(DEV)
-    h_on = make_handle(sd, True, True, monkeypatch)
-    h_now64 = make_handle(sd, True, False, monkeypatch)
-    h_noregs = make_handle(sd, True, True, monkeypatch, regs=False)
-    h_off = make_handle(sd, False, True, monkeypatch)
+    h_on = make_handle(sd, False, False, monkeypatch, split=True, regs=True, w64=True)
+    h_now64 = make_handle(sd, False, False, monkeypatch, split=True, regs=True, w64=False)
+    h_noregs = make_handle(sd, False, False, monkeypatch, split=True, regs=False, w64=True)
+    h_off = make_handle(sd, False, False, monkeypatch, split=False, regs=True, w64=True)
     on, now64, noregs, off = fwd(h_on, xd), fwd(h_now64, xd), fwd(h_noregs, xd), fwd(h_off, xd)
     assert h_on.split_state() == 1
     for name, a, b, r in zip(("enhanced", "reflectance", "illumination"), on, off, ref):
@@ -244,12 +145,12 @@ def test_overflow_in_a_w64_op_switches_to_exact_plan(monkeypatch):
     sd["ie_net.dec2.conv.4.weight"] = sd["ie_net.dec2.conv.4.weight"] * 1.0e-7
     xd = torch.rand(2, 3, 64, 64, generator=torch.Generator().manual_seed(13)).to(DEV)
     # only dec2.conv.3 reads the large values: with the four kept exact nothing overflows
-    h_now64 = make_handle(sd, True, False, monkeypatch)
+    h_now64 = make_handle(sd, False, False, monkeypatch, split=True, regs=True, w64=False)
     fwd(h_now64, xd)
     fwd(h_now64, xd)
     assert h_now64.split_state() == 1
-    h_on = make_handle(sd, True, True, monkeypatch)
-    h_off = make_handle(sd, False, True, monkeypatch)
+    h_on = make_handle(sd, False, False, monkeypatch, split=True, regs=True, w64=True)
+    h_off = make_handle(sd, False, False, monkeypatch, split=False, regs=True, w64=True)
     assert h_on.split_state() == 1
     fwd(h_on, xd)
     assert dict(h_on.op_forms())["ie_net.dec2.conv.3"] == 3
