@@ -165,9 +165,26 @@ int upr_t_conv_mfma16(const float* x, int B, int H, int W, int Cin, int x_cs, in
                       void* y16, int y16_cs, void* stream);
 /* y[i] = (fp16) x[i], n elements. */
 int upr_t_cast_f16(const float* x, void* y, size_t n, void* stream);
-/* Weight gradient of an NHWC conv as an MFMA GEMM over pixels:
+/* The MFMA-path weight gradients: upr_t_conv_wgrad, upr_t_conv_wgrad16 and
+ * upr_t_conv_wgrad_into.  All three check their arguments the same way and
+ * queue nothing, write nothing, when a check fails:
+ *   UPR_ERR_ARG    a NULL dy or dwp / dw, a NULL x (with no x16 where one is
+ *                  taken); B <= 0; Cin or Cout <= 0 or no multiple of 32; H, W,
+ *                  Ho, Wo, kh, kw, stride or dil <= 0; pad < 0; a channel slice
+ *                  outside its buffer (x_coff or dy_coff < 0, x_cs < x_coff +
+ *                  Cin, dy_cs < dy_coff + Cout);
+ *   UPR_ERR_SHAPE  Ho != (H + 2 pad - dil (kh - 1) - 1) / stride + 1, the same
+ *                  for Wo, or a window larger than the padded image.
+ * Each picks a kernel by shape, strides and pointer alignment;
+ * upr_t_conv_wgrad_ran tells which one ran.
+ *
+ * Weight gradient of an NHWC conv as an MFMA GEMM over pixels:
  * dwp[co][(ky,kx,ci)] += sum_p dy[p][co] * x[window(p, ky, kx)][ci]
- * (packed layout of upr_t_pack_weight mode 0).  Cin, Cout multiples of 32. */
+ * (packed layout of upr_t_pack_weight mode 0).  Cin, Cout multiples of 32.
+ * fp32 operands and accumulation: a split-K GEMM whose partial tiles are added
+ * in a fixed order (the same bits run to run), or -- x, dy or dwp off 16-byte
+ * alignment, strides / offsets no multiple of 4 -- a per-tap kernel that adds
+ * its pixel blocks with fp32 atomics. */
 int upr_t_conv_wgrad(const float* x, int B, int H, int W, int Cin, int x_cs, int x_coff, const float* dy, int Ho,
                      int Wo, int Cout, int dy_cs, int dy_coff, int kh, int kw, int stride, int pad, int dil,
                      float* dwp, void* stream);
@@ -176,7 +193,9 @@ int upr_t_conv_wgrad(const float* x, int B, int H, int W, int Cin, int x_cs, int
  * accumulation (v_mfma_f32_16x16x32_f16).  x16: the compact fp16 copy
  * [B][H][W][Cin] of x made by the AMP forward (upr_t_conv_mfma16), or NULL
  * (x is cast into a stream-ordered temporary).  Shapes the fp16 kernel does
- * not take (Wo % 64 != 0, ...) run the fp32 upr_t_conv_wgrad. */
+ * not take (Wo % 64 != 0, ...) run the fp32 upr_t_conv_wgrad.  That call then
+ * computes from the fp32 x and dy themselves, not from fp16-rounded values,
+ * whether or not x16 was given (x NULL: UPR_ERR_ARG, nothing written). */
 int upr_t_conv_wgrad16(const float* x, const void* x16, int B, int H, int W, int Cin, int x_cs, int x_coff,
                        const float* dy, int Ho, int Wo, int Cout, int dy_cs, int dy_coff, int kh, int kw, int stride,
                        int pad, int dil, float* dwp, void* stream);
@@ -203,10 +222,34 @@ int upr_t_conv_mfma16_relu_bwd_cs(const void* x16, int x16_cs, int B, int H, int
  * only): dy's fp16 copy = (half)dy in dy's own layout (element (pixel p,
  * channel c) at dy16[p * dy_cs + dy_coff + c]: a channel slice of a concat's
  * gradient reads the concat's copy), read instead of dy (the same operand
- * values, half the bytes).  dw needs no alignment. */
+ * values, half the bytes; a dy16 off 8-byte alignment is ignored and dy
+ * read).  dw needs no alignment.  When x16 is given but the fp16 kernel does
+ * not take the shape, the gradient is computed from the fp32 x and dy
+ * themselves, not from fp16-rounded values (x NULL: UPR_ERR_ARG, nothing
+ * written); operands the split-K GEMM does not take either go through the
+ * packed form in scratch and are added to dw by upr_t_unpack_grad. */
 int upr_t_conv_wgrad_into(const float* x, const void* x16, int B, int H, int W, int Cin, int x_cs, int x_coff,
                           const float* dy, const void* dy16, int Ho, int Wo, int Cout, int dy_cs, int dy_coff, int kh,
                           int kw, int stride, int pad, int dil, float* dw, void* stream);
+/* Which kernel the calling thread's latest upr_t_conv_wgrad, _wgrad16 or
+ * _wgrad_into call ran last (thread-local; for _wgrad_into's scratch-and-
+ * unpack path the inner call's kernel).  kernel: UPR_WGRAD_NONE (no call yet,
+ * or the call was refused before a launch), _GEMM32 (wgrad_gemm_kernel<BM, BN>:
+ * t0 = BM, t1 = BN), _TAP32 (conv_wgrad_kernel, fp32 atomics: t0 = t1 = 32, the
+ * block's tile of one tap; splits = its pixel blocks), _IM2COL16
+ * (wgrad16_kernel<BM, NR>: t0 = BM, t1 = NR) or _HALO16 (wgrad16h_kernel<CIN,
+ * COUT, NTAP, RPW, D>: t0 = CIN, t1 = NTAP, t2 = D).  splits: the partial sums
+ * a weight is added from.  dy16: 1 when the kernel read dy's fp16 copy.
+ * Returns UPR_ERR_ARG for a NULL out. */
+#define UPR_WGRAD_NONE 0
+#define UPR_WGRAD_GEMM32 1
+#define UPR_WGRAD_TAP32 2
+#define UPR_WGRAD_IM2COL16 3
+#define UPR_WGRAD_HALO16 4
+typedef struct UprWgradRan {
+  int kernel, t0, t1, t2, splits, dy16;
+} UprWgradRan;
+int upr_t_conv_wgrad_ran(UprWgradRan* out);
 /* Weight layout transforms.  mode 0: [Co][Ci][kh][kw] -> [Co][(ky,kx,ci)];
  * mode 1: -> [Ci][(ky,kx,co)] spatially flipped (stride-1 dgrad as a conv);
  * mode 2: ConvTranspose [Ci][Co][2][2] -> [(a,b,co)][ci] (forward GEMM);

@@ -144,5 +144,9 @@ int wgrad_gemm(const float* x, int B, int H, int W, int Cin, int x_cs, int x_cof
 int wgrad16_gemm(const void* x16, int B, int H, int W, int Cin, const float* dy, int Ho, int Wo, int Cout, int dy_cs,
                  int dy_coff, int kh, int kw, int stride, int pad, int dil, float* dwp, hipStream_t st,
                  int torch_ci = 0, const void* dy16 = nullptr);
+// the calling thread's record for upr_t_conv_wgrad_ran: an entry clears it (kernel UPR_WGRAD_NONE),
+// the launcher that queues a weight-gradient kernel fills it in
+void wgrad_ran_set(int kernel, int t0 = 0, int t1 = 0, int t2 = 0, int splits = 0, int dy16 = 0);
+const UprWgradRan& wgrad_ran();
 
 }  // namespace upr

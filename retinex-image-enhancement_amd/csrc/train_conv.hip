@@ -472,6 +472,22 @@ static int direct_conv_args(const UprView* a, const UprView* b, const void* p, i
   return UPR_OK;
 }
 
+// The argument checks of upr_t_conv_wgrad / _wgrad16 / _wgrad_into beyond their
+// pointers; every one of them comes before anything is queued
+static int mfma_wgrad_args(int B, int H, int W, int Cin, int x_cs, int x_coff, int Ho, int Wo, int Cout, int dy_cs,
+                           int dy_coff, int kh, int kw, int stride, int pad, int dil) {
+  if (B <= 0 || Cin % 32 || Cout % 32 || Cin <= 0 || Cout <= 0) return UPR_ERR_ARG;
+  if (H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 || dil <= 0)
+    return UPR_ERR_ARG;
+  if (x_coff < 0 || dy_coff < 0 || (long long)x_cs < (long long)x_coff + Cin ||
+      (long long)dy_cs < (long long)dy_coff + Cout)
+    return UPR_ERR_ARG;
+  const long long eh = (long long)H + 2ll * pad - (long long)dil * (kh - 1) - 1;
+  const long long ew = (long long)W + 2ll * pad - (long long)dil * (kw - 1) - 1;
+  if (eh < 0 || ew < 0 || Ho != eh / stride + 1 || Wo != ew / stride + 1) return UPR_ERR_SHAPE;
+  return UPR_OK;
+}
+
 extern "C" {
 
 int upr_t_conv_direct(const UprView* x, int B, int H, int W, int Cin, const float* w, const float* bias, int Cout,
@@ -721,7 +737,10 @@ int upr_t_conv_mfma16_relu_bwd_cs(const void* x16, int x16_cs, int B, int H, int
 int upr_t_conv_wgrad(const float* x, int B, int H, int W, int Cin, int x_cs, int x_coff, const float* dy, int Ho,
                      int Wo, int Cout, int dy_cs, int dy_coff, int kh, int kw, int stride, int pad, int dil,
                      float* dwp, void* stream) {
-  if (!x || !dy || !dwp || B <= 0 || Cin % 32 || Cout % 32 || Cin <= 0 || Cout <= 0) return UPR_ERR_ARG;
+  wgrad_ran_set(UPR_WGRAD_NONE);
+  if (!x || !dy || !dwp) return UPR_ERR_ARG;
+  if (const int bad = mfma_wgrad_args(B, H, W, Cin, x_cs, x_coff, Ho, Wo, Cout, dy_cs, dy_coff, kh, kw, stride, pad, dil))
+    return bad;
   {
     const int rc = wgrad_gemm(x, B, H, W, Cin, x_cs, x_coff, dy, Ho, Wo, Cout, dy_cs, dy_coff, kh, kw, stride, pad, dil,
                               dwp, ST(stream));
@@ -733,13 +752,17 @@ int upr_t_conv_wgrad(const float* x, int B, int H, int W, int Cin, int x_cs, int
   dim3 grid((unsigned)chunks, Cout / 32, kh * kw * (Cin / 32));
   hipLaunchKernelGGL(conv_wgrad_kernel, grid, dim3(256), 0, ST(stream), x, B, H, W, Cin, x_cs, x_coff, dy, Ho, Wo,
                      Cout, dy_cs, dy_coff, kh, kw, stride, pad, dil, dwp);
+  wgrad_ran_set(UPR_WGRAD_TAP32, 32, 32, 0, (int)chunks);
   LAUNCH_CHECK();
 }
 
 int upr_t_conv_wgrad16(const float* x, const void* x16, int B, int H, int W, int Cin, int x_cs, int x_coff,
                        const float* dy, int Ho, int Wo, int Cout, int dy_cs, int dy_coff, int kh, int kw, int stride,
                        int pad, int dil, float* dwp, void* stream) {
-  if ((!x && !x16) || !dy || !dwp || B <= 0 || Cin % 32 || Cout % 32 || Cin <= 0 || Cout <= 0) return UPR_ERR_ARG;
+  wgrad_ran_set(UPR_WGRAD_NONE);
+  if ((!x && !x16) || !dy || !dwp) return UPR_ERR_ARG;
+  if (const int bad = mfma_wgrad_args(B, H, W, Cin, x_cs, x_coff, Ho, Wo, Cout, dy_cs, dy_coff, kh, kw, stride, pad, dil))
+    return bad;
   hipStream_t st = ST(stream);
   const bool fits = Wo % 64 == 0 && dy_cs % 4 == 0 && dy_coff % 4 == 0 && (uintptr_t)dy % 16 == 0 &&
                     (uintptr_t)dwp % 16 == 0 && (x16 || (x && x_cs % 8 == 0 && x_coff % 8 == 0 && (uintptr_t)x % 16 == 0));
@@ -765,7 +788,10 @@ int upr_t_conv_wgrad16(const float* x, const void* x16, int B, int H, int W, int
 int upr_t_conv_wgrad_into(const float* x, const void* x16, int B, int H, int W, int Cin, int x_cs, int x_coff,
                           const float* dy, const void* dy16, int Ho, int Wo, int Cout, int dy_cs, int dy_coff, int kh,
                           int kw, int stride, int pad, int dil, float* dw, void* stream) {
-  if ((!x && !x16) || !dy || !dw || B <= 0 || Cin % 32 || Cout % 32 || Cin <= 0 || Cout <= 0) return UPR_ERR_ARG;
+  wgrad_ran_set(UPR_WGRAD_NONE);
+  if ((!x && !x16) || !dy || !dw) return UPR_ERR_ARG;
+  if (const int bad = mfma_wgrad_args(B, H, W, Cin, x_cs, x_coff, Ho, Wo, Cout, dy_cs, dy_coff, kh, kw, stride, pad, dil))
+    return bad;
   hipStream_t st = ST(stream);
   if (x16) {
     const int rc = wgrad16_gemm(x16, B, H, W, Cin, dy, Ho, Wo, Cout, dy_cs, dy_coff, kh, kw, stride, pad, dil, dw, st,
@@ -790,6 +816,12 @@ int upr_t_conv_wgrad_into(const float* x, const void* x16, int B, int H, int W, 
                                   dil, tmp, stream);
   if (rc == UPR_OK) rc = upr_t_unpack_grad(tmp, dw, Cout, Cin, kh, kw, 0, 1, stream);
   return rc;
+}
+
+int upr_t_conv_wgrad_ran(UprWgradRan* out) {
+  if (!out) return UPR_ERR_ARG;
+  *out = wgrad_ran();
+  return UPR_OK;
 }
 
 int upr_t_pack_weight(const float* w, float* out, int Co, int Ci, int kh, int kw, int mode, void* stream) {

@@ -6,8 +6,9 @@
 //
 // * M = Cout, N = kh*kw*Cin, K = the B*Ho*Wo output pixels, split into
 //   `splits` contiguous pixel ranges.  Block tile BM x BN (4 waves, each a
-//   32 x 64 block of v_mfma_f32_32x32x2_f32 accumulators), K step = 32
-//   pixels.
+//   32 x 64 block of v_mfma_f32_32x32x2_f32 accumulators, two interleaved
+//   sets of them so that a split's chain of additions is halved), K step =
+//   32 pixels.
 // * Both operands global -> LDS by LDS-DMA into two stages (one barrier per
 //   step): A = the dy rows of the step's pixels (BM channels each), B = their
 //   im2col rows (BN/32 runs of 32 channels, each at its tap's shifted pixel;
@@ -31,6 +32,14 @@ typedef __attribute__((address_space(3))) void* lds_void_ptr_w2;
 __device__ __attribute__((aligned(128))) uint4 g_wg_zero[8];
 
 constexpr int WG_KP = 32;  // pixels per K step
+
+static thread_local UprWgradRan t_wgrad_ran = {UPR_WGRAD_NONE, 0, 0, 0, 0, 0};
+
+void wgrad_ran_set(int kernel, int t0, int t1, int t2, int splits, int dy16) {
+  t_wgrad_ran = UprWgradRan{kernel, t0, t1, t2, splits, dy16};
+}
+
+const UprWgradRan& wgrad_ran() { return t_wgrad_ran; }
 
 struct WgArgs {
   const float* x;
@@ -104,9 +113,13 @@ __global__ __launch_bounds__(256) void wgrad_gemm_kernel(WgArgs a) {
     }
   };
 
-  f32x16 acc0, acc1;
+  // two accumulators a tile, taking the pixel pairs of a step in turn and added at the end: one
+  // chain over a whole split (a rounding per pixel) missed the op-level bound at 70 pixels
+  f32x16 acc0[2], acc1[2];
 #pragma unroll
-  for (int e = 0; e < 16; ++e) { acc0[e] = 0.f; acc1[e] = 0.f; }
+  for (int c = 0; c < 2; ++c)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) { acc0[c][e] = 0.f; acc1[c][e] = 0.f; }
   const int half = lane >> 5, col = lane & 31;
 
   if (steps > 0) issue(0, 0);
@@ -122,8 +135,8 @@ __global__ __launch_bounds__(256) void wgrad_gemm_kernel(WgArgs a) {
       const float av = As[row * BM + wm * 32 + col];
       const float b0 = Bs[row * BN + wn * 64 + col];
       const float b1 = Bs[row * BN + wn * 64 + 32 + col];
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b0, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b1, acc1, 0, 0, 0);
+      acc0[s & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b0, acc0[s & 1], 0, 0, 0);
+      acc1[s & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b1, acc1[s & 1], 0, 0, 0);
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -132,8 +145,8 @@ __global__ __launch_bounds__(256) void wgrad_gemm_kernel(WgArgs a) {
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     const int row = (e & 3) + 8 * (e >> 2) + 4 * half;
-    sl[(size_t)row * a.ldn] = acc0[e];
-    sl[(size_t)row * a.ldn + 32] = acc1[e];
+    sl[(size_t)row * a.ldn] = acc0[0][e] + acc0[1][e];
+    sl[(size_t)row * a.ldn + 32] = acc1[0][e] + acc1[1][e];
   }
 }
 
@@ -217,6 +230,7 @@ static int launch_wgrad_gemm(WgArgs a, float* dwp, hipStream_t st, int torch_ci)
   if (!buf) return (int)hipErrorOutOfMemory;
   a.slab = (float*)buf;
   hipLaunchKernelGGL((wgrad_gemm_kernel<BM, BN>), dim3(tiles * splits), dim3(256), LDS, st, a);
+  wgrad_ran_set(UPR_WGRAD_GEMM32, BM, BN, 0, splits);
   return reduce_slabs(a.slab, splits, a.Cout, a.KT, a.ldn, dwp, torch_ci, st);
 }
 
@@ -466,6 +480,7 @@ static int launch_wgrad16(Wg16Args a, float* dwp, hipStream_t st, int torch_ci) 
   if (!buf) return (int)hipErrorOutOfMemory;
   a.slab = (float*)buf;
   hipLaunchKernelGGL((wgrad16_kernel<BM, NR>), dim3(tiles * splits), dim3(256), LDS, st, a);
+  wgrad_ran_set(UPR_WGRAD_IM2COL16, BM, NR, 0, splits, a.dy16 != nullptr);
   return reduce_slabs(a.slab, splits, a.Cout, a.KT, a.ldn, dwp, torch_ci, st);
 }
 
@@ -758,6 +773,7 @@ static int launch_wgrad16h(Wg16hArgs a, float* dwp, hipStream_t st, int torch_ci
     hipLaunchKernelGGL((wgrad16h_kernel<CIN, COUT, NTAP, RPW, D, true>), dim3(splits * a.ntg), dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL((wgrad16h_kernel<CIN, COUT, NTAP, RPW, D, false>), dim3(splits * a.ntg), dim3(256), 0, st, a);
+  wgrad_ran_set(UPR_WGRAD_HALO16, CIN, NTAP, D, splits, a.dy16 != nullptr);
   const int KT = C::TAPS * CIN;
   return reduce_slabs(a.slab, splits, COUT, KT, a.ldn, dwp, torch_ci, st);
 }

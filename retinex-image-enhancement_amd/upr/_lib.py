@@ -163,6 +163,20 @@ class UprPackJob(ctypes.Structure):
                 ("n", ctypes.c_int)]
 
 
+class UprWgradRan(ctypes.Structure):
+    """include/upr_train.h UprWgradRan: the kernel the latest MFMA-path weight gradient ran."""
+    _fields_ = [("kernel", ctypes.c_int), ("t0", ctypes.c_int), ("t1", ctypes.c_int), ("t2", ctypes.c_int),
+                ("splits", ctypes.c_int), ("dy16", ctypes.c_int)]
+
+
+# include/upr_train.h UPR_WGRAD_*: UprWgradRan.kernel
+UPR_WGRAD_NONE = 0
+UPR_WGRAD_GEMM32 = 1
+UPR_WGRAD_TAP32 = 2
+UPR_WGRAD_IM2COL16 = 3
+UPR_WGRAD_HALO16 = 4
+
+
 class UprAugParams(ctypes.Structure):
     """include/upr_train.h UprAugParams: one sample's augmentation record (40 bytes)."""
     _fields_ = [("flags", ctypes.c_uint32), ("gamma", ctypes.c_float), ("contrast", ctypes.c_float),
@@ -218,6 +232,7 @@ SIGNATURES.update({
                                            _i, _i, _p]),
     "upr_t_conv_wgrad_into": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
                                    _p, _p]),
+    "upr_t_conv_wgrad_ran": (_i, [ctypes.POINTER(UprWgradRan)]),
     "upr_t_pack_weight": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     "upr_t_pack_weights": (_i, [_p, _i, _i, _p]),
     "upr_t_unpack_grad": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
