@@ -473,6 +473,59 @@ int upr_jpeg_bound(int H, int W, int restart_rows, size_t* bytes_per_image, size
 int upr_jpeg_encode(const uint8_t* hwc_u8, int B, int H, int W, int quality, int restart_rows, uint8_t* out,
                     size_t out_stride, int64_t* sizes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Guided-filter restore of the letterboxed result to the source's size (the
+ * fast guided filter of He & Sun 2015, per channel; no reference counterpart:
+ * the reference records original_size and never uses it).  All pixel values
+ * are in 0..255 units; the arithmetic is stated exactly, and the device agrees
+ * with a numpy restatement byte for byte (tests/guided_ref.py).
+ *
+ * upr_guided_fit: guide_u8 and target_u8 are u8 [B,Hl,Wl,3], the letterboxed
+ * input and result as the output files hold them; only the content rectangle
+ * (top, left, nh, nw) of either is read.  Per image, channel c and content
+ * pixel (y, x), with the window of `radius` clipped to the content rectangle:
+ *   N (count), S_I, S_p, S_II, S_Ip: exact integer sums over the window of
+ *     I = guide[..., c] and p = target[..., c] (int32; the products in int64)
+ *   num = (double)(N S_Ip - S_I S_p)
+ *   den = (double)(N S_II - S_I S_I) + (eps * 65025.0) * (double)(N N)
+ *   a = num / den,  b = ((double)S_p - a (double)S_I) / (double)N
+ * in fp64, one operation at a time, no contraction.  The coefficient maps are
+ * the clipped window means A = hsum_then_vsum(a) / (double)N and B likewise:
+ * a pixel's row sum adds its in-range taps in increasing x starting from the
+ * first one, the column sum adds those row sums in increasing y (no running
+ * sums that subtract).  ab: fp64 [B,2,3,nh,nw] (A's three planes, then B's).
+ * workspace: upr_guided_fit_workspace(B, nh, nw) bytes (the a, b maps).
+ *
+ * upr_guided_apply: src_u8 is B u8 HWC images of one H x W, image b at
+ * src_u8 + b * src_stride (bytes, >= 3 H W; any alignment, the harness stages
+ * at multiples of 16).  Per full-resolution pixel (Y, X):
+ *   fy = ((double)Y + 0.5) * ((double)nh / (double)H) - 0.5, clamped to
+ *     [0, nh - 1]; y0 = floor(fy), y1 = min(y0 + 1, nh - 1), wy = fy - y0;
+ *     the same in x
+ *   v(M) = (1 - wy) ((1 - wx) M00 + wx M01) + wy ((1 - wx) M10 + wx M11)
+ *   enh = (uint8)floor(min(max(v(A) src + v(B), 0), 255) + 0.5)
+ * illu_lb_u8 (NULL: none) is the letterboxed illumination file's pixels, u8
+ * [B,Hl,Wl,3]; the map is not fitted: its full-resolution pixels are the same
+ * bilinear sample of channel 0 of its content pixels, floor(v(illu) + 0.5),
+ * replicated to RGB.  Outputs: enh_u8 [B,H,W,3], illu_u8 [B,H,W,3] (NULL: not
+ * written) and cmp_u8 [B,H,cmp_panels*W,3] (NULL: not written), the panels
+ * [src | enh] (2) or [src | enh | illu] (3) as in upr_panels_u8.  One pass:
+ * every source byte is read once, every output byte written once.
+ *
+ * Both: UPR_ERR_ARG, with nothing launched, for a NULL guide / target / ab /
+ * workspace / src / enh_u8, B < 1, a content rectangle outside Hl x Wl, radius
+ * outside 1..32, eps <= 0, an output that needs illu_lb_u8 without it,
+ * cmp_panels other than 2 / 3 with cmp_u8, src_stride < 3 H W; UPR_ERR_SHAPE
+ * for nh > H or nw > W (the restore never shrinks) or B beyond one launch's
+ * grid (10922 fit, 65535 apply); UPR_ERR_WORKSPACE for too little workspace. */
+size_t upr_guided_fit_workspace(int B, int nh, int nw);
+int upr_guided_fit(const uint8_t* guide_u8, const uint8_t* target_u8, int B, int Hl, int Wl, int top, int left,
+                   int nh, int nw, int radius, double eps, double* ab /* [B,2,3,nh,nw] */, void* workspace,
+                   size_t workspace_bytes, void* stream);
+int upr_guided_apply(const uint8_t* src_u8, size_t src_stride, int B, int H, int W, const double* ab,
+                     const uint8_t* illu_lb_u8 /* [B,Hl,Wl,3] or NULL */, int Hl, int Wl, int top, int left, int nh,
+                     int nw, uint8_t* enh_u8 /* [B,H,W,3] */, uint8_t* illu_u8 /* [B,H,W,3] or NULL */,
+                     uint8_t* cmp_u8 /* [B,H,P*W,3] or NULL */, int cmp_panels /* 2 or 3 */, void* stream);
+
 /* Host copies of the 8-bit Lab integer tables (for CPU-side verification):
  * gamma[256], cbrt[3072], yf[512], invgamma[4096] (uint16), rgb2xyz[9], xyz2rgb[9]. */
 void upr_lab_tables(uint16_t* gamma, uint16_t* cbrt, uint16_t* yf, uint16_t* invgamma, int32_t* rgb2xyz,

@@ -13,6 +13,10 @@ Intentional divergences, each a reference bug:
     raises TypeError);
   * enhance_batch_images takes optional use_preact/use_aspp/seed (defaults keep
     the reference behaviour: UP_Retinex() defaults, unseeded init).
+output_size="original" (an addition; the default "letterbox" changes nothing) writes the three
+files at the source's size: the letterboxed result is carried to the decoded image's pixels by
+the guided-filter restore of upr.guided (radius guided_radius, regulariser guided_eps), or, when
+the letterbox resized nothing, by cropping the bars away.
 enhance_batch_images(batch_size > 1) and main.py --infer_batch run the batched
 directory path (run_batched): files grouped by letterboxed shape (plan_batches),
 one upload + upr_letterbox_batch, one forward, one CLAHE, one upr_panels_u8 and
@@ -33,7 +37,7 @@ from models.model import UP_Retinex
 from enhancers.adaptive_params import AdaptiveParameterAdjuster
 from enhancers.multi_scale import MultiScaleEnhancer
 from enhancers.content_aware import ContentAwareEnhancer
-from utils.letterbox import letterbox_shape, letterbox_u8_batch, letterbox_u8_image
+from utils.letterbox import letterbox_content, letterbox_shape, letterbox_u8_batch, letterbox_u8_image
 
 # Writer threads running beside the GPU; 3 files per image.
 # png_encoder="host": each writer runs PIL's PNG encoder (it releases the GIL), ~90 /
@@ -60,6 +64,16 @@ def _check_format(image_format, jpeg_quality):
         raise ValueError(f"image_format must be one of {IMAGE_FORMATS}, got {image_format!r}")
     if image_format == "jpg" and not 1 <= int(jpeg_quality) <= 100:
         raise ValueError(f"jpeg_quality must be in 1..100, got {jpeg_quality!r}")
+
+
+OUTPUT_SIZES = ("letterbox", "original")
+
+
+def _check_output_size(output_size, guided_radius, guided_eps):
+    if output_size not in OUTPUT_SIZES:
+        raise ValueError(f"output_size must be one of {OUTPUT_SIZES}, got {output_size!r}")
+    from upr import guided
+    guided.check_params(guided_radius, guided_eps)
 
 
 def _writer_count():
@@ -198,17 +212,50 @@ def create_comparison(img_low, img_enhanced, save_path, writer=None, illu_map=No
         _emit(np.concatenate(panels, axis=1), save_path, "已保存对比图像", writer, image_format, jpeg_quality)
 
 
+def save_original_size(src_u8, img_low, img_enhanced, illu_map, paths, max_size=None, comparison=2, writer=None,
+                       png_encoder="host", image_format="png", jpeg_quality=95, guided_radius=4, guided_eps=1e-4):
+    """The three files of one image at the source's size (output_size="original").  src_u8: the
+    decoded uint8 HWC image; img_low / img_enhanced / illu_map: the [1,C,H',W'] letterboxed
+    tensors whose pixels the files hold with output_size="letterbox"; paths: (enhanced,
+    illumination, comparison) file names, the last unused with comparison=None (2: [input |
+    enhanced], 3: [input | enhanced | illumination]).  upr.guided.restore on those pixels."""
+    from upr import guided, runtime
+    H, W = src_u8.shape[:2]
+    content = letterbox_content((H, W), max_size if max_size is not None else (H, W), auto=True, scaleup=False)
+    dev = img_enhanced.device
+
+    def u8(t):
+        return runtime.to_u8_hwc(t.detach().squeeze(0).to(dev)).unsqueeze(0)
+
+    src = torch.from_numpy(np.ascontiguousarray(src_u8)).to(dev).unsqueeze(0)
+    outs = guided.restore(src, u8(img_low), u8(img_enhanced), u8(illu_map), content, guided_radius, guided_eps,
+                          comparison)
+    for arr, path, msg in zip(outs, paths, ("已保存", "已保存", "已保存对比图像")):
+        if arr is None:
+            continue
+        if png_encoder in _DEVICE_MATCHES:
+            _emit_device(arr[0], [(path, msg)], writer, png_encoder, image_format, jpeg_quality)
+        else:
+            _emit(arr[0].cpu().numpy(), path, msg, writer, image_format, jpeg_quality)
+
+
 def enhance_single_image(model, image_path, output_dir, device, max_size=None, enable_multi_scale=False,
                          enable_content_aware=False, adjuster=None, precision="fp32", _decoded=None, _writer=None,
-                         png_encoder="host", image_format="png", jpeg_quality=95):
+                         png_encoder="host", image_format="png", jpeg_quality=95, output_size="letterbox",
+                         guided_radius=4, guided_eps=1e-4):
     """Enhance one file and write {name}_enhanced/_illumination/_comparison.png (reference :135-199;
     .jpg with image_format="jpg", quality jpeg_quality).
     precision="fp16" runs the fp16 storage / fp16-MFMA graph (input cast to half).
     png_encoder="device" encodes the three files on the GPU (same pixels, larger files),
-    "device_lz" does so with LZ77 matching (same pixels, smaller files than "device")."""
+    "device_lz" does so with LZ77 matching (same pixels, smaller files than "device").
+    output_size="original" writes the three files at the source's size (save_original_size);
+    the returned tensors stay the letterboxed ones."""
     _check_encoder(png_encoder)
     _check_format(image_format, jpeg_quality)
+    _check_output_size(output_size, guided_radius, guided_eps)
     print(f"正在处理: {os.path.basename(image_path)}")
+    if _decoded is None and output_size == "original":
+        _decoded = _decode(image_path)
     img_low, _ = load_image(image_path, max_size, decoded=_decoded)
     if precision == "fp16":
         img_low = img_low.half()
@@ -228,6 +275,13 @@ def enhance_single_image(model, image_path, output_dir, device, max_size=None, e
     os.makedirs(output_dir, exist_ok=True)
     name = os.path.splitext(os.path.basename(image_path))[0]
     fmt = dict(image_format=image_format, jpeg_quality=jpeg_quality)
+    if output_size == "original":
+        save_original_size(_decoded[0], img_low, img_enhanced, illu_map,
+                           [os.path.join(output_dir, f"{name}_{kind}.{image_format}")
+                            for kind in ("enhanced", "illumination", "comparison")], max_size, 2, _writer,
+                           png_encoder, guided_radius=guided_radius, guided_eps=guided_eps, **fmt)
+        print("图像增强完成！")
+        return img_enhanced, illu_map
     save_image(img_enhanced, os.path.join(output_dir, f"{name}_enhanced.{image_format}"), _writer, png_encoder, **fmt)
     save_image(illu_map, os.path.join(output_dir, f"{name}_illumination.{image_format}"), _writer, png_encoder, **fmt)
     create_comparison(img_low, img_enhanced, os.path.join(output_dir, f"{name}_comparison.{image_format}"), _writer,
@@ -287,6 +341,21 @@ def letterboxed_shapes(image_files, max_size=None):
             w, h = im.size
         shapes.append(letterbox_shape((h, w), max_size if max_size is not None else (h, w), auto=True, scaleup=False))
     return shapes
+
+
+def batch_keys(image_files, max_size=None, output_size="letterbox"):
+    """plan_batches' key of every file: its letterboxed (H, W), followed with
+    output_size="original" by its own (H, W) -- a batch then holds images of one size, so its
+    restored outputs are one [B,H,W,3] tensor."""
+    keys = letterboxed_shapes(image_files, max_size)
+    if output_size != "original":
+        return keys
+    out = []
+    for path, key in zip(image_files, keys):
+        with Image.open(path) as im:
+            w, h = im.size
+        out.append(tuple(key) + (h, w))
+    return out
 
 
 class _StageClock:
@@ -396,7 +465,7 @@ def _finish_batch(job, writer, clock, image_lines, write_pixels=_write_png, trim
 
 def run_batched(model, image_files, output_dir, device, *, max_size=None, precision="fp32", png_encoder="host",
                 batch_size=8, decode_threads=4, clahe=True, comparison=2, image_lines=True, timings=None,
-                image_format="png", jpeg_quality=95):
+                image_format="png", jpeg_quality=95, output_size="letterbox", guided_radius=4, guided_eps=1e-4):
     """The batched directory pipeline behind enhance_batch_images(batch_size > 1) and
     main.py --mode predict --infer_batch: for every file {name}_enhanced.png,
     {name}_illumination.png and, unless comparison is None, {name}_comparison.png
@@ -416,13 +485,24 @@ def run_batched(model, image_files, output_dir, device, *, max_size=None, precis
     keep a buffer until the work queued on it has drained); only the PNG scratch is reused,
     stream-ordered.  timings: an optional dict that receives wall-time sums per stage
     (decode_wait, launch, drain_wait on the main thread; event_wait, copy_write over the
-    copier and writer threads)."""
-    from upr import runtime
+    copier and writer threads).
+
+    output_size="original": the files have the source's size.  Batches are keyed by
+    (letterboxed shape, original shape) (batch_keys), so mixed sizes form more batches; behind
+    upr_panels_u8 a batch runs upr.guided.restore on the staged sources (upr_guided_fit +
+    upr_guided_apply, or the crop when nothing was resized) and the encoders take its uniform
+    [B,H,W,3] outputs.  A batch's device and pinned host memory then grow with the
+    full-resolution pixel count: 3 + 3 * (2 + comparison) bytes per source pixel on the device
+    (the staged source and the three outputs) plus the encoders' buffers, not with the
+    letterboxed one."""
+    from upr import guided, runtime
     _check_encoder(png_encoder)
     _check_format(image_format, jpeg_quality)
+    _check_output_size(output_size, guided_radius, guided_eps)
+    original = output_size == "original"
     if comparison not in (None, 2, 3):
         raise ValueError(f"comparison must be None, 2 or 3, got {comparison!r}")
-    batches = plan_batches(letterboxed_shapes(image_files, max_size), batch_size)
+    batches = plan_batches(batch_keys(image_files, max_size, output_size), batch_size)
     dev = torch.device(device)
     if dev.type == "cuda" and dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -436,13 +516,22 @@ def run_batched(model, image_files, output_dir, device, *, max_size=None, precis
     n_files, count = len(image_files), 0
 
     def launch(idxs, images):
-        x = letterbox_u8_batch(images, max_size if max_size is not None else images[0].shape[:2], auto=True,
-                               scaleup=False, device=dev, dtype=dtype)
+        new_shape = max_size if max_size is not None else images[0].shape[:2]
+        x = letterbox_u8_batch(images, new_shape, auto=True, scaleup=False, device=dev, dtype=dtype,
+                               return_sources=original)
+        if original:
+            x, sources = x
         with torch.no_grad():
             enh, _, illu = model(x)
         if clahe:
             enh = adjuster.apply_clahe_enhancement(enh)
-        u8s = runtime.panels_u8(x, enh, illu, comparison)
+        if original:
+            enh_u8, illu_u8, _ = runtime.panels_u8(x, enh, illu, None)
+            u8s = guided.restore(sources, runtime.panels_u8(x, x, None, None)[0], enh_u8, illu_u8,
+                                 letterbox_content(images[0].shape[:2], new_shape, auto=True, scaleup=False),
+                                 guided_radius, guided_eps, comparison)
+        else:
+            u8s = runtime.panels_u8(x, enh, illu, comparison)
         outputs = []
         for (_, msg), u8 in zip(kinds, u8s):
             if png_encoder in _DEVICE_MATCHES:
@@ -506,7 +595,8 @@ def run_batched(model, image_files, output_dir, device, *, max_size=None, precis
 
 def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preact=True, use_aspp=True, seed=None,
                          precision="fp32", png_encoder="host", batch_size=1, decode_threads=4, timings=None,
-                         image_format="png", jpeg_quality=95):
+                         image_format="png", jpeg_quality=95, output_size="letterbox", guided_radius=4,
+                         guided_eps=1e-4):
     """Enhance every image of a directory (reference :202-250).
 
     batch_size=1 (the default) is the reference's one-image-at-a-time loop with a decode
@@ -517,9 +607,12 @@ def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preac
     image's files are exactly what the model, apply_clahe_enhancement and to_u8_hwc give for
     the batch tensor the image was placed in (measured on the GPU, no output byte depended on
     that batch: DESIGN.md 4.5).  timings: see run_batched (batched path only).  image_format="jpg"
-    writes the three files as .jpg of quality jpeg_quality."""
+    writes the three files as .jpg of quality jpeg_quality.  output_size="original" writes them
+    at each source's size (run_batched / save_original_size; guided_radius, guided_eps)."""
     _check_encoder(png_encoder)
     _check_format(image_format, jpeg_quality)
+    _check_output_size(output_size, guided_radius, guided_eps)
+    restore = dict(output_size=output_size, guided_radius=guided_radius, guided_eps=guided_eps)
     batch_size = int(batch_size)
     if batch_size < 1:
         raise ValueError(f"batch_size must be >= 1, got {batch_size}")
@@ -538,7 +631,7 @@ def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preac
         t0 = time.time()
         run_batched(model, image_files, output_dir, device, max_size=max_size, precision=precision,
                     png_encoder=png_encoder, batch_size=batch_size, decode_threads=decode_threads, clahe=True,
-                    comparison=2, timings=timings, image_format=image_format, jpeg_quality=jpeg_quality)
+                    comparison=2, timings=timings, image_format=image_format, jpeg_quality=jpeg_quality, **restore)
         total = time.time() - t0
         return _print_totals(len(image_files), total)
     # host pipeline around the device work: the next file is decoded on a
@@ -554,7 +647,7 @@ def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preac
                 nxt = reader.submit(_decode, image_files[i])
             enhance_single_image(model, path, output_dir, device, max_size, precision=precision, _decoded=decoded,
                                  _writer=writer, png_encoder=png_encoder, image_format=image_format,
-                                 jpeg_quality=jpeg_quality)
+                                 jpeg_quality=jpeg_quality, **restore)
             total += time.time() - t0
             print("-" * 50)
     _print_totals(len(image_files), total)

@@ -13,6 +13,10 @@ jpg writes the enhance / predict outputs as baseline 4:4:4 JPEGs, PIL's with
 Intentional divergences (reference bugs): a single-file --mode enhance works
 (reference main.py:240-249 raises TypeError); --mode predict unpacks the
 model's 3-tuple (reference predict.py:163 raises ValueError).
+--output_size {letterbox,original} (an addition, default letterbox) with
+--guided_radius R / --guided_eps E: original writes the enhance / predict files
+at the source's size -- the letterboxed result carried to the decoded pixels by
+the guided-filter restore (upr.guided), the bars cropped away.
 --infer_batch N (an addition, default 1) runs --mode enhance / predict on a
 directory N images at a time (enhancers/simple_enhance.py run_batched).
 --mode train runs trainers.train.train(args): images of --train_dir are decoded
@@ -38,7 +42,8 @@ if _HERE not in sys.path:
 
 from models.model import UP_Retinex  # noqa: E402
 from enhancers.simple_enhance import (enhance_single_image, enhance_batch_images, list_images,  # noqa: E402
-                                      load_image, save_image, create_comparison, run_batched)
+                                      load_image, save_image, create_comparison, run_batched, save_original_size,
+                                      _decode)
 from enhancers.adaptive_params import AdaptiveParameterAdjuster  # noqa: E402
 
 
@@ -99,6 +104,11 @@ def build_parser():
                         '--png_encoder chooses PIL or the device encoder for it as well)')
     p.add_argument('--jpeg_quality', type=_jpeg_quality, default=95,
                    help='--image_format jpg: quality 1..100, as PIL\'s `quality`')
+    p.add_argument('--output_size', choices=['letterbox', 'original'], default='letterbox',
+                   help='--mode enhance / predict: size of the output files: the letterboxed tensor\'s (default) '
+                        'or the source\'s (guided-filter restore of the result to the decoded image)')
+    p.add_argument('--guided_radius', type=int, default=4, help='--output_size original: window radius, 1..32')
+    p.add_argument('--guided_eps', type=float, default=1e-4, help='--output_size original: regulariser, > 0')
     p.add_argument('--infer_batch', type=int, default=1,
                    help='--mode enhance / predict on a directory: images per batch (1: one image at a time; '
                         '> 1: the batched path, files grouped by letterboxed shape, --num_workers decode threads; '
@@ -124,11 +134,16 @@ def _output_format(args):
     return dict(png_encoder=args.png_encoder, image_format=args.image_format, jpeg_quality=args.jpeg_quality)
 
 
+def _restore(args):
+    return dict(output_size=args.output_size, guided_radius=args.guided_radius, guided_eps=args.guided_eps)
+
+
 def _predict_one(model, path, args):
     """predictors/predict.py:144-191 predict_single_image: enhanced, illumination
     and the 3-panel [input | enhanced | illumination] comparison (:102-140; the
     1-channel map's channel mean is the map itself, replicated to RGB)."""
-    x, _ = load_image(path, args.max_size)
+    decoded = _decode(path)
+    x, _ = load_image(path, args.max_size, decoded=decoded)
     x = x.to(args.device)
     if args.precision == 'fp16':
         x = x.half()
@@ -137,6 +152,13 @@ def _predict_one(model, path, args):
     os.makedirs(args.output_dir, exist_ok=True)
     name = os.path.splitext(os.path.basename(path))[0]
     enc, ext = _output_format(args), args.image_format
+    if args.output_size == 'original':
+        save_original_size(decoded[0], x, enh, illu,
+                           [os.path.join(args.output_dir, f"{name}_{kind}.{ext}")
+                            for kind in ("enhanced", "illumination", "comparison")], args.max_size,
+                           None if args.no_comparison else 3, guided_radius=args.guided_radius,
+                           guided_eps=args.guided_eps, **enc)
+        return
     save_image(enh, os.path.join(args.output_dir, f"{name}_enhanced.{ext}"), **enc)
     save_image(illu, os.path.join(args.output_dir, f"{name}_illumination.{ext}"), **enc)
     if not args.no_comparison:
@@ -243,7 +265,8 @@ def main(argv=None):
         if p.is_dir() and args.infer_batch > 1:
             run_batched(model, files, args.output_dir, args.device, max_size=args.max_size, precision=args.precision,
                         batch_size=args.infer_batch, decode_threads=args.num_workers, clahe=False,
-                        comparison=None if args.no_comparison else 3, image_lines=False, **_output_format(args))
+                        comparison=None if args.no_comparison else 3, image_lines=False, **_output_format(args),
+                        **_restore(args))
         else:
             for f in files:
                 _predict_one(model, f, args)
@@ -257,12 +280,13 @@ def main(argv=None):
         enhance_single_image(model=model, image_path=str(p), output_dir=args.output_dir, device=args.device,
                              max_size=args.max_size, adjuster=AdaptiveParameterAdjuster(),
                              enable_multi_scale=args.multi_scale, enable_content_aware=args.content_aware,
-                             precision=args.precision, **_output_format(args))
+                             precision=args.precision, **_output_format(args), **_restore(args))
     elif p.is_dir():
         # reference: enhance_batch_images builds UP_Retinex() with its defaults (preact + ASPP)
         enhance_batch_images(input_dir=str(p), output_dir=args.output_dir, device=args.device,
                              max_size=args.max_size, seed=args.seed, precision=args.precision,
-                             batch_size=args.infer_batch, decode_threads=args.num_workers, **_output_format(args))
+                             batch_size=args.infer_batch, decode_threads=args.num_workers, **_output_format(args),
+                             **_restore(args))
     else:
         print(f"错误: 输入路径 '{args.input_path}' 不存在")
         return

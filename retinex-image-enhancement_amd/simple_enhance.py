@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Root enhance CLI (drop-in for the reference simple_enhance.py:17-94):
---input/--output/--max_size/--device/--multi_scale/--content_aware, plus --seed."""
+--input/--output/--max_size/--device/--multi_scale/--content_aware, plus --seed and
+--output_size {letterbox,original} with --guided_radius / --guided_eps (original: the files
+have the source's size, upr.guided)."""
 import argparse
 import os
 import sys
@@ -16,7 +18,7 @@ from enhancers.simple_enhance import enhance_single_image, enhance_batch_images 
 from models.model import UP_Retinex  # noqa: E402
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description='简化版UP-Retinex图像增强工具 (MI355X)')
     ap.add_argument('--input', type=str, required=True)
     ap.add_argument('--output', type=str, default='./results')
@@ -25,7 +27,17 @@ def main(argv=None):
     ap.add_argument('--multi_scale', action='store_true')
     ap.add_argument('--content_aware', action='store_true')
     ap.add_argument('--seed', type=int, default=None)
-    args = ap.parse_args(argv)
+    ap.add_argument('--output_size', choices=['letterbox', 'original'], default='letterbox',
+                    help='size of the output files: the letterboxed tensor\'s (default) or the source\'s '
+                         '(guided-filter restore)')
+    ap.add_argument('--guided_radius', type=int, default=4, help='--output_size original: window radius, 1..32')
+    ap.add_argument('--guided_eps', type=float, default=1e-4, help='--output_size original: regulariser, > 0')
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    restore = dict(output_size=args.output_size, guided_radius=args.guided_radius, guided_eps=args.guided_eps)
     if args.device is None:
         args.device = 'cuda' if torch.cuda.is_available() else 'cpu'
     print(f"使用设备: {args.device}")
@@ -39,10 +51,10 @@ def main(argv=None):
         model = UP_Retinex().to(args.device).eval()
         # the reference passes only enable_multi_scale here (--content_aware is ignored, :66-77)
         enhance_single_image(model=model, image_path=str(p), output_dir=args.output, device=args.device,
-                             max_size=args.max_size, enable_multi_scale=args.multi_scale)
+                             max_size=args.max_size, enable_multi_scale=args.multi_scale, **restore)
     elif p.is_dir():
         enhance_batch_images(input_dir=str(p), output_dir=args.output, device=args.device, max_size=args.max_size,
-                             seed=args.seed)
+                             seed=args.seed, **restore)
     else:
         print(f"错误: 输入路径 '{args.input}' 不是有效的文件或目录")
         return

@@ -132,6 +132,11 @@ SIGNATURES = {
     "upr_jpeg_bound": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
     "upr_jpeg_encode": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
                                 c_size_t, c_void_p]),
+    "upr_guided_fit_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "upr_guided_fit": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                               ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "upr_guided_apply": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                 c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "upr_lab_tables": (None, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "upr_retinex_decompose": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_void_p]),

@@ -15,6 +15,7 @@ reference returns CPU tensors; the harness moves them to the device next).
 cv2 is absent here, so the resize arithmetic is "parity unpinned" (DESIGN.md);
 its CPU restatement is oracle/letterbox.py (test infrastructure).
 """
+import collections
 import math
 
 import numpy as np
@@ -87,6 +88,17 @@ def letterbox_shape(shape, new_shape=640, auto=True, scale_fill=False, scaleup=T
     """(H, W) of the letterboxed image for an input of shape (H, W)."""
     (nw, nh), _, _, (top, bottom, left, right) = letterbox_geometry(shape, new_shape, auto, scale_fill, scaleup)
     return nh + top + bottom, nw + left + right
+
+
+def letterbox_content(shape, new_shape=640, auto=True, scaleup=True):
+    """(top, left, nh, nw): where the resized image lies in the letterboxed one, for an input of shape (H, W)."""
+    (nw, nh), _, _, (top, _bottom, left, _right) = letterbox_geometry(shape, new_shape, auto, False, scaleup)
+    return top, left, nh, nw
+
+
+class StagedSources(collections.namedtuple("StagedSources", "buf stride shape count")):
+    """The decoded u8 HWC images of a batch as letterbox_u8_batch staged them on the device:
+    image b of `count` images of one `shape` (H, W) starts at byte b * stride of `buf`."""
 
 
 def _device(t):
@@ -163,7 +175,7 @@ _ALIGN = 16
 
 
 def letterbox_u8_batch(images_u8, new_shape, *, auto=True, scaleup=False, device=None, dtype=torch.float32,
-                       color=(114, 114, 114)):
+                       color=(114, 114, 114), return_sources=False):
     """B decoded uint8 HWC images (any sizes that letterbox to ONE shape) -> the
     [B,3,H',W'] batch tensor, float32 (image b bit-identical to
     letterbox_u8_image's) or float16 (its .half()), in one upload and one launch
@@ -171,7 +183,9 @@ def letterbox_u8_batch(images_u8, new_shape, *, auto=True, scaleup=False, device
     pinned host buffer, every image at a 16-byte aligned offset, and go to the
     device in one non-blocking copy on the current stream; the tap tables are
     _device_taps'.  ValueError (naming the indices) when an image letterboxes to
-    another shape than the first."""
+    another shape than the first.  return_sources=True (the original-size outputs;
+    the images must then be of one size): returns (batch tensor, StagedSources), the
+    device copy of the decoded images that the launch read."""
     import ctypes
     from upr import runtime
     images = [np.ascontiguousarray(a) for a in images_u8]
@@ -186,6 +200,8 @@ def letterbox_u8_batch(images_u8, new_shape, *, auto=True, scaleup=False, device
     if bad:
         raise ValueError(f"images {bad} letterbox to {[shapes[i] for i in bad]}, image 0 to {shapes[0]}: "
                          f"one batch takes one shape")
+    if return_sources and any(a.shape != images[0].shape for a in images):
+        raise ValueError("return_sources needs images of one size")
     Ho, Wo = shapes[0]
     code = runtime.dtype_code(dtype)
     if device is not None:
@@ -228,4 +244,7 @@ def letterbox_u8_batch(images_u8, new_shape, *, auto=True, scaleup=False, device
         rc = L.lib().upr_letterbox_batch(base + rec_off, B, Ho, Wo, col, out.data_ptr(), code,
                                          torch.cuda.current_stream(dev).cuda_stream)
     L.check(rc, "upr_letterbox_batch")
+    if return_sources:
+        stride = offs[1] if B > 1 else rec_off
+        return out, StagedSources(stage, stride, tuple(images[0].shape[:2]), B)
     return out

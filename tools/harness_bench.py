@@ -6,12 +6,17 @@ enhance_batch_images over N synthetic low-light PNGs, images/s including IO.
   python tools/harness_bench.py --n 32 --size 512 [--precision fp16] [--png_encoder device|device_lz]
                                 [--batch_size 32 [--decode_threads 4]] [--mixed]
                                 [--image_format jpg [--jpeg_quality 95]]
+                                [--max_size 512 [--output_size original]] [--restore_compare [--rounds 3]]
 
 --batch_size > 1 runs the batched path and adds its per-stage wall-time sums
 (`stage_seconds`) to the JSON; --mixed writes images of --size and of half of it,
 interleaved, so the batches are formed from two shape buckets.  --image_format jpg
 writes the three output files per image as JPEGs (PIL with the host encoder, upr.jpeg
-with a device encoder) and adds the bytes written to the JSON.
+with a device encoder) and adds the bytes written to the JSON.  --max_size M letterboxes to M;
+--output_size original writes the files at the sources' size (the guided-filter restore).
+--restore_compare times the two routes to source-sized files on the same directory, alternating,
+--rounds times each: `--max_size M --output_size original` against no --max_size (the forward at
+the sources' own size); images/s as median and range of the rounds.
 """
 import argparse
 import contextlib
@@ -40,12 +45,16 @@ def write_inputs(src, n, size, mixed=False):
 
 
 def run(src, out, n, size, precision="fp32", png_encoder="host", batch_size=1, decode_threads=4, mixed=False,
-        warm=True, image_format="png", jpeg_quality=95):
+        warm=True, image_format="png", jpeg_quality=95, max_size=None, output_size="letterbox"):
     """One timed enhance_batch_images over the files of `src` -> the result dict."""
     from enhancers.simple_enhance import enhance_batch_images
     kw = {"png_encoder": png_encoder} if png_encoder != "host" else {}
     if image_format != "png":
         kw.update(image_format=image_format, jpeg_quality=jpeg_quality)
+    if max_size is not None:
+        kw["max_size"] = max_size
+    if output_size != "letterbox":
+        kw["output_size"] = output_size
     timings = None
     if batch_size != 1:
         timings = {}
@@ -64,13 +73,35 @@ def run(src, out, n, size, precision="fp32", png_encoder="host", batch_size=1, d
                      "CLAHE-in-Lab + 3 PNG writes per image)", "value": n / el, "unit": "images/s",
            "n": n, "size": size, "precision": precision, "png_encoder": png_encoder,
            "batch_size": batch_size, "mixed": bool(mixed), "seconds": el, "files_written": len(os.listdir(out)),
-           "image_format": image_format,
+           "image_format": image_format, "max_size": max_size, "output_size": output_size,
            "output_bytes": sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out))}
     if image_format == "jpg":
         res["jpeg_quality"] = jpeg_quality
     if timings is not None:
         res["decode_threads"] = decode_threads
         res["stage_seconds"] = {k: round(v, 6) for k, v in sorted(timings.items())}
+    return res
+
+
+def restore_compare(src, out, args):
+    """Alternating runs of the restore route and the full-size route on one directory."""
+    import statistics
+    routes = {"restore": dict(max_size=args.max_size or 512, output_size="original"), "full_size": {}}
+    common = dict(precision=args.precision, png_encoder=args.png_encoder, batch_size=args.batch_size,
+                  decode_threads=args.decode_threads, image_format=args.image_format, jpeg_quality=args.jpeg_quality)
+    rates = {k: [] for k in routes}
+    for rnd in range(args.rounds + 1):  # round 0 warms both routes and is not counted
+        for name, kw in routes.items():
+            r = run(src, f"{out}_{name}{rnd}", args.n, args.size, warm=False, **common, **kw)
+            assert r["files_written"] == 3 * args.n, r
+            if rnd:
+                rates[name].append(r["value"])
+    res = {"metric": "enhance harness images/s to source-sized files: --max_size M --output_size original against "
+                     "the forward at the sources' own size, alternating runs", "unit": "images/s", "n": args.n,
+           "size": args.size, "rounds": args.rounds, **common, "restore_max_size": routes["restore"]["max_size"]}
+    for name, v in rates.items():
+        res[name] = {"median": statistics.median(v), "min": min(v), "max": max(v), "runs": v}
+    res["restore_over_full_size"] = res["restore"]["median"] / res["full_size"]["median"]
     return res
 
 
@@ -85,12 +116,20 @@ def main():
     ap.add_argument("--mixed", action="store_true")
     ap.add_argument("--image_format", choices=["png", "jpg"], default="png")
     ap.add_argument("--jpeg_quality", type=int, default=95)
+    ap.add_argument("--max_size", type=int, default=None)
+    ap.add_argument("--output_size", choices=["letterbox", "original"], default="letterbox")
+    ap.add_argument("--restore_compare", action="store_true")
+    ap.add_argument("--rounds", type=int, default=3)
     args = ap.parse_args()
     with tempfile.TemporaryDirectory(dir="/tmp") as d:
         src, out = os.path.join(d, "in"), os.path.join(d, "out")
         write_inputs(src, args.n, args.size, args.mixed)
-        res = run(src, out, args.n, args.size, args.precision, args.png_encoder, args.batch_size,
-                  args.decode_threads, args.mixed, image_format=args.image_format, jpeg_quality=args.jpeg_quality)
+        if args.restore_compare:
+            res = restore_compare(src, out, args)
+        else:
+            res = run(src, out, args.n, args.size, args.precision, args.png_encoder, args.batch_size,
+                      args.decode_threads, args.mixed, image_format=args.image_format,
+                      jpeg_quality=args.jpeg_quality, max_size=args.max_size, output_size=args.output_size)
     print(json.dumps(res))
 
 
