@@ -453,8 +453,9 @@ int upr_png_encode(const uint8_t* hwc_u8, int B, int H, int W, int filter, int r
  * multiples of 8 by repeating the last row / column.  Colour conversion, the
  * forward DCT and the quantisation are integer arithmetic, stated in
  * the output is a function of the pixels and the arguments
- * only.  Not built: 4:2:0 or any other subsampling, Huffman tables optimised
- * per image, grayscale files, progressive scans.
+ * only.  upr_jpeg_encode / upr_jpeg_bound are the _ex forms below with
+ * (UPR_JPEG_444, UPR_JPEG_HUFF_STANDARD).  Not built: 4:2:2, progressive
+ * scans, arithmetic coding.
  * upr_jpeg_bound: the largest file of one H x W image (out_stride must be at
  * least that) and the scratch bytes per image (upr_jpeg_encode needs B times
  * that, 16-byte aligned).  The bound comes from the code tables: a block is at
@@ -472,6 +473,65 @@ enum { UPR_JPEG_HEADER_BYTES = 629, UPR_JPEG_MAX_BLOCK_BITS = 1660 };
 int upr_jpeg_bound(int H, int W, int restart_rows, size_t* bytes_per_image, size_t* scratch_bytes);
 int upr_jpeg_encode(const uint8_t* hwc_u8, int B, int H, int W, int quality, int restart_rows, uint8_t* out,
                     size_t out_stride, int64_t* sizes, void* scratch, size_t scratch_bytes, void* stream);
+
+/* The encoder's further modes.  Everything above holds (colour formulae, DCT,
+ * quantisation, entropy coding rules, stuffing, 1-padding, RSTm, DRI always
+ * written); restart_rows counts MCU rows in every mode and Ri = MCUs per row
+ * x restart_rows, clamped to the image, at most 65535.
+ * subsampling:
+ *   UPR_JPEG_444   the file of upr_jpeg_encode; an MCU is 8x8 pixels, Y Cb Cr.
+ *   UPR_JPEG_420   H and W are padded to multiples of 16 by repeating the last
+ *                  row / column; Y, Cb, Cr (0..255) per pixel by the formulae
+ *                  above; a chroma sample is the 2x2 box (a + b + c + d + 2)
+ *                  >> 2, then minus 128.  SOF0 sampling factors Y 0x22, Cb
+ *                  0x11, Cr 0x11; an MCU is 16x16 pixels, blocks Y00 Y01 Y10
+ *                  Y11 Cb Cr, one DC predictor per component.
+ *   UPR_JPEG_GRAY  one component: Y of the [H,W,3] input by the formula above
+ *                  (exactly v for R = G = B = v).  SOF0 Nf 1 (id 1, 0x11, Tq
+ *                  0), DQT 0 alone, DHT DC0 and AC0 alone, SOS Ns 1; an MCU is
+ *                  one 8x8 block, blocks in raster order.
+ * huffman:
+ *   UPR_JPEG_HUFF_STANDARD   the Annex K tables.
+ *   UPR_JPEG_HUFF_OPTIMIZED  tables of each image's own: DC0 / AC0 for Y, DC1
+ *     / AC1 for Cb + Cr.  Per table: the exact count of every symbol the
+ *     image's coding emits over all its intervals (DC categories; AC (run,
+ *     size), ZRL, EOB); while the counts' total exceeds 2^22 every non-zero
+ *     count f becomes (f + 1) >> 1 (merge depth <= 31); Annex K.2 as libjpeg's
+ *     jpeg_gen_optimal_table states it on 257 entries with freq[256] = 1 (c1
+ *     the smallest non-zero count, ties to the largest index; c2 the next
+ *     smallest other than c1, ties to the largest index; c2 merges into c1,
+ *     codesize incremented along both `others` chains; until there is no c2);
+ *     bits[codesize[i]]++; the Figure K.3 limit for i = 32 .. 17 (while
+ *     bits[i] > 0: j from i - 2 down to the first with bits[j] > 0; bits[i]
+ *     -= 2, bits[i-1]++, bits[j+1] += 2, bits[j]--); the longest non-empty
+ *     length is decremented once (the reserved entry: no code is all ones);
+ *     HUFFVAL in the order len = 1..32, sym = 0..255 with codesize[sym] ==
+ *     len; canonical codes (Annex C).  A table with one used symbol has one
+ *     1-bit code.  A DHT segment is 19 + nvals bytes behind its marker, so
+ *     the header's length varies per image.
+ * upr_jpeg_bound_ex: as upr_jpeg_bound with a block at most
+ * UPR_JPEG_MAX_BLOCK_BITS (standard) or (16 + 11) + 63 (16 + 10) =
+ * UPR_JPEG_MAX_BLOCK_BITS_OPTIMIZED bits, n = units per MCU (3, 6, 1) x MCUs
+ * per row x the interval's MCU rows, and the header UPR_JPEG_HEADER_BYTES
+ * (UPR_JPEG_HEADER_BYTES_GRAY for gray; an optimised DHT is never longer than
+ * the Annex K one: at most 12 DC and 162 AC symbols exist).  The scratch of
+ * the optimised mode also holds the image's counts and tables.
+ * Errors as above; an unknown subsampling or huffman value is UPR_ERR_ARG.
+ * upr_jpeg_huffman_build: the encoder's table routine on caller-supplied
+ * counts: freq is n tables of 257 u32 (entry 256 is ignored: the reserved
+ * entry is always 1) on the device; table t's BITS[16] then HUFFVAL[256]
+ * (zero behind nvals[t]) go to bits_vals + 272 t, the number of coded symbols
+ * to nvals[t]; all-zero counts give nvals 0.  UPR_ERR_ARG for a null pointer
+ * or n <= 0. */
+enum { UPR_JPEG_444 = 0, UPR_JPEG_420 = 1, UPR_JPEG_GRAY = 2 };
+enum { UPR_JPEG_HUFF_STANDARD = 0, UPR_JPEG_HUFF_OPTIMIZED = 1 };
+enum { UPR_JPEG_HEADER_BYTES_GRAY = 334, UPR_JPEG_MAX_BLOCK_BITS_OPTIMIZED = 1665 };
+int upr_jpeg_bound_ex(int H, int W, int restart_rows, int subsampling, int huffman, size_t* bytes_per_image,
+                      size_t* scratch_bytes);
+int upr_jpeg_encode_ex(const uint8_t* hwc_u8, int B, int H, int W, int quality, int restart_rows, int subsampling,
+                       int huffman, uint8_t* out, size_t out_stride, int64_t* sizes, void* scratch,
+                       size_t scratch_bytes, void* stream);
+int upr_jpeg_huffman_build(const uint32_t* freq, int n, uint8_t* bits_vals, int32_t* nvals, void* stream);
 
 /* Guided-filter restore of the letterboxed result to the source's size (the
  * fast guided filter of He & Sun 2015, per channel; no reference counterpart:

@@ -38,9 +38,12 @@ int launch_decompose_bwd(const void* x, const void* illu, const void* g, void* g
 int png_bound(int H, int W, int rows_per_strip, int match, size_t* bytes_per_image, size_t* scratch_bytes);
 int launch_png_encode(const uint8_t* img, int B, int H, int W, int filter, int match, int rows_per_strip, uint8_t* out,
                       size_t out_stride, long long* sizes, uint8_t* scratch, size_t scratch_bytes, hipStream_t st);
-int jpeg_bound(int H, int W, int restart_rows, size_t* bytes_per_image, size_t* scratch_bytes);
-int launch_jpeg_encode(const uint8_t* img, int B, int H, int W, int quality, int restart_rows, uint8_t* out,
-                       size_t out_stride, long long* sizes, uint8_t* scratch, size_t scratch_bytes, hipStream_t st);
+int jpeg_bound(int H, int W, int restart_rows, int subsampling, int huffman, size_t* bytes_per_image,
+               size_t* scratch_bytes);
+int launch_jpeg_encode(const uint8_t* img, int B, int H, int W, int quality, int restart_rows, int subsampling,
+                       int huffman, uint8_t* out, size_t out_stride, long long* sizes, uint8_t* scratch,
+                       size_t scratch_bytes, hipStream_t st);
+int launch_jpeg_huffman_build(const uint32_t* freq, int n, uint8_t* bits_vals, int32_t* nvals, hipStream_t st);
 }  // namespace upr
 
 using namespace upr;
@@ -207,17 +210,40 @@ int upr_png_encode(const uint8_t* hwc_u8, int B, int H, int W, int filter, int r
                            scratch_bytes, stream);
 }
 
+static bool jpeg_modes_ok(int subsampling, int huffman) {
+  return subsampling >= UPR_JPEG_444 && subsampling <= UPR_JPEG_GRAY &&
+         (huffman == UPR_JPEG_HUFF_STANDARD || huffman == UPR_JPEG_HUFF_OPTIMIZED);
+}
+
+int upr_jpeg_bound_ex(int H, int W, int restart_rows, int subsampling, int huffman, size_t* bytes_per_image,
+                      size_t* scratch_bytes) {
+  if (!bytes_per_image || !scratch_bytes || !jpeg_modes_ok(subsampling, huffman)) return UPR_ERR_ARG;
+  return jpeg_bound(H, W, restart_rows, subsampling, huffman, bytes_per_image, scratch_bytes);
+}
+
 int upr_jpeg_bound(int H, int W, int restart_rows, size_t* bytes_per_image, size_t* scratch_bytes) {
-  if (!bytes_per_image || !scratch_bytes) return UPR_ERR_ARG;
-  return jpeg_bound(H, W, restart_rows, bytes_per_image, scratch_bytes);
+  return upr_jpeg_bound_ex(H, W, restart_rows, UPR_JPEG_444, UPR_JPEG_HUFF_STANDARD, bytes_per_image, scratch_bytes);
+}
+
+int upr_jpeg_encode_ex(const uint8_t* hwc_u8, int B, int H, int W, int quality, int restart_rows, int subsampling,
+                       int huffman, uint8_t* out, size_t out_stride, int64_t* sizes, void* scratch,
+                       size_t scratch_bytes, void* stream) {
+  if (!hwc_u8 || !out || !sizes || !scratch || B <= 0 || H <= 0 || W <= 0 || restart_rows <= 0) return UPR_ERR_ARG;
+  if (quality < 1 || quality > 100 || ((size_t)scratch & 15) || !jpeg_modes_ok(subsampling, huffman))
+    return UPR_ERR_ARG;
+  return launch_jpeg_encode(hwc_u8, B, H, W, quality, restart_rows, subsampling, huffman, out, out_stride,
+                            (long long*)sizes, (uint8_t*)scratch, scratch_bytes, (hipStream_t)stream);
 }
 
 int upr_jpeg_encode(const uint8_t* hwc_u8, int B, int H, int W, int quality, int restart_rows, uint8_t* out,
                     size_t out_stride, int64_t* sizes, void* scratch, size_t scratch_bytes, void* stream) {
-  if (!hwc_u8 || !out || !sizes || !scratch || B <= 0 || H <= 0 || W <= 0 || restart_rows <= 0) return UPR_ERR_ARG;
-  if (quality < 1 || quality > 100 || ((size_t)scratch & 15)) return UPR_ERR_ARG;
-  return launch_jpeg_encode(hwc_u8, B, H, W, quality, restart_rows, out, out_stride, (long long*)sizes,
-                            (uint8_t*)scratch, scratch_bytes, (hipStream_t)stream);
+  return upr_jpeg_encode_ex(hwc_u8, B, H, W, quality, restart_rows, UPR_JPEG_444, UPR_JPEG_HUFF_STANDARD, out,
+                            out_stride, sizes, scratch, scratch_bytes, stream);
+}
+
+int upr_jpeg_huffman_build(const uint32_t* freq, int n, uint8_t* bits_vals, int32_t* nvals, void* stream) {
+  if (!freq || !bits_vals || !nvals || n <= 0) return UPR_ERR_ARG;
+  return launch_jpeg_huffman_build(freq, n, bits_vals, nvals, (hipStream_t)stream);
 }
 
 void upr_lab_tables(uint16_t* gamma, uint16_t* cbrt, uint16_t* yf, uint16_t* invgamma, int32_t* rgb2xyz,

@@ -6,7 +6,11 @@ png_encoder="device", the device's (upr.png: larger files, no host encode);
 png_encoder="device_lz" is the device's with LZ77 matching (smaller files).
 image_format="jpg" (an addition; the default "png" changes nothing) writes the
 three files as baseline JPEGs of quality jpeg_quality: PIL with the host encoder,
-upr.jpeg (4:4:4, the device's own integer DCT) with either device encoder.
+upr.jpeg (the device's own integer DCT) with either device encoder.  With either,
+jpeg_subsampling="420" halves the chroma of all three files (the default "444" does
+not), jpeg_optimize=True gives every file Huffman tables of its own and
+jpeg_gray_maps=True writes _illumination.jpg as a one-component file (the enhanced
+file and the comparison stay colour); image_format="png" ignores the three.
 Intentional divergences, each a reference bug:
   * enhance_single_image accepts and ignores `adjuster=` so main.py's
     single-file branch works (reference main.py:240-249 vs simple_enhance.py:135
@@ -24,6 +28,7 @@ three batched PNG encodes per batch, two batches in flight.
 """
 import functools
 import os
+from typing import NamedTuple
 from collections import deque
 from concurrent.futures import ThreadPoolExecutor
 import threading
@@ -59,11 +64,32 @@ def _check_encoder(png_encoder):
 IMAGE_FORMATS = ("png", "jpg")
 
 
-def _check_format(image_format, jpeg_quality):
+JPEG_SUBSAMPLINGS = ("444", "420")
+
+
+def _check_format(image_format, jpeg_quality, jpeg_subsampling="444", jpeg_optimize=False, jpeg_gray_maps=False):
     if image_format not in IMAGE_FORMATS:
         raise ValueError(f"image_format must be one of {IMAGE_FORMATS}, got {image_format!r}")
-    if image_format == "jpg" and not 1 <= int(jpeg_quality) <= 100:
+    if image_format != "jpg":
+        return
+    if not 1 <= int(jpeg_quality) <= 100:
         raise ValueError(f"jpeg_quality must be in 1..100, got {jpeg_quality!r}")
+    if jpeg_subsampling not in JPEG_SUBSAMPLINGS:
+        raise ValueError(f"jpeg_subsampling must be one of {JPEG_SUBSAMPLINGS}, got {jpeg_subsampling!r}")
+    for name, v in (("jpeg_optimize", jpeg_optimize), ("jpeg_gray_maps", jpeg_gray_maps)):
+        if not isinstance(v, bool):
+            raise ValueError(f"{name} must be True or False, got {v!r}")
+
+
+class _Jpeg(NamedTuple):
+    """How one .jpg file is written: what the public jpeg_* arguments mean for that file."""
+    quality: int = 95
+    subsampling: str = "444"
+    optimize: bool = False
+    gray: bool = False  # a one-component file (the illumination map with jpeg_gray_maps)
+
+    def colour(self):
+        return self._replace(gray=False)
 
 
 OUTPUT_SIZES = ("letterbox", "original")
@@ -128,18 +154,22 @@ def _write_png(arr, save_path, msg):
     print(f"{msg}: {save_path}")
 
 
-def _write_jpg(arr, save_path, msg, quality):
-    Image.fromarray(arr).save(save_path, format="JPEG", quality=int(quality), subsampling=0)
+def _write_jpg(arr, save_path, msg, jpeg):
+    im = Image.fromarray(arr)
+    if jpeg.gray:  # exact for the maps' R = G = B; one component has nothing to subsample
+        im = im.convert("L")
+    im.save(save_path, format="JPEG", quality=int(jpeg.quality), optimize=bool(jpeg.optimize),
+            subsampling=2 if jpeg.subsampling == "420" and not jpeg.gray else 0)
     print(f"{msg}: {save_path}")
 
 
-def _pixel_writer(image_format, jpeg_quality):
+def _pixel_writer(image_format, jpeg):
     """The host encoder of a format: f(arr, save_path, msg)."""
-    return _write_png if image_format == "png" else functools.partial(_write_jpg, quality=jpeg_quality)
+    return _write_png if image_format == "png" else functools.partial(_write_jpg, jpeg=jpeg)
 
 
-def _emit(arr, save_path, msg, writer, image_format="png", jpeg_quality=95):
-    write = _pixel_writer(image_format, jpeg_quality)
+def _emit(arr, save_path, msg, writer, image_format="png", jpeg=_Jpeg()):
+    write = _pixel_writer(image_format, jpeg)
     if writer is None:
         write(arr, save_path, msg)
     else:  # encode + file write on the batch harness's writer thread
@@ -158,20 +188,21 @@ def _write_device_pngs(buf, sizes, done, jobs):
         print(f"{msg}: {save_path}")
 
 
-def _encode_device(u8_images, png_encoder, image_format, jpeg_quality):
+def _encode_device(u8_images, png_encoder, image_format, jpeg):
     """(buf, sizes) of the device encoder of a format; queued on the current stream."""
     if image_format == "jpg":
-        from upr import jpeg
-        return jpeg.encode_device(u8_images, quality=jpeg_quality)
+        from upr import jpeg as upr_jpeg
+        return upr_jpeg.encode_device(u8_images, quality=jpeg.quality,
+                                      subsampling="gray" if jpeg.gray else jpeg.subsampling, optimize=jpeg.optimize)
     from upr import png
     return png.encode_device(u8_images, matches=_DEVICE_MATCHES[png_encoder])
 
 
-def _emit_device(u8_images, jobs, writer, png_encoder, image_format="png", jpeg_quality=95):
+def _emit_device(u8_images, jobs, writer, png_encoder, image_format="png", jpeg=_Jpeg()):
     """u8_images: u8 [B,H,W,3] (or [H,W,3]) on the device, jobs: (save_path, msg) per image.
     The encode is queued on the current stream here; the copy and the write happen on the
     writer thread (or right away without one)."""
-    buf, sizes = _encode_device(u8_images, png_encoder, image_format, jpeg_quality)
+    buf, sizes = _encode_device(u8_images, png_encoder, image_format, jpeg)
     done = torch.cuda.Event()
     done.record(torch.cuda.current_stream(buf.device))
     if writer is None:
@@ -180,40 +211,47 @@ def _emit_device(u8_images, jobs, writer, png_encoder, image_format="png", jpeg_
         writer.submit(_write_device_pngs, buf, sizes, done, jobs)
 
 
-def save_image(tensor, save_path, writer=None, png_encoder="host", image_format="png", jpeg_quality=95):
+def save_image(tensor, save_path, writer=None, png_encoder="host", image_format="png", jpeg_quality=95,
+               jpeg_subsampling="444", jpeg_optimize=False, jpeg_gray_maps=False):
     """[1,C,H,W] or [C,H,W] -> PNG; 1-channel maps are replicated to RGB (reference :65-99).
-    image_format="jpg": the same pixels as a JPEG of quality jpeg_quality."""
+    image_format="jpg": the same pixels as a JPEG of quality jpeg_quality, chroma as
+    jpeg_subsampling says, Huffman tables of its own with jpeg_optimize; jpeg_gray_maps=True
+    says the tensor is a map (the caller's _illumination file): a one-component file."""
     _check_encoder(png_encoder)
-    _check_format(image_format, jpeg_quality)
+    _check_format(image_format, jpeg_quality, jpeg_subsampling, jpeg_optimize, jpeg_gray_maps)
+    jpeg = _Jpeg(jpeg_quality, jpeg_subsampling, jpeg_optimize, jpeg_gray_maps)
     if tensor.dim() == 4:
         tensor = tensor.squeeze(0)
     if png_encoder in _DEVICE_MATCHES:
-        _emit_device(_to_u8_hwc_device(tensor), [(save_path, "已保存")], writer, png_encoder, image_format,
-                     jpeg_quality)
+        _emit_device(_to_u8_hwc_device(tensor), [(save_path, "已保存")], writer, png_encoder, image_format, jpeg)
     else:
-        _emit(_to_u8_hwc(tensor), save_path, "已保存", writer, image_format, jpeg_quality)
+        _emit(_to_u8_hwc(tensor), save_path, "已保存", writer, image_format, jpeg)
 
 
 def create_comparison(img_low, img_enhanced, save_path, writer=None, illu_map=None, png_encoder="host",
-                      image_format="png", jpeg_quality=95):
+                      image_format="png", jpeg_quality=95, jpeg_subsampling="444", jpeg_optimize=False,
+                      jpeg_gray_maps=False):
     """[input | enhanced] side by side (reference :102-132); with `illu_map`
     the predictor's 3-panel form [input | enhanced | illumination]
-    (reference predictors/predict.py:102-140)."""
+    (reference predictors/predict.py:102-140).  The comparison is a colour file whatever
+    jpeg_gray_maps says."""
     _check_encoder(png_encoder)
-    _check_format(image_format, jpeg_quality)
+    _check_format(image_format, jpeg_quality, jpeg_subsampling, jpeg_optimize, jpeg_gray_maps)
+    jpeg = _Jpeg(jpeg_quality, jpeg_subsampling, jpeg_optimize)
     to_u8 = _to_u8_hwc_device if png_encoder in _DEVICE_MATCHES else _to_u8_hwc
     panels = [to_u8(img_low.squeeze(0)), to_u8(img_enhanced.squeeze(0))]
     if illu_map is not None:
         panels.append(to_u8(illu_map.squeeze(0)))
     if png_encoder in _DEVICE_MATCHES:  # the panel is joined on the device, along W
         _emit_device(torch.cat(panels, dim=1), [(save_path, "已保存对比图像")], writer, png_encoder,
-                     image_format, jpeg_quality)
+                     image_format, jpeg)
     else:
-        _emit(np.concatenate(panels, axis=1), save_path, "已保存对比图像", writer, image_format, jpeg_quality)
+        _emit(np.concatenate(panels, axis=1), save_path, "已保存对比图像", writer, image_format, jpeg)
 
 
 def save_original_size(src_u8, img_low, img_enhanced, illu_map, paths, max_size=None, comparison=2, writer=None,
-                       png_encoder="host", image_format="png", jpeg_quality=95, guided_radius=4, guided_eps=1e-4):
+                       png_encoder="host", image_format="png", jpeg_quality=95, guided_radius=4, guided_eps=1e-4,
+                       jpeg_subsampling="444", jpeg_optimize=False, jpeg_gray_maps=False):
     """The three files of one image at the source's size (output_size="original").  src_u8: the
     decoded uint8 HWC image; img_low / img_enhanced / illu_map: the [1,C,H',W'] letterboxed
     tensors whose pixels the files hold with output_size="letterbox"; paths: (enhanced,
@@ -230,28 +268,32 @@ def save_original_size(src_u8, img_low, img_enhanced, illu_map, paths, max_size=
     src = torch.from_numpy(np.ascontiguousarray(src_u8)).to(dev).unsqueeze(0)
     outs = guided.restore(src, u8(img_low), u8(img_enhanced), u8(illu_map), content, guided_radius, guided_eps,
                           comparison)
-    for arr, path, msg in zip(outs, paths, ("已保存", "已保存", "已保存对比图像")):
+    colour = _Jpeg(jpeg_quality, jpeg_subsampling, jpeg_optimize)
+    modes = (colour, colour._replace(gray=bool(jpeg_gray_maps)), colour)
+    for arr, path, msg, jpeg in zip(outs, paths, ("已保存", "已保存", "已保存对比图像"), modes):
         if arr is None:
             continue
         if png_encoder in _DEVICE_MATCHES:
-            _emit_device(arr[0], [(path, msg)], writer, png_encoder, image_format, jpeg_quality)
+            _emit_device(arr[0], [(path, msg)], writer, png_encoder, image_format, jpeg)
         else:
-            _emit(arr[0].cpu().numpy(), path, msg, writer, image_format, jpeg_quality)
+            _emit(arr[0].cpu().numpy(), path, msg, writer, image_format, jpeg)
 
 
 def enhance_single_image(model, image_path, output_dir, device, max_size=None, enable_multi_scale=False,
                          enable_content_aware=False, adjuster=None, precision="fp32", _decoded=None, _writer=None,
                          png_encoder="host", image_format="png", jpeg_quality=95, output_size="letterbox",
-                         guided_radius=4, guided_eps=1e-4):
+                         guided_radius=4, guided_eps=1e-4, jpeg_subsampling="444", jpeg_optimize=False,
+                         jpeg_gray_maps=False):
     """Enhance one file and write {name}_enhanced/_illumination/_comparison.png (reference :135-199;
-    .jpg with image_format="jpg", quality jpeg_quality).
+    .jpg with image_format="jpg", quality jpeg_quality; jpeg_subsampling and jpeg_optimize apply to
+    all three files, jpeg_gray_maps makes _illumination.jpg a one-component file).
     precision="fp16" runs the fp16 storage / fp16-MFMA graph (input cast to half).
     png_encoder="device" encodes the three files on the GPU (same pixels, larger files),
     "device_lz" does so with LZ77 matching (same pixels, smaller files than "device").
     output_size="original" writes the three files at the source's size (save_original_size);
     the returned tensors stay the letterboxed ones."""
     _check_encoder(png_encoder)
-    _check_format(image_format, jpeg_quality)
+    _check_format(image_format, jpeg_quality, jpeg_subsampling, jpeg_optimize, jpeg_gray_maps)
     _check_output_size(output_size, guided_radius, guided_eps)
     print(f"正在处理: {os.path.basename(image_path)}")
     if _decoded is None and output_size == "original":
@@ -274,16 +316,19 @@ def enhance_single_image(model, image_path, output_dir, device, max_size=None, e
     print(f"增强耗时: {time.time() - start:.4f}s")
     os.makedirs(output_dir, exist_ok=True)
     name = os.path.splitext(os.path.basename(image_path))[0]
-    fmt = dict(image_format=image_format, jpeg_quality=jpeg_quality)
+    fmt = dict(image_format=image_format, jpeg_quality=jpeg_quality, jpeg_subsampling=jpeg_subsampling,
+               jpeg_optimize=jpeg_optimize)
     if output_size == "original":
         save_original_size(_decoded[0], img_low, img_enhanced, illu_map,
                            [os.path.join(output_dir, f"{name}_{kind}.{image_format}")
                             for kind in ("enhanced", "illumination", "comparison")], max_size, 2, _writer,
-                           png_encoder, guided_radius=guided_radius, guided_eps=guided_eps, **fmt)
+                           png_encoder, guided_radius=guided_radius, guided_eps=guided_eps,
+                           jpeg_gray_maps=jpeg_gray_maps, **fmt)
         print("图像增强完成！")
         return img_enhanced, illu_map
     save_image(img_enhanced, os.path.join(output_dir, f"{name}_enhanced.{image_format}"), _writer, png_encoder, **fmt)
-    save_image(illu_map, os.path.join(output_dir, f"{name}_illumination.{image_format}"), _writer, png_encoder, **fmt)
+    save_image(illu_map, os.path.join(output_dir, f"{name}_illumination.{image_format}"), _writer, png_encoder,
+               jpeg_gray_maps=jpeg_gray_maps, **fmt)
     create_comparison(img_low, img_enhanced, os.path.join(output_dir, f"{name}_comparison.{image_format}"), _writer,
                       png_encoder=png_encoder, **fmt)
     print("图像增强完成！")
@@ -418,7 +463,8 @@ def _write_image_files(files, clock, lines, write_pixels=_write_png):
 def _finish_batch(job, writer, clock, image_lines, write_pixels=_write_png, trim=False):
     """Copier thread: wait for the batch's event, bring its files (device encoder) or pixels
     (host encoder) to pinned host memory in one copy per tensor, hand the per-image writes to
-    the writer threads.  Returns their futures.  trim (the device JPEG encoder, whose buffer is
+    the writer threads.  Returns their futures.  write_pixels: the host encoder, or one per
+    kind of file.  trim (the device JPEG encoder, whose buffer is
     sized by a bound several times the files): the sizes come first, then only the columns up
     to the longest file."""
     done, dev, outputs, paths = job
@@ -459,18 +505,21 @@ def _finish_batch(job, writer, clock, image_lines, write_pixels=_write_png, trim
         if host[0][2] is not None:  # encoded already: one task writes the image's files
             futs.append(writer.submit(_write_image_files, files, clock, lines))
         else:  # PIL encodes: one task per file
-            futs += [writer.submit(_write_image_files, [f], clock, lines, write_pixels) for f in files]
+            per_file = write_pixels if isinstance(write_pixels, (list, tuple)) else [write_pixels] * len(files)
+            futs += [writer.submit(_write_image_files, [f], clock, lines, w) for f, w in zip(files, per_file)]
     return futs
 
 
 def run_batched(model, image_files, output_dir, device, *, max_size=None, precision="fp32", png_encoder="host",
                 batch_size=8, decode_threads=4, clahe=True, comparison=2, image_lines=True, timings=None,
-                image_format="png", jpeg_quality=95, output_size="letterbox", guided_radius=4, guided_eps=1e-4):
+                image_format="png", jpeg_quality=95, output_size="letterbox", guided_radius=4, guided_eps=1e-4,
+                jpeg_subsampling="444", jpeg_optimize=False, jpeg_gray_maps=False):
     """The batched directory pipeline behind enhance_batch_images(batch_size > 1) and
     main.py --mode predict --infer_batch: for every file {name}_enhanced.png,
     {name}_illumination.png and, unless comparison is None, {name}_comparison.png
     ([input | enhanced] for comparison=2, [input | enhanced | illumination] for 3); .jpg files of
-    quality jpeg_quality with image_format="jpg" (host encoder: PIL, device encoders: upr.jpeg).
+    quality jpeg_quality with image_format="jpg" (host encoder: PIL, device encoders: upr.jpeg;
+    jpeg_subsampling and jpeg_optimize for every kind of file, jpeg_gray_maps for the maps).
     clahe: apply_clahe_enhancement after the forward (the enhance mode's default path);
     image_lines: print enhance mode's per-image lines (predict mode prints the saves only).
 
@@ -497,7 +546,7 @@ def run_batched(model, image_files, output_dir, device, *, max_size=None, precis
     letterboxed one."""
     from upr import guided, runtime
     _check_encoder(png_encoder)
-    _check_format(image_format, jpeg_quality)
+    _check_format(image_format, jpeg_quality, jpeg_subsampling, jpeg_optimize, jpeg_gray_maps)
     _check_output_size(output_size, guided_radius, guided_eps)
     original = output_size == "original"
     if comparison not in (None, 2, 3):
@@ -513,6 +562,8 @@ def run_batched(model, image_files, output_dir, device, *, max_size=None, precis
     writers = max(1, min(_WRITERS, _BATCH_CPUS - decode_threads))
     os.makedirs(output_dir, exist_ok=True)
     kinds = [("enhanced", "已保存"), ("illumination", "已保存")] + ([("comparison", "已保存对比图像")] if comparison else [])
+    colour = _Jpeg(jpeg_quality, jpeg_subsampling, jpeg_optimize)
+    jpegs = [colour._replace(gray=bool(jpeg_gray_maps)) if kind == "illumination" else colour for kind, _ in kinds]
     n_files, count = len(image_files), 0
 
     def launch(idxs, images):
@@ -533,9 +584,9 @@ def run_batched(model, image_files, output_dir, device, *, max_size=None, precis
         else:
             u8s = runtime.panels_u8(x, enh, illu, comparison)
         outputs = []
-        for (_, msg), u8 in zip(kinds, u8s):
+        for (_, msg), u8, jpeg in zip(kinds, u8s, jpegs):
             if png_encoder in _DEVICE_MATCHES:
-                buf, sizes = _encode_device(u8, png_encoder, image_format, jpeg_quality)
+                buf, sizes = _encode_device(u8, png_encoder, image_format, jpeg)
                 outputs.append((msg, None, buf, sizes))
             else:
                 outputs.append((msg, u8, None, None))
@@ -583,7 +634,7 @@ def run_batched(model, image_files, output_dir, device, *, max_size=None, precis
                 print(f"正在处理: {os.path.basename(image_files[i])}")
                 print(f"增强耗时: {dt / len(idxs):.4f}s")  # the image's share of queueing its batch (no synchronise)
             inflight.append(copier.submit(_finish_batch, job, writer, clock, image_lines,
-                                          _pixel_writer(image_format, jpeg_quality), image_format == "jpg"))
+                                          [_pixel_writer(image_format, j) for j in jpegs], image_format == "jpg"))
             del job
         while inflight:
             drain(inflight.popleft())
@@ -596,7 +647,7 @@ def run_batched(model, image_files, output_dir, device, *, max_size=None, precis
 def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preact=True, use_aspp=True, seed=None,
                          precision="fp32", png_encoder="host", batch_size=1, decode_threads=4, timings=None,
                          image_format="png", jpeg_quality=95, output_size="letterbox", guided_radius=4,
-                         guided_eps=1e-4):
+                         guided_eps=1e-4, jpeg_subsampling="444", jpeg_optimize=False, jpeg_gray_maps=False):
     """Enhance every image of a directory (reference :202-250).
 
     batch_size=1 (the default) is the reference's one-image-at-a-time loop with a decode
@@ -607,12 +658,14 @@ def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preac
     image's files are exactly what the model, apply_clahe_enhancement and to_u8_hwc give for
     the batch tensor the image was placed in (measured on the GPU, no output byte depended on
     that batch: DESIGN.md 4.5).  timings: see run_batched (batched path only).  image_format="jpg"
-    writes the three files as .jpg of quality jpeg_quality.  output_size="original" writes them
+    writes the three files as .jpg of quality jpeg_quality (jpeg_subsampling, jpeg_optimize and
+    jpeg_gray_maps as in enhance_single_image).  output_size="original" writes them
     at each source's size (run_batched / save_original_size; guided_radius, guided_eps)."""
     _check_encoder(png_encoder)
-    _check_format(image_format, jpeg_quality)
+    _check_format(image_format, jpeg_quality, jpeg_subsampling, jpeg_optimize, jpeg_gray_maps)
     _check_output_size(output_size, guided_radius, guided_eps)
-    restore = dict(output_size=output_size, guided_radius=guided_radius, guided_eps=guided_eps)
+    restore = dict(output_size=output_size, guided_radius=guided_radius, guided_eps=guided_eps,
+                   jpeg_subsampling=jpeg_subsampling, jpeg_optimize=jpeg_optimize, jpeg_gray_maps=jpeg_gray_maps)
     batch_size = int(batch_size)
     if batch_size < 1:
         raise ValueError(f"batch_size must be >= 1, got {batch_size}")

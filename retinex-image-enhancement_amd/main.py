@@ -10,6 +10,9 @@ device is Huffman-only and writes larger files, device_lz adds LZ77 matching).
 --image_format {png,jpg} and --jpeg_quality Q (additions, default png / 95):
 jpg writes the enhance / predict outputs as baseline 4:4:4 JPEGs, PIL's with
 --png_encoder host, the device encoder's (upr.jpeg) with device or device_lz.
+--jpeg_subsampling {444,420} (default 444), --jpeg_optimize and --jpeg_gray_maps
+(additions, jpg only): 4:2:0 chroma and per-file Huffman tables for every file,
+the illumination map as a one-component file.
 Intentional divergences (reference bugs): a single-file --mode enhance works
 (reference main.py:240-249 raises TypeError); --mode predict unpacks the
 model's 3-tuple (reference predict.py:163 raises ValueError).
@@ -104,6 +107,12 @@ def build_parser():
                         '--png_encoder chooses PIL or the device encoder for it as well)')
     p.add_argument('--jpeg_quality', type=_jpeg_quality, default=95,
                    help='--image_format jpg: quality 1..100, as PIL\'s `quality`')
+    p.add_argument('--jpeg_subsampling', choices=['444', '420'], default='444',
+                   help='--image_format jpg: chroma subsampling of the three files (420: PIL\'s default)')
+    p.add_argument('--jpeg_optimize', action='store_true',
+                   help='--image_format jpg: Huffman tables built per file (PIL\'s optimize=True)')
+    p.add_argument('--jpeg_gray_maps', action='store_true',
+                   help='--image_format jpg: write _illumination.jpg as a one-component (grayscale) file')
     p.add_argument('--output_size', choices=['letterbox', 'original'], default='letterbox',
                    help='--mode enhance / predict: size of the output files: the letterboxed tensor\'s (default) '
                         'or the source\'s (guided-filter restore of the result to the decoded image)')
@@ -131,7 +140,9 @@ def _place(model, args):
 
 
 def _output_format(args):
-    return dict(png_encoder=args.png_encoder, image_format=args.image_format, jpeg_quality=args.jpeg_quality)
+    return dict(png_encoder=args.png_encoder, image_format=args.image_format, jpeg_quality=args.jpeg_quality,
+                jpeg_subsampling=args.jpeg_subsampling, jpeg_optimize=args.jpeg_optimize,
+                jpeg_gray_maps=args.jpeg_gray_maps)
 
 
 def _restore(args):
@@ -159,7 +170,7 @@ def _predict_one(model, path, args):
                            None if args.no_comparison else 3, guided_radius=args.guided_radius,
                            guided_eps=args.guided_eps, **enc)
         return
-    save_image(enh, os.path.join(args.output_dir, f"{name}_enhanced.{ext}"), **enc)
+    save_image(enh, os.path.join(args.output_dir, f"{name}_enhanced.{ext}"), **dict(enc, jpeg_gray_maps=False))
     save_image(illu, os.path.join(args.output_dir, f"{name}_illumination.{ext}"), **enc)
     if not args.no_comparison:
         create_comparison(x, enh, os.path.join(args.output_dir, f"{name}_comparison.{ext}"), illu_map=illu, **enc)

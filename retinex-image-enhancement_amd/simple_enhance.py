@@ -2,7 +2,9 @@
 """Root enhance CLI (drop-in for the reference simple_enhance.py:17-94):
 --input/--output/--max_size/--device/--multi_scale/--content_aware, plus --seed and
 --output_size {letterbox,original} with --guided_radius / --guided_eps (original: the files
-have the source's size, upr.guided)."""
+have the source's size, upr.guided), and --image_format {png,jpg} with --jpeg_quality,
+--jpeg_subsampling {444,420}, --jpeg_optimize and --jpeg_gray_maps (jpg: the three files as
+JPEGs, as main.py's flags of the same names)."""
 import argparse
 import os
 import sys
@@ -32,12 +34,22 @@ def build_parser():
                          '(guided-filter restore)')
     ap.add_argument('--guided_radius', type=int, default=4, help='--output_size original: window radius, 1..32')
     ap.add_argument('--guided_eps', type=float, default=1e-4, help='--output_size original: regulariser, > 0')
+    ap.add_argument('--image_format', choices=['png', 'jpg'], default='png', help='format of the output files')
+    ap.add_argument('--jpeg_quality', type=int, default=95, help='--image_format jpg: quality 1..100')
+    ap.add_argument('--jpeg_subsampling', choices=['444', '420'], default='444',
+                    help='--image_format jpg: chroma subsampling of the three files')
+    ap.add_argument('--jpeg_optimize', action='store_true', help='--image_format jpg: Huffman tables built per file')
+    ap.add_argument('--jpeg_gray_maps', action='store_true',
+                    help='--image_format jpg: write _illumination.jpg as a one-component (grayscale) file')
     return ap
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    restore = dict(output_size=args.output_size, guided_radius=args.guided_radius, guided_eps=args.guided_eps)
+    restore = dict(output_size=args.output_size, guided_radius=args.guided_radius, guided_eps=args.guided_eps,
+                   image_format=args.image_format, jpeg_quality=args.jpeg_quality,
+                   jpeg_subsampling=args.jpeg_subsampling, jpeg_optimize=args.jpeg_optimize,
+                   jpeg_gray_maps=args.jpeg_gray_maps)
     if args.device is None:
         args.device = 'cuda' if torch.cuda.is_available() else 'cpu'
     print(f"使用设备: {args.device}")

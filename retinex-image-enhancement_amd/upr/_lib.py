@@ -65,6 +65,11 @@ PNG_MATCHES = {"none": 0, "lz": 1}
 # include/upr.h UPR_JPEG_*: the fixed parts of upr_jpeg_bound's formula
 UPR_JPEG_HEADER_BYTES = 629
 UPR_JPEG_MAX_BLOCK_BITS = 1660
+UPR_JPEG_HEADER_BYTES_GRAY = 334
+UPR_JPEG_MAX_BLOCK_BITS_OPTIMIZED = 1665
+# include/upr.h UPR_JPEG_444 / _420 / _GRAY and UPR_JPEG_HUFF_*: upr_jpeg_encode_ex's modes
+JPEG_SUBSAMPLINGS = {"444": 0, "420": 1, "gray": 2}
+JPEG_HUFFMAN = {"standard": 0, "optimized": 1}
 
 UPR_OP_CONV_IGEMM = 0
 UPR_OP_OTHER = 1
@@ -132,6 +137,11 @@ SIGNATURES = {
     "upr_jpeg_bound": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
     "upr_jpeg_encode": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
                                 c_size_t, c_void_p]),
+    "upr_jpeg_bound_ex": (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_size_t),
+                                  ctypes.POINTER(c_size_t)]),
+    "upr_jpeg_encode_ex": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                   c_void_p, c_void_p, c_size_t, c_void_p]),
+    "upr_jpeg_huffman_build": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "upr_guided_fit_workspace": (c_size_t, [c_int, c_int, c_int]),
     "upr_guided_fit": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),

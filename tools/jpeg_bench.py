@@ -7,6 +7,11 @@ low-light noise and the real crop of tests/golden/g4_real_crop.npz tiled to 512 
 
   python tools/jpeg_bench.py [--n 32] [--size 512] [--reps 50] [--quality 95] [--restart_rows 1]
                              [--out profiles/jpeg_encode_v1.json]
+  python tools/jpeg_bench.py --modes [--out profiles/jpeg_modes_v1.json]
+
+--modes measures all six (subsampling, optimize) modes in one run instead, 444 / standard first as
+the run's baseline: encode ms (median and range of --reps), file bytes over PIL's at the same
+settings (subsampling=0|2 or mode "L", optimize=) and over the 444 / standard file.
 
 Times are device events around upr.jpeg.encode_device (its three kernels, no copy to the host),
 median of --reps calls after a warm-up.  hbm_floor_ms is (pixels read + file bytes written) over
@@ -34,6 +39,45 @@ def pil_bytes(a, quality):
     f = io.BytesIO()
     Image.fromarray(a).save(f, format="JPEG", quality=quality, subsampling=0)
     return f.tell()
+
+
+MODES = [(s, o) for s in ("444", "420", "gray") for o in (False, True)]
+
+
+def pil_mode_bytes(a, quality, subsampling, optimize):
+    f = io.BytesIO()
+    im = Image.fromarray(a)
+    if subsampling == "gray":
+        im.convert("L").save(f, format="JPEG", quality=quality, optimize=optimize)
+    else:
+        im.save(f, format="JPEG", quality=quality, subsampling=2 if subsampling == "420" else 0, optimize=optimize)
+    return f.tell()
+
+
+def measure_modes(name, imgs, reps, quality, restart_rows):
+    from upr import jpeg
+    x = torch.from_numpy(imgs).cuda()
+    sample = range(0, len(imgs), max(1, len(imgs) // 4))
+    rows, base_bytes, base_ms = [], None, None
+    for sub, opt in MODES:
+        kw = dict(quality=quality, restart_rows=restart_rows, subsampling=sub, optimize=opt)
+        files = jpeg.encode(x, **kw)
+        im = Image.open(io.BytesIO(files[0]))
+        im.load()
+        assert im.mode == ("L" if sub == "gray" else "RGB") and im.size == (imgs.shape[2], imgs.shape[1]), (name, kw)
+        ms = event_ms(lambda: jpeg.encode_device(x, **kw), reps)
+        dev_bytes = sum(len(f) for f in files)
+        pil = sum(pil_mode_bytes(imgs[k], quality, sub, opt) for k in sample)
+        med = statistics.median(ms)
+        if base_bytes is None:
+            base_bytes, base_ms = dev_bytes, med
+        rows.append({"subsampling": sub, "optimize": opt, "encode_ms_median": med, "encode_ms_min": min(ms),
+                     "encode_ms_max": max(ms), "reps": reps, "encode_ms_over_444_standard": med / base_ms,
+                     "device_bytes_per_image": dev_bytes / imgs.shape[0],
+                     "device_over_pil": sum(len(files[k]) for k in sample) / pil,
+                     "device_over_444_standard": dev_bytes / base_bytes})
+    return {"set": name, "images": int(imgs.shape[0]), "size": int(imgs.shape[1]), "quality": quality,
+            "restart_rows": restart_rows, "modes": rows}
 
 
 def event_ms(fn, reps):
@@ -98,21 +142,31 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--quality", type=int, default=95)
     ap.add_argument("--restart_rows", type=int, default=1)
+    ap.add_argument("--modes", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("jpeg_bench needs a ROCm device")
+    sets = (("harness_noise", harness_images(args.n, args.size)), ("real_crop_tiled", real_images(args.n, args.size)))
+    if args.modes:
+        res = {"metric": "device JPEG encode (upr.jpeg.encode_device) in every (subsampling, optimize) mode, "
+                         "device-event time per call",
+               "sets": [measure_modes(name, imgs, args.reps, args.quality, args.restart_rows) for name, imgs in sets]}
+        return finish(res, args.out)
     from upr import calib
     hbm = calib.measure(torch.device("cuda"), warm_s=0.5)["hbm_copy_TBps"]
     res = {"metric": "device JPEG encode (upr.jpeg.encode_device), device-event time per call",
            "hbm_copy_TBps": hbm,
            "sets": [measure_set(name, imgs, args.reps, hbm, args.quality, args.restart_rows)
-                    for name, imgs in (("harness_noise", harness_images(args.n, args.size)),
-                                       ("real_crop_tiled", real_images(args.n, args.size)))]}
+                    for name, imgs in sets]}
+    finish(res, args.out)
+
+
+def finish(res, out):
     print(json.dumps(res))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as fh:
             fh.write(json.dumps(res, indent=1) + "\n")
 
 
