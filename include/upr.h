@@ -385,6 +385,33 @@ size_t upr_image_metrics_workspace(int B, int H, int W);
 int upr_image_metrics(const void* enh, const void* ref, double* metrics, double* sums, int32_t* hist,
                       void* workspace, size_t workspace_bytes, int B, int H, int W, int dtype, void* stream);
 
+/* Lightness order error (LOE; S. Wang, J. Zheng, H.-M. Hu, B. Li, "Naturalness
+ * preserved enhancement algorithm for non-uniform illumination images", IEEE
+ * Trans. Image Processing 22(9), 2013) of enh against its own low-light input
+ * low, both [B,3,H,W] of one dtype (H, W >= 1, H * W < 2^31), per image; no
+ * ground truth is involved and the reference has no counterpart.  Integer and
+ * exact:
+ *   q(v)   upr_to_u8_hwc's cast: clamp to [0, 1], times 255 in float32,
+ *          truncated (fp16 input widened exactly first)
+ *   L(p)   max(q(R), q(G), q(B)), 0..255
+ *   grid   with m = min(H, W): every pixel when sample == 0 or m <= sample,
+ *          else h x w pixels, h = max(1, (H * sample + m / 2) / m) and w
+ *          likewise (integer division); grid row i is source row
+ *          ((2 i + 1) * H) / (2 h), columns likewise; N = h * w
+ *   D      the ordered pairs (x, y) of grid pixels with
+ *          (L_low(x) >= L_low(y)) != (L_enh(x) >= L_enh(y))
+ *   loe    D / N as one fp64 division (the paper's mean relative-order
+ *          difference); sample = 50 is the literature's convention
+ * D is taken from the 256 x 256 joint histogram of (L_low, L_enh) and its 2-D
+ * prefix, never pair by pair.  loe fp64 [B]; counts int64 [B][2] = (D, N),
+ * nullable.  Image b's result does not depend on B or its position, and every
+ * sum is an integer sum: a rerun gives the same bits.  The workspace
+ * (upr_image_loe_workspace(B) bytes: two int32 tables per image) is zeroed by
+ * the call itself on `stream`; a caller may reuse one across calls. */
+size_t upr_image_loe_workspace(int B);
+int upr_image_loe(const void* low, const void* enh, double* loe, int64_t* counts, void* workspace,
+                  size_t workspace_bytes, int B, int H, int W, int sample, int dtype, void* stream);
+
 /* Lossless 8-bit RGB PNG files written entirely on the device (no reference
  * counterpart: the reference saves through PIL on the host).  hwc_u8 is B
  * images u8 [H,W,3]; image b's complete file is written contiguously at out +

@@ -31,6 +31,9 @@ int launch_content_aware(const void* x, const void* enh, void* out, float* sal_o
 size_t metrics_ws(int B, int H, int W);
 int launch_metrics(const void* enh, const void* ref, double* metrics, double* sums, int* hist, uint8_t* ws, int B,
                    int H, int W, int dtype, hipStream_t st);
+size_t loe_ws(int B);
+int launch_loe(const void* low, const void* enh, double* loe, long long* counts, uint8_t* ws, int B, int H, int W,
+               int sample, int dtype, hipStream_t st);
 int launch_decompose(const void* x, const void* illu, void* refl, int B, int C, int HW, int illu_c, int dtype,
                      hipStream_t st);
 int launch_decompose_bwd(const void* x, const void* illu, const void* g, void* gx, void* gillu, int B, int C, int HW,
@@ -167,6 +170,18 @@ int upr_image_metrics(const void* enh, const void* ref, double* metrics, double*
   if (B < 1 || H < 8 || W < 8 || (long long)H * W * 3 * 4 > 0x40000000LL) return UPR_ERR_SHAPE;
   if (workspace_bytes < metrics_ws(B, H, W)) return UPR_ERR_WORKSPACE;
   return launch_metrics(enh, ref, metrics, sums, hist, (uint8_t*)workspace, B, H, W, dtype, (hipStream_t)stream);
+}
+
+size_t upr_image_loe_workspace(int B) { return B > 0 ? loe_ws(B) : 0; }
+
+int upr_image_loe(const void* low, const void* enh, double* loe, int64_t* counts, void* workspace,
+                  size_t workspace_bytes, int B, int H, int W, int sample, int dtype, void* stream) {
+  if (!low || !enh || !loe || !workspace || !dtype_ok(dtype) || sample < 0) return UPR_ERR_ARG;
+  // (grid pixel indices and the table's entries are int32)
+  if (B < 1 || H < 1 || W < 1 || (long long)H * W >= (1LL << 31)) return UPR_ERR_SHAPE;
+  if (workspace_bytes < loe_ws(B)) return UPR_ERR_WORKSPACE;
+  return launch_loe(low, enh, loe, (long long*)counts, (uint8_t*)workspace, B, H, W, sample, dtype,
+                    (hipStream_t)stream);
 }
 
 int upr_retinex_decompose(const void* x, const void* illu, void* refl, int B, int C, int H, int W, int illu_c,

@@ -252,6 +252,29 @@ class TotalLoss(_EngineHolder):
                 self.loss_history[k].append(d[k])
         return total, d
 
+    def evaluate(self, img_low, img_enhanced, illu_map, reflectance=None):
+        """Forward only, for held-out data (trainers.train.validate): the terms
+        under the constructor weights -- no DWA, nothing appended to
+        loss_history, no autograd graph, no host read-back.  Returns the device
+        float32 tensor of the engine's scalars in upr.loss_engine.TERM_ORDER
+        (exposure .. frequency, total at 7), the dynamic smooth weight at 8."""
+        no_refl = reflectance is None
+        for t, n in ((img_low, "img_low"), (img_enhanced, "img_enhanced"), (illu_map, "illu_map"),
+                     (reflectance, "reflectance")):
+            if t is not None:
+                _require(t, n)
+        if no_refl:
+            reflectance = img_enhanced
+        eng = self._engine(img_enhanced.device)
+        eng.w = dict(self._weights)
+        if no_refl:
+            eng.w["decouple"] = 0.0
+        eng.zero_decouple = no_refl
+        with torch.no_grad():
+            _, terms = loss_forward(eng, img_low.contiguous(), img_enhanced.contiguous(), illu_map.contiguous(),
+                                    reflectance.contiguous())
+        return terms
+
     def _compute_adaptive_weights(self):
         """Dynamic Weight Average (loss.py:755-798): w_k = (L_k[-1] / L_k[-2]) / T
         (T = 2, ratio 1 when L_k[-2] <= 1e-8; the constructor weight while a

@@ -30,7 +30,15 @@ and results.csv follow the reference (trainers/train.py:189-396).  --seed also
 seeds the shuffle, the augmentation draws and the noise generator.
 --mode evaluate (an addition) runs no model: the image-quality metrics of
 utils/utils.py for every image of --input_path, against --reference_dir when
-given, written to <output_dir>/metrics.csv.
+given, written to <output_dir>/metrics.csv.  --lowlight_dir DIR (an addition)
+adds a last column `loe`, the lightness order error (Wang et al. 2013) of each
+image against its low-light source on a --loe_size grid (default 50).
+--val_dir DIR (an addition, --mode train) validates on held-out images after
+every --val_freq-th epoch (trainers.train.validate: eval-mode fp32 forward,
+TotalLoss forward only, the metrics and LOE; --val_reference_dir adds psnr /
+ssim / mse), appends val_* columns to results.csv, lets --best_by choose what
+picks best_model.pth, and writes --val_samples comparison panels under
+<save_dir>/samples/.
 """
 import argparse
 import os
@@ -55,6 +63,18 @@ def _jpeg_quality(text):
     if not 1 <= q <= 100:
         raise argparse.ArgumentTypeError(f"must be in 1..100, got {text}")
     return q
+
+
+def _int_at_least(lo):
+    def parse(text):
+        v = int(text)
+        if v < lo:
+            raise argparse.ArgumentTypeError(f"must be >= {lo}, got {text}")
+        return v
+    return parse
+
+
+_positive, _non_negative = _int_at_least(1), _int_at_least(0)
 
 
 def build_parser():
@@ -124,7 +144,39 @@ def build_parser():
                         'a single-file input ignores it)')
     p.add_argument('--reference_dir', type=str, default=None,
                    help='--mode evaluate: ground-truth images, matched by file stem (adds psnr / ssim / mse)')
+    p.add_argument('--lowlight_dir', type=str, default=None,
+                   help='--mode evaluate: the low-light sources, matched by file stem (adds the lightness order '
+                        'error column `loe`)')
+    p.add_argument('--loe_size', type=_non_negative, default=50,
+                   help='--lowlight_dir / --val_dir: LOE sample grid, pixels on the shorter side (0: every pixel)')
+    p.add_argument('--val_dir', type=str, default=None,
+                   help='--mode train: held-out low-light images; validation after every --val_freq-th epoch')
+    p.add_argument('--val_reference_dir', type=str, default=None,
+                   help='--val_dir: ground truth matched by file stem (adds val_psnr / val_ssim / val_mse)')
+    p.add_argument('--val_freq', type=_positive, default=1,
+                   help='--val_dir: validate after every N-th epoch and always after the last epoch run')
+    p.add_argument('--val_batch_size', type=_positive, default=None, help='--val_dir: default --batch_size')
+    p.add_argument('--best_by', choices=['train_total', 'val_total', 'val_psnr', 'val_loe'], default='train_total',
+                   help='--mode train: the number that picks best_model.pth and drives --patience (val_psnr: '
+                        'higher is better; val_* need --val_dir, val_psnr --val_reference_dir)')
+    p.add_argument('--val_samples', type=_non_negative, default=4,
+                   help='--val_dir: [input | enhanced | illumination] panels of the first K validation images under '
+                        '<save_dir>/samples/epoch_NNNN/ on validated --save_freq epochs and the last (0: none)')
     return p
+
+
+def parse_args(argv=None):
+    """build_parser().parse_args plus the checks that span flags (an argument
+    error, before anything touches the device)."""
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.best_by.startswith('val_') and not args.val_dir:
+        parser.error(f"--best_by {args.best_by} needs --val_dir")
+    if args.best_by == 'val_psnr' and not args.val_reference_dir:
+        parser.error("--best_by val_psnr needs --val_reference_dir")
+    if args.val_reference_dir and not args.val_dir:
+        parser.error("--val_reference_dir needs --val_dir")
+    return args
 
 
 def _model(args):
@@ -201,39 +253,54 @@ def evaluate(args):
     """Metrics of every image of --input_path (utils.utils.batch_metrics) -> <output_dir>/metrics.csv:
     `file`, then the metric names in calculate_metrics' order; one row per image
     (values as repr(float)) and a last row `mean` of the column means.
-    Consecutive images of one size share a launch, up to --batch_size."""
-    from utils.utils import batch_metrics, metric_names
+    Consecutive images of one size share a launch, up to --batch_size.
+    With --lowlight_dir a last column `loe` (utils.utils.batch_loe, --loe_size)
+    measures each image against its low-light source, matched by stem like the
+    ground truth."""
+    from utils.utils import batch_loe, batch_metrics, metric_names
     p = Path(args.input_path)
     files = [str(p)] if p.is_file() else (list_images(str(p)) if p.is_dir() else None)
     if not files:
         print(f"错误: 输入路径 '{args.input_path}' 不存在")
         return None
     paired = args.reference_dir is not None
-    names = metric_names(paired)
+    lowlight = getattr(args, 'lowlight_dir', None)
+    names = metric_names(paired) + (('loe',) if lowlight else ())
     by_stem = _reference_stems(args.reference_dir) if paired else None
+    low_by_stem = _reference_stems(lowlight) if lowlight else None
     cols = []  # per launch: [n_metrics, b] device tensors
 
-    def flush(xs, ys):
+    def flush(xs, ys, ls):
         if xs:
-            m = batch_metrics(torch.cat(xs), torch.cat(ys) if paired else None)
+            x = torch.cat(xs)
+            m = batch_metrics(x, torch.cat(ys) if paired else None)
+            if lowlight:
+                m['loe'] = batch_loe(torch.cat(ls), x, args.loe_size)
             cols.append(torch.stack([m[n] for n in names]))
 
-    xs, ys = [], []
+    xs, ys, ls = [], [], []
     for f in files:
         x, _ = load_image(f, args.max_size, device=args.device)
-        y = None
+        y = low = None
         if paired:
             rf = _reference_for(f, args.reference_dir, by_stem)
             y, _ = load_image(rf, args.max_size, device=args.device)
             if y.shape != x.shape:
                 raise ValueError(f"reference '{rf}' is {tuple(y.shape[2:])} after loading, '{f}' is "
                                  f"{tuple(x.shape[2:])}")
+        if lowlight:
+            lf = _reference_for(f, lowlight, low_by_stem)
+            low, _ = load_image(lf, args.max_size, device=args.device)
+            if low.shape != x.shape:
+                raise ValueError(f"low-light image '{lf}' is {tuple(low.shape[2:])} after loading, '{f}' is "
+                                 f"{tuple(x.shape[2:])}")
         if xs and (x.shape != xs[0].shape or len(xs) >= max(1, args.batch_size)):
-            flush(xs, ys)
-            xs, ys = [], []
+            flush(xs, ys, ls)
+            xs, ys, ls = [], [], []
         xs.append(x)
         ys.append(y)
-    flush(xs, ys)
+        ls.append(low)
+    flush(xs, ys, ls)
     table = torch.cat(cols, dim=1).t().cpu().tolist()  # the one device-to-host copy
     means = [sum(r[k] for r in table) / len(table) for k in range(len(names))]
     os.makedirs(args.output_dir, exist_ok=True)
@@ -248,7 +315,7 @@ def evaluate(args):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     if args.device is None:
         args.device = 'cuda' if torch.cuda.is_available() else 'cpu'
     print(f"使用设备: {args.device}")

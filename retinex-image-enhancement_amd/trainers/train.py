@@ -223,18 +223,173 @@ def _finish_plot(plt, path):
     plt.close()
 
 
-def save_results_to_csv(loss_history, save_dir):
-    """results.csv: one row per epoch, columns epoch + the loss keys (reference :571-600)."""
+def save_results_to_csv(loss_history, save_dir, val_history=None):
+    """results.csv: one row per epoch, columns epoch + the loss keys (reference :571-600).
+    val_history (column -> one entry per epoch, None where the epoch was not
+    validated) appends its columns after them, with empty cells for None."""
     os.makedirs(save_dir, exist_ok=True)
     csv_path = os.path.join(save_dir, 'results.csv')
     keys = list(loss_history)
+    vkeys = list(val_history) if val_history else []
     with open(csv_path, 'w', newline='') as f:
         w = csv.writer(f)
-        w.writerow(['epoch'] + keys)
+        w.writerow(['epoch'] + keys + vkeys)
         for epoch in range(max((len(v) for v in loss_history.values()), default=0)):
-            w.writerow([epoch] + [loss_history[k][epoch] if epoch < len(loss_history[k]) else '' for k in keys])
+            row = [epoch] + [loss_history[k][epoch] if epoch < len(loss_history[k]) else '' for k in keys]
+            for k in vkeys:
+                v = val_history[k][epoch] if epoch < len(val_history[k]) else None
+                row.append('' if v is None else v)
+            w.writerow(row)
     print(f"Saved results to CSV: {csv_path}")
     return csv_path
+
+
+# ---- validation on held-out images (an addition: the reference's README names --val_data_path,
+# its parser has no such flag) ----------------------------------------------------------------
+BEST_BY = ('train_total', 'val_total', 'val_psnr', 'val_loe')
+
+
+def val_columns(paired):
+    """The keys of validate()'s dict = the val_* columns of results.csv, in order:
+    val_total and the other six loss keys, calculate_metrics' names, val_loe."""
+    from utils.utils import metric_names
+    return [f'val_{k}' for k in LOSS_KEYS] + [f'val_{n}' for n in metric_names(paired)] + ['val_loe']
+
+
+def check_best_by(best_by, has_val, has_reference):
+    """The rules of --best_by: a val_* choice needs --val_dir, val_psnr also --val_reference_dir."""
+    if best_by not in BEST_BY:
+        raise ValueError(f"best_by must be one of {BEST_BY}, got {best_by!r}")
+    if best_by.startswith('val_') and not has_val:
+        raise ValueError(f"--best_by {best_by} needs --val_dir")
+    if best_by == 'val_psnr' and not has_reference:
+        raise ValueError("--best_by val_psnr needs --val_reference_dir")
+
+
+class BestTracker:
+    """Which epoch is the best so far and how long since (best_model.pth, --patience).
+    update(train_total, val) -> True (a new best), False (no improvement: the
+    patience counter advanced) or None (a val_* choice on an epoch that was not
+    validated: neither).  val_psnr is better when higher, the others when lower."""
+
+    def __init__(self, best_by='train_total'):
+        self.best_by = best_by
+        self.higher = best_by == 'val_psnr'
+        self.best = -float('inf') if self.higher else float('inf')
+        self.counter = 0
+
+    def update(self, train_total, val=None):
+        if self.best_by == 'train_total':
+            v = train_total
+        elif val is None:
+            return None
+        else:
+            v = val[self.best_by]
+        if (v > self.best) if self.higher else (v < self.best):
+            self.best, self.counter = v, 0
+            return True
+        self.counter += 1
+        return False
+
+
+def make_val_loaders(val_dir, reference_dir=None, image_size=640, batch_size=8, num_workers=4, device=None):
+    """(loader, reference_loader or None) over the held-out images: LowLightDataset
+    without augmentation (every image letterboxed to image_size), in file order,
+    the short last batch kept.  The ground truth of NAME.ext is the file of
+    reference_dir with stem NAME, loaded the same way."""
+    from datasets.dataset import DeviceLoader, LowLightDataset
+
+    def loader(ds):
+        ds.device = device
+        # seed 0: the (unused) draws would come from a generator of the loader's own, never the global `random`
+        return DeviceLoader(ds, batch_size=batch_size, shuffle=False, num_workers=num_workers, drop_last=False,
+                            device=device, seed=0)
+
+    ds = LowLightDataset(val_dir, image_size=image_size, augment=False, advanced_augment=False)
+    if reference_dir is None:
+        return loader(ds), None
+    ref = LowLightDataset(reference_dir, image_size=image_size, augment=False, advanced_augment=False)
+    by_stem = {}
+    for f in ref.image_files:
+        by_stem.setdefault(os.path.splitext(os.path.basename(f))[0], f)
+    stems = [os.path.splitext(os.path.basename(f))[0] for f in ds.image_files]
+    missing = [f for f, st in zip(ds.image_files, stems) if st not in by_stem]
+    if missing:
+        raise ValueError(f"no ground truth in '{reference_dir}' for {', '.join(repr(m) for m in missing)} "
+                         f"(matched by file stem)")
+    ref.image_files = [by_stem[st] for st in stems]
+    return loader(ds), loader(ref)
+
+
+def validate(model, loader, criterion, device, reference_loader=None, loe_size=50, on_batch=None):
+    """One pass over held-out images: the eval-mode forward in fp32 under
+    no_grad (the inference executor, whatever --use_amp says), TotalLoss forward
+    only (criterion.evaluate: constructor weights, no DWA, no history),
+    batch_metrics against the ground truth of reference_loader when given, and
+    batch_loe against the input.  Per-image values are summed on the device in
+    fp64 (a batch's loss terms weighted by its image count); one device-to-host
+    copy at the end.  Returns {val_columns(paired)[i]: mean over the images}.
+    on_batch(first_index, low, enh, illu), when given, sees every batch (the
+    sample panels).  The run is left as found: no parameter, buffer, optimiser,
+    scaler, loss history or `random` state changes; model.training is restored."""
+    from upr.loss_engine import TERM_ORDER
+    from utils.utils import batch_loe, batch_metrics, metric_names
+    paired = reference_loader is not None
+    names = metric_names(paired)
+    order = [TERM_ORDER.index(k) for k in LOSS_KEYS]
+    was_training = model.training
+    model.eval()
+    sums, n = None, 0
+    try:
+        with torch.no_grad(), torch.autocast("cuda", enabled=False):
+            refs = iter(reference_loader) if paired else None
+            for low in loader:
+                low = low.to(device, torch.float32)
+                gt = None
+                if paired:
+                    gt = next(refs).to(device, torch.float32)
+                    if gt.shape != low.shape:
+                        files = loader.dataset.image_files[n:n + low.shape[0]]
+                        rfiles = reference_loader.dataset.image_files[n:n + low.shape[0]]
+                        raise ValueError(f"ground truth {rfiles} letterboxes to {tuple(gt.shape[2:])}, "
+                                         f"{files} to {tuple(low.shape[2:])}")
+                enh, refl, illu = model(low)
+                terms = criterion.evaluate(low, enh, illu, refl)
+                m = batch_metrics(enh, gt)
+                b = low.shape[0]
+                row = torch.cat([terms[order].double() * b, torch.stack([m[k] for k in names]).sum(dim=1),
+                                 batch_loe(low, enh, loe_size).sum().reshape(1)])
+                sums = row if sums is None else sums + row
+                if on_batch is not None:
+                    on_batch(n, low, enh, illu)
+                n += b
+    finally:
+        model.train(was_training)
+    if n == 0:
+        raise ValueError("validate: the loader gave no images")
+    return dict(zip(val_columns(paired), (sums / n).cpu().tolist()))  # the one device-to-host copy
+
+
+def save_val_samples(sample_dir, files, first, low, enh, illu, k, output_format=None):
+    """<sample_dir>/<stem>_comparison.<ext> for the images of this batch among the
+    first k of the validation set: the [input | enhanced | illumination] panel
+    of enhancers.simple_enhance.create_comparison (the reference's
+    save_sample_visualizations, :399-517, without torchvision / matplotlib)."""
+    from enhancers.simple_enhance import create_comparison
+    fmt = dict(output_format or {})
+    ext = fmt.get('image_format', 'png')
+    os.makedirs(sample_dir, exist_ok=True)
+    for i in range(max(0, min(low.shape[0], k - first))):
+        stem = os.path.splitext(os.path.basename(files[first + i]))[0]
+        create_comparison(low[i:i + 1], enh[i:i + 1], os.path.join(sample_dir, f"{stem}_comparison.{ext}"),
+                          illu_map=illu[i:i + 1], **fmt)
+
+
+def _output_format(args):
+    return dict(png_encoder=getattr(args, 'png_encoder', 'host'), image_format=getattr(args, 'image_format', 'png'),
+                jpeg_quality=getattr(args, 'jpeg_quality', 95), jpeg_subsampling=getattr(args, 'jpeg_subsampling', '444'),
+                jpeg_optimize=getattr(args, 'jpeg_optimize', False),
+                jpeg_gray_maps=getattr(args, 'jpeg_gray_maps', False))
 
 
 def train(args):
@@ -242,12 +397,19 @@ def train(args):
     and the device data path.  Differences: the schedulers are this module's
     (closed forms; a resumed run continues the schedule at its epoch instead of
     restarting it), TensorBoard and the matplotlib curves are used when they
-    import, save_sample_visualizations is not built, and the rows of
-    results.csv are the epochs this call ran.  Returns the loss history."""
+    import, save_sample_visualizations is replaced by the validation pass's
+    panels, and the rows of results.csv are the epochs this call ran.
+    With --val_dir, validate() runs after every --val_freq-th epoch and after the
+    last one: its numbers are printed, logged as Val/<name>, appended to
+    results.csv as val_* columns, and --best_by may pick best_model.pth and drive
+    --patience by one of them.  Returns the loss history."""
     from datasets.dataset import get_train_dataloader
     from losses.loss import TotalLoss
     from models.model import MultiScaleUP_Retinex
 
+    val_dir, val_ref_dir = getattr(args, 'val_dir', None), getattr(args, 'val_reference_dir', None)
+    best_by = getattr(args, 'best_by', 'train_total')
+    check_best_by(best_by, val_dir is not None, val_ref_dir is not None)
     if not torch.cuda.is_available():
         raise RuntimeError("--mode train runs on ROCm devices only (no CPU fallback)")
     dev = getattr(args, 'device', None)
@@ -293,9 +455,41 @@ def train(args):
     if len(train_loader) == 0:
         print(f"No training batches: {len(train_loader.dataset)} samples, batch_size={args.batch_size}")
         return None
+    val_loader = val_ref_loader = None
+    if val_dir is not None:
+        val_loader, val_ref_loader = make_val_loaders(
+            val_dir, val_ref_dir, image_size=args.image_size,
+            batch_size=getattr(args, 'val_batch_size', None) or args.batch_size, num_workers=args.num_workers,
+            device=device)
+        print(f"Validation: {len(val_loader.dataset)} images in {len(val_loader)} batches, best model by {best_by}")
+    val_freq, val_samples = getattr(args, 'val_freq', 1), getattr(args, 'val_samples', 4)
+    save_freq, loe_size = getattr(args, 'save_freq', 10), getattr(args, 'loe_size', 50)
+    val_history = {k: [] for k in val_columns(val_ref_loader is not None)} if val_loader is not None else None
+
+    def run_validation(epoch, samples):
+        """validate() -> its dict, printed and logged; samples: also write this epoch's panels."""
+        on_batch = None
+        if samples:
+            sample_dir = os.path.join(args.save_dir, 'samples', f'epoch_{epoch + 1:04d}')
+            files, fmt = val_loader.dataset.image_files, _output_format(args)
+
+            def on_batch(first, low, enh, illu):
+                save_val_samples(sample_dir, files, first, low, enh, illu, val_samples, fmt)
+        t0 = time.time()
+        val_loader.set_epoch(0)
+        if val_ref_loader is not None:
+            val_ref_loader.set_epoch(0)
+        val = validate(model, val_loader, criterion, device, reference_loader=val_ref_loader, loe_size=loe_size,
+                       on_batch=on_batch)
+        print(f"  Validation: {time.time() - t0:.2f}s, " + ", ".join(f"{k} {v:.6f}" for k, v in val.items()))
+        if writer is not None:
+            for k, v in val.items():
+                writer.add_scalar(f"Val/{k[len('val_'):]}", v, epoch)
+        return val
+
     writer = _summary_writer(os.path.join(args.save_dir, 'logs', datetime.now().strftime('%Y%m%d_%H%M%S')))
     loss_history = {k: [] for k in LOSS_KEYS}
-    best_loss, patience_counter = float('inf'), 0
+    tracker = BestTracker(best_by)
     for epoch in range(start_epoch, args.num_epochs):
         train_loader.set_epoch(epoch)
         avg = train_one_epoch(model, train_loader, criterion, optimizer, device, epoch, writer, scaler=scaler,
@@ -310,20 +504,35 @@ def train(args):
             writer.add_scalar('Learning_Rate', current_lr, epoch)
             for k in LOSS_KEYS:
                 writer.add_scalar(f'Epoch_Loss/{k}', loss_history[k][-1], epoch)
-        is_best = loss_history['total'][-1] < best_loss
+        val, sampled = None, False
+        if val_loader is not None:
+            last = epoch == args.num_epochs - 1
+            if (epoch + 1) % val_freq == 0 or last:
+                sampled = val_samples > 0 and ((epoch + 1) % save_freq == 0 or last)
+                val = run_validation(epoch, sampled)
+        is_best = tracker.update(loss_history['total'][-1], val)
         if is_best:
-            best_loss, patience_counter = loss_history['total'][-1], 0
-            print(f"  New best loss: {best_loss:.6f}")
+            print(f"  New best {'loss' if best_by == 'train_total' else best_by}: {tracker.best:.6f}")
+        elif is_best is None:
+            print(f"  Not validated: best {best_by} and patience unchanged")
         else:
-            patience_counter += 1
-            print(f"  Patience: {patience_counter}/{patience}")
-        save_checkpoint(model, optimizer, epoch, args.save_dir, is_best)
-        if patience_counter >= patience:
-            print(f"Early stopping after {epoch + 1} epochs, best loss {best_loss:.6f}")
+            print(f"  Patience: {tracker.counter}/{patience}")
+        stop = tracker.counter >= patience
+        if stop and val_loader is not None and (val is None or (val_samples > 0 and not sampled)):
+            # early stopping makes this the last epoch run: it is validated, and its panels written
+            again = run_validation(epoch, val_samples > 0)
+            val = again if val is None else val
+        if val_history is not None:
+            for k in val_history:
+                val_history[k].append(None if val is None else val[k])
+        save_checkpoint(model, optimizer, epoch, args.save_dir, bool(is_best))
+        if stop:
+            print(f"Early stopping after {epoch + 1} epochs, best loss {tracker.best:.6f}")
             break
+    best_loss = tracker.best
     if writer is not None:
         writer.close()
     save_loss_curves(loss_history, args.save_dir)
-    save_results_to_csv(loss_history, args.save_dir)
+    save_results_to_csv(loss_history, args.save_dir, val_history)
     print(f"Training completed. Best loss: {best_loss:.6f}. Models saved in: {args.save_dir}")
     return loss_history

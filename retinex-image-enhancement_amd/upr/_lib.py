@@ -128,6 +128,9 @@ SIGNATURES = {
     "upr_image_metrics_workspace": (c_size_t, [c_int, c_int, c_int]),
     "upr_image_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int,
                                   c_int, c_int, c_void_p]),
+    "upr_image_loe_workspace": (c_size_t, [c_int]),
+    "upr_image_loe": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int,
+                              c_int, c_void_p]),
     "upr_png_bound": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
     "upr_png_encode": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
                                c_size_t, c_void_p]),

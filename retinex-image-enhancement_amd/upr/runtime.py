@@ -572,6 +572,34 @@ def image_metrics(enh, ref=None, sums=False, hist=False):
     return m, s, h
 
 
+def image_loe(low, enh, size=50, counts=False):
+    """Lightness order error (Wang et al. 2013; include/upr.h upr_image_loe) of
+    every image of enh [B,3,H,W] against its low-light input low (same shape,
+    dtype and device) on the size-pixel sample grid (0: every pixel).  Returns
+    loe [B] f64, or (loe, counts [B,2] int64 = (D, N)) with counts=True, on the
+    device, no synchronisation."""
+    _require_device(low, "low")
+    _require_device(enh, "enhanced")
+    if low.dim() != 4 or low.shape[1] != 3:
+        raise RuntimeError(f"expected an image batch of shape [B, 3, H, W], got {tuple(low.shape)}")
+    if enh.shape != low.shape or enh.dtype != low.dtype or enh.device != low.device:
+        raise RuntimeError("image_loe: the enhanced image must match the input's shape, dtype and device")
+    if int(size) != size or size < 0:
+        raise ValueError(f"image_loe: size must be an integer >= 0, got {size!r}")
+    low, enh = low.contiguous(), enh.contiguous()
+    B, _, H, W = low.shape
+    dev = low.device
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        out = torch.empty((B,), dtype=torch.float64, device=dev)
+        c = torch.empty((B, 2), dtype=torch.int64, device=dev) if counts else None
+        ws = _WS.get(dev, lib.upr_image_loe_workspace(B))
+        rc = lib.upr_image_loe(_ptr(low), _ptr(enh), _ptr(out), _ptr(c), _ptr(ws), ctypes.c_size_t(ws.numel()), B, H,
+                               W, int(size), dtype_code(low.dtype), _stream(dev))
+    L.check(rc, "upr_image_loe")
+    return (out, c) if counts else out
+
+
 class _Decompose(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, illu):

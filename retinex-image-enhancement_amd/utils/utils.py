@@ -7,6 +7,8 @@ makes one device-to-host copy.  Inputs are device tensors [3,H,W] / [1,3,H,W]
 or numpy arrays in the reference's [H,W,C] layout (uploaded to the current
 device); CPU tensors are refused like everywhere else in this package.
 batch_metrics is the batched, non-synchronising form the reference lacks.
+batch_loe / calculate_loe (an addition) give the lightness order error of an
+enhanced image against its own low-light input (upr.runtime.image_loe).
 
 Divergences: the simplified NIQE clamps a window's variance at 0 (the
 reference's float32 expression yields NaN on flat windows), and a batch is
@@ -114,6 +116,27 @@ def calculate_saturation(img):
 def calculate_naturalness(img):
     """0.3 colour balance + 0.4 contrast score + 0.3 brightness score (utils.py:306-333)."""
     return float(_single(img)[0][_INDEX["naturalness"]])
+
+
+def batch_loe(img_low, img_enhanced, size=50):
+    """Lightness order error (Wang et al. 2013, "Naturalness preserved
+    enhancement algorithm for non-uniform illumination images") of every image
+    of img_enhanced [B,3,H,W] against its low-light input img_low, on a
+    size-pixel sample grid (0: every pixel): float64 device tensor [B].  No
+    ground truth involved; no synchronisation, no host copy."""
+    x = _as_batch(img_low, "img_low")
+    y = _as_batch(img_enhanced, "img_enhanced")
+    if y.dtype != x.dtype:
+        y = y.to(x.dtype)
+    return runtime.image_loe(x, y, size)
+
+
+def calculate_loe(img_low, img_enhanced, size=50):
+    """batch_loe of one image pair as a Python float (inputs as calculate_metrics takes them)."""
+    v = batch_loe(img_low, img_enhanced, size)
+    if v.shape[0] != 1:
+        raise RuntimeError(f"expected one image, got a batch of {v.shape[0]} (use batch_loe)")
+    return float(v.cpu()[0])
 
 
 def ensure_dir(directory):
