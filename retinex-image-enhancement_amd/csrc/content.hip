@@ -536,9 +536,7 @@ int launch_content_aware(const void* x, const void* enh, void* out, float* sal_o
   sum = 1. / sum;
   for (int i = 0; i < 15; ++i) g.k[i] *= sum;
   const size_t n = (size_t)B * HW;
-  // UPR_CA_FUSED=0: the three-kernel saliency form and the scalar passes (A/B)
-  static const bool fused = [] { const char* e = getenv("UPR_CA_FUSED"); return !e || atoi(e) != 0; }();
-  if (fused && HW % 4 == 0) {
+  if (HW % 4 == 0) {
     // one fused saliency pass (tiles of 64 x 64) + the 4-pixel attention / apply
     // passes, each consumer reducing its producer's per-block min / max itself
     const int tiles_x = (W + CA_TW - 1) / CA_TW, tiles = ca_tiles(H, W);
@@ -563,6 +561,7 @@ int launch_content_aware(const void* x, const void* enh, void* out, float* sal_o
                          att_out, (const float*)enh, (float*)out, HW4);
     return (int)hipGetLastError();
   }
+  // H * W % 4 != 0: the three-kernel saliency form and the scalar passes
   if (dtype == kF16)
     hipLaunchKernelGGL((ca_lap_kernel<half_t>), dim3(gd(n)), dim3(256), 0, st, (const half_t*)x, lap, B, H, W);
   else

@@ -105,9 +105,13 @@ struct HaloArgs {
   ConvOp op;
   HaloSteps hs;
   int tiles_x, tiles_y, ntiles, region_bytes;
-  // experiments (UPR_HALO_SCHED="flags,n"; timing only, results wrong for 4..64):
-  // 1 setprio / 2 start stagger (n x s_sleep(127)) for the grid's 2nd half,
-  // 4 no staging, 8 no epilogue, 16 no LDS stores, 32 no prefetch loads, 64 no post-staging barrier
+  // timing-experiment flags, always 0: the launcher sets 0 and nothing else
+  // writes it (1 setprio / 2 start stagger (n x s_sleep(127)) for the grid's 2nd
+  // half, 4 no staging, 8 no epilogue, 16 no LDS stores, 32 no prefetch loads,
+  // 64 no post-staging barrier; results wrong for 4..64).  The kernel's tests
+  // of it are dead at run time but stay for now: taking them out moved the
+  // register allocation of every instantiation, and 9 of 63 gained registers
+  // or scratch
   int sched;
 };
 
@@ -843,7 +847,6 @@ static int seg_kind(const ConvOp& op, int s, int Ho, int Wo, bool& pair) {
 //   fp16: 4-row tiles at 2 blocks/CU for N >= 64 (64-wide N blocks) and the FAM
 //         fusion (weights resident); 8-row tiles at 2 blocks/CU for N = 32 and
 //         1x1; the residual head 4-row at 3 blocks/CU
-// UPR_HALO="<th>,<occ>" overrides (experiments).
 static void halo_choice(int dtype, int prog, int store, int N, int& th, int& occ) {
   if (dtype == kF16) {
     th = N >= 64 || prog == kProgFam ? 4 : 8;

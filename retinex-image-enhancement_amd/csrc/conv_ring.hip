@@ -85,9 +85,6 @@ enum RingMode : int { kRingConv = 0, kRingHead = 1, kRingFam = 2, kRingS2 = 3 };
 enum RingFlags : int {
   kRingRes = 1, kRingRelu = 2, kRingSc = 4, kRingOcc3 = 8, kRingWide = 16, kRingOut2 = 32, kRingOut32 = 64,
   kRingDil2 = 128, kRingResPre = 256, kRingPool = 512, kRingXPool = 1024, kRingR32 = 2048,
-  // timing ablations only (results garbage; UPR_RING_ABL, tools/convbench.py):
-  // no ring DMA after the first two steps / no MFMAs / no output stores
-  kRingAblDma = 4096, kRingAblMma = 8192, kRingAblSt = 16384,
   // fp32 ring only: split in registers (ConvOp::mma16) -- the fragments are
   // split into fp16 (hi, lo) after the LDS read and run on v_mfma_f32_16x16x32_f16
   kRingMma16 = 32768,
@@ -288,8 +285,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, RingCfg<MODE, C, NB, FL
   auto issue = [&](int k) {
     const bool live = dc.j < nu;
     const int grp = (k + 1) & 3;
-    if ((FL & kRingAblDma) && k >= 2) {
-    } else if (!dma_wave) {
+    if (!dma_wave) {
     } else if constexpr (S2) {
       la.issue(srcA, csA, dc.b, Hin, Win, 2 * (dc.y0 + 4 * dc.s), 2 * dc.x0 - 1, live, zero, ringA, grp, wave);
     } else {
@@ -480,12 +476,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, RingCfg<MODE, C, NB, FL
                 f16x8_r wf;
                 if constexpr (K::WREG) wf = wr[(r * 3 + sc) * K::KS + ks][nt];
                 else wf = w[sc][nt];
-                if constexpr ((FL & kRingAblMma) != 0) {
-                  if (c == 0 && sc == 0) acc[nt][g] = bias4[nt] + (f32x4_r)__builtin_bit_cast(f32x4_r, x[sc * GPW + g]);
-                } else {
-                  acc[nt][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf, x[sc * GPW + g],
-                                                                      c == 0 && sc == 0 ? bias4[nt] : acc[nt][g], 0, 0, 0);
-                }
+                acc[nt][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf, x[sc * GPW + g],
+                                                                    c == 0 && sc == 0 ? bias4[nt] : acc[nt][g], 0, 0, 0);
               }
         };
         ld(0, bx[0], bw[0]);
@@ -1600,12 +1592,6 @@ static bool ring_seg_ok(const ConvSeg& s) {
 
 template <int MODE, int C, int NB, int FL>
 static int ring_relu(const ConvOp& op, hipStream_t st) {
-  // timing ablations of the plain 32/64-channel programs (UPR_RING_ABL = 1 no DMA, 2 no MFMA)
-  static const int abl = [] { const char* e = getenv("UPR_RING_ABL"); return e ? atoi(e) : 0; }();
-  if constexpr (MODE == kRingConv && (FL & ~(kRingWide | kRingOcc3)) == 0) {
-    if (abl == 1 && op.relu) return launch_ring_cfg<MODE, C, NB, FL | kRingRelu | kRingAblDma>(op, st);
-    if (abl == 2 && op.relu) return launch_ring_cfg<MODE, C, NB, FL | kRingRelu | kRingAblMma>(op, st);
-  }
   return op.relu ? launch_ring_cfg<MODE, C, NB, FL | kRingRelu>(op, st) : launch_ring_cfg<MODE, C, NB, FL>(op, st);
 }
 

@@ -1071,11 +1071,8 @@ static int launch_hwide3(const ConvOp& op, hipStream_t st) {
 // (< 8 pixels x 1024 channels x 2 B), so a 16 KiB zero block
 __device__ __attribute__((aligned(256))) uint4 g_halo_zero[1024];
 
-// ABL (timing ablations only, compiled on request -- the dispatcher instantiates
-// ABL = 0; results are garbage; profiles/r3_hwide4_bneck_ablations*): bit 0 drops
-// the main loop's DMA (region rows + B stages), bit 1 its LDS fragment reads,
-// bit 2 the epilogue, bit 3 the MFMAs.  DS: operand-swapped MFMAs + the
-// direct-store epilogue above (hw4_ds_ok decides per op).
+// DS: operand-swapped MFMAs + the direct-store epilogue above (hw4_ds_ok
+// decides per op).
 // DL: dilated 3x3 (the ASPP branches, dilation = padding = d, any d < W): the
 // three tap rows of a chunk read three disjoint 4-row bands, so the K loop is
 // (tap row, chunk, tap column) and each (tap row, chunk) REGION of 4 rows is
@@ -1108,8 +1105,8 @@ __device__ __attribute__((aligned(256))) uint4 g_halo_zero[1024];
 // region k's last tap (three steps of lookahead), B(S + 2) after barrier S.
 // NR: the op has no residual (res1 = res2 = null): no residual prefetch
 // registers (rv0) -- 32 VGPRs the bottleneck conv1 / ASPP programs spilled for
-template <int BN, int W, int NCH, int ABL = 0, bool DS = false, bool DL = false, int TR = 4, int NSC = 0,
-          bool PW = false, bool S2 = false, bool NR = false>
+template <int BN, int W, int NCH, bool DS = false, bool DL = false, int TR = 4, int NSC = 0, bool PW = false,
+          bool S2 = false, bool NR = false>
 __global__ __launch_bounds__(512, 2) void conv_hwide4_kernel(ConvOp op) {
   using HC = Halo3Cfg<BN, W, TR, PW ? 12 : S2 ? 4 * TR : 0>;
   static_assert(TR == 4 || (NCH == 1 && !DL && DS), "2-row tiles: one chunk, direct store");
@@ -1406,7 +1403,6 @@ __global__ __launch_bounds__(512, 2) void conv_hwide4_kernel(ConvOp op) {
   };
   // one A row fragment against all WN B fragments
   auto mm_row = [&](int a, const f16x8_w& af, const f16x8_w (&bf)[WN]) {
-    if constexpr ((ABL & 8) != 0) return;
 #pragma unroll
     for (int b = 0; b < WN; ++b) {
       if constexpr (DS)
@@ -1521,20 +1517,18 @@ __global__ __launch_bounds__(512, 2) void conv_hwide4_kernel(ConvOp op) {
           else
             asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(VB) : "memory");
           __builtin_amdgcn_s_barrier();
-          if constexpr (!(ABL & 1)) {
-            issue_b(S % NBS, bc, bt);
-            if constexpr (S2) {
-              if constexpr (S % 3 == 2 && S / 3 + 2 < NREG) region_s2(S / 3 + 2);
-            } else if constexpr (PW) {
-              if constexpr (S + 3 < NCH) {
+          issue_b(S % NBS, bc, bt);
+          if constexpr (S2) {
+            if constexpr (S % 3 == 2 && S / 3 + 2 < NREG) region_s2(S / 3 + 2);
+          } else if constexpr (PW) {
+            if constexpr (S + 3 < NCH) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) region_row(S + 3, r);
-              }
-            } else if constexpr (DL) {
-              if constexpr (S % 3 == 2) region_dl(S / 3 + 2);
-            } else {
-              issue_rows(nc, nt);
+              for (int r = 0; r < 4; ++r) region_row(S + 3, r);
             }
+          } else if constexpr (DL) {
+            if constexpr (S % 3 == 2) region_dl(S / 3 + 2);
+          } else {
+            issue_rows(nc, nt);
           }
           if constexpr (DS && !NR && S == TOTAL - 2)
             hw4_res_load<WM, WN, HC::WAVES_M, W>(op, rv0, m0, n0, wm, wn, lane);
@@ -1556,40 +1550,30 @@ __global__ __launch_bounds__(512, 2) void conv_hwide4_kernel(ConvOp op) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
     }
-    if constexpr ((ABL & 4) != 0) {
-      if (acc[0][0][0] == 12345.f)
-        hw4_direct_epilogue<BN, WM, WN, HC::WAVES_M, W, !NR>(op, acc, m0, n0, wm, wn, lane, rv0, smem);
-    } else {
-      hw4_direct_epilogue<BN, WM, WN, HC::WAVES_M, W, !NR>(op, acc, m0, n0, wm, wn, lane, rv0, smem);
-    }
-    if constexpr ((ABL & 4) != 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    hw4_direct_epilogue<BN, WM, WN, HC::WAVES_M, W, !NR>(op, acc, m0, n0, wm, wn, lane, rv0, smem);
     return;
   }
   // the last steps' (unread) DMAs land before the epilogue reuses LDS
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();  // every wave is done with the ring and stages before the epilogue reuses LDS
 
-  if constexpr ((ABL & 4) != 0) {
-    if (acc[0][0][0] == 12345.f) wide_epilogue<BN, WM, WN, HC::WAVES_M, BM, true, W>(op, acc, smem, m0, n0, M, HW);
-  } else {
-    wide_epilogue<BN, WM, WN, HC::WAVES_M, BM, true, W>(op, acc, smem, m0, n0, M, HW);
-  }
+  wide_epilogue<BN, WM, WN, HC::WAVES_M, BM, true, W>(op, acc, smem, m0, n0, M, HW);
 }
 
-template <int BN, int W, int NCH, int ABL = 0, bool DS = false, bool DL = false, int TR = 4, int NSC = 0,
-          bool PW = false, bool S2 = false, bool NR = false>
+template <int BN, int W, int NCH, bool DS = false, bool DL = false, int TR = 4, int NSC = 0, bool PW = false,
+          bool S2 = false, bool NR = false>
 static int launch_hwide4_k(const ConvOp& op, hipStream_t st) {
   using HC = Halo3Cfg<BN, W, TR, PW ? 12 : S2 ? 4 * TR : 0>;
   static bool attr_set = false;
   if (!attr_set) {
     const hipError_t e =
-        hipFuncSetAttribute((const void*)conv_hwide4_kernel<BN, W, NCH, ABL, DS, DL, TR, NSC, PW, S2, NR>,
+        hipFuncSetAttribute((const void*)conv_hwide4_kernel<BN, W, NCH, DS, DL, TR, NSC, PW, S2, NR>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, HC::LDS);
     if (e != hipSuccess) return (int)e;
     attr_set = true;
   }
   const int grid = (op.B * op.Ho * W / HC::BM) * (op.N / BN);
-  hipLaunchKernelGGL((conv_hwide4_kernel<BN, W, NCH, ABL, DS, DL, TR, NSC, PW, S2, NR>), dim3(grid), dim3(512),
+  hipLaunchKernelGGL((conv_hwide4_kernel<BN, W, NCH, DS, DL, TR, NSC, PW, S2, NR>), dim3(grid), dim3(512),
                      HC::LDS, st, op);
   return (int)hipGetLastError();
 }
@@ -1597,18 +1581,10 @@ static int launch_hwide4_k(const ConvOp& op, hipStream_t st) {
 template <int BN, int W, int NCH>
 static int launch_hwide4(const ConvOp& op, hipStream_t st) {
   if (hw4_ds_ok(op)) {
-    if constexpr (BN == 256 && W == 64 && NCH == 4) {
-      // UPR_HW4_ABL: timing ablations of the bottleneck form (garbage results; profiles/r6_hw4_abl*)
-      static const int abl = [] { const char* e = getenv("UPR_HW4_ABL"); return e ? atoi(e) : 0; }();
-      if (!op.res1 && !op.res2 && abl == 1) return launch_hwide4_k<BN, W, NCH, 1, true, false, 4, 0, false, false, true>(op, st);
-      if (!op.res1 && !op.res2 && abl == 4) return launch_hwide4_k<BN, W, NCH, 4, true, false, 4, 0, false, false, true>(op, st);
-      if (!op.res1 && !op.res2 && abl == 5) return launch_hwide4_k<BN, W, NCH, 5, true, false, 4, 0, false, false, true>(op, st);
-      if (!op.res1 && !op.res2 && abl == 7) return launch_hwide4_k<BN, W, NCH, 7, true, false, 4, 0, false, false, true>(op, st);
-    }
-    if (!op.res1 && !op.res2) return launch_hwide4_k<BN, W, NCH, 0, true, false, 4, 0, false, false, true>(op, st);
-    return launch_hwide4_k<BN, W, NCH, 0, true>(op, st);
+    if (!op.res1 && !op.res2) return launch_hwide4_k<BN, W, NCH, true, false, 4, 0, false, false, true>(op, st);
+    return launch_hwide4_k<BN, W, NCH, true>(op, st);
   }
-  return launch_hwide4_k<BN, W, NCH, 0, false>(op, st);
+  return launch_hwide4_k<BN, W, NCH, false>(op, st);
 }
 
 // the compile-time-schedule hwide4 for the graph's shapes (bottleneck: W 64,
@@ -1623,10 +1599,10 @@ static int launch_hwide34(const ConvOp& op, hipStream_t st) {
       // dec3 (W 128, 2 chunks) on the direct-store form only (its LDS-epilogue
       // straight line spilled 40 VGPRs): dec3.conv.0 shape 0.196 -> 0.153 ms,
       // conv.3 (+ residual) 0.223 -> 0.186 (same-box A/B, profiles/r3_hw4_ds_ab.txt)
-      if (nch == 2 && hw4_ds_ok(op)) return launch_hwide4_k<BN, W, 2, 0, true>(op, st);
+      if (nch == 2 && hw4_ds_ok(op)) return launch_hwide4_k<BN, W, 2, true>(op, st);
       // 256-channel inputs at W 128 (the training step's VGG-19 conv3_x and
       // their input gradients, losses/loss.py:198-211)
-      if (nch == 4 && hw4_ds_ok(op)) return launch_hwide4_k<BN, W, 4, 0, true>(op, st);
+      if (nch == 4 && hw4_ds_ok(op)) return launch_hwide4_k<BN, W, 4, true>(op, st);
     }
   }
   return launch_hwide3<BN, W>(op, st);
@@ -1663,14 +1639,11 @@ static int hw4_pw_route(const ConvOp& op, hipStream_t st) {
   if (s.Hin != op.Ho || s.Win != op.Wo || op.Wo != 64 || op.N % 256 || (op.Ho * op.Wo) % 256 || op.Kpad != s.C)
     return kErrUnsupported;
   if (s.cs % 8 || s.coff % 8 || (uintptr_t)s.src % 16 || !hw4_ds_ok(op)) return kErrUnsupported;
-  // UPR_HW4_PW: 0 = the gathered kernel instead, 2 = no chunk rotation (A/B, tools/convbench.py)
-  static const int mode = [] { const char* e = getenv("UPR_HW4_PW"); return e ? atoi(e) : 1; }();
-  if (mode == 0) return kErrUnsupported;
   ConvOp o = op;
-  o.krot = mode != 2;
-  if (s.C == 256) return launch_hwide4_k<256, 64, 4, 0, true, false, 4, 0, true>(o, st);
-  if (s.C == 1024) return launch_hwide4_k<256, 64, 16, 0, true, false, 4, 0, true>(o, st);
-  if (s.C == 1280) return launch_hwide4_k<256, 64, 20, 0, true, false, 4, 0, true>(o, st);  // (+ global branch)
+  o.krot = 1;
+  if (s.C == 256) return launch_hwide4_k<256, 64, 4, true, false, 4, 0, true>(o, st);
+  if (s.C == 1024) return launch_hwide4_k<256, 64, 16, true, false, 4, 0, true>(o, st);
+  if (s.C == 1280) return launch_hwide4_k<256, 64, 20, true, false, 4, 0, true>(o, st);  // (+ global branch)
   return kErrUnsupported;
 }
 
@@ -1683,23 +1656,20 @@ static int hw4_s2_route(const ConvOp& op, hipStream_t st) {
     return kErrUnsupported;
   if (s.Hin != 2 * op.Ho || s.Win != 2 * op.Wo || op.N % 128 || op.Kpad != 9 * s.C || !hw4_ds_ok(op))
     return kErrUnsupported;
-  static const bool off = [] { const char* e = getenv("UPR_HW4_S2"); return e && atoi(e) == 0; }();
-  if (off) return kErrUnsupported;  // A/B against the gathered kernel (tools/convbench.py)
   if (op.Wo == 64 && op.Ho % 4 == 0) {
-    if (s.C == 64) return launch_hwide4_k<128, 64, 1, 0, true, false, 4, 0, false, true>(op, st);
-    if (s.C == 128) return launch_hwide4_k<128, 64, 2, 0, true, false, 4, 0, false, true>(op, st);
-    if (s.C == 256) return launch_hwide4_k<128, 64, 4, 0, true, false, 4, 0, false, true>(op, st);
+    if (s.C == 64) return launch_hwide4_k<128, 64, 1, true, false, 4, 0, false, true>(op, st);
+    if (s.C == 128) return launch_hwide4_k<128, 64, 2, true, false, 4, 0, false, true>(op, st);
+    if (s.C == 256) return launch_hwide4_k<128, 64, 4, true, false, 4, 0, false, true>(op, st);
   }
   if (op.Wo == 128 && op.Ho % 2 == 0 && s.C == 64)
-    return launch_hwide4_k<128, 128, 1, 0, true, false, 2, 0, false, true>(op, st);
+    return launch_hwide4_k<128, 128, 1, true, false, 2, 0, false, true>(op, st);
   return kErrUnsupported;
 }
 
 static int halo_route(const ConvOp& op, hipStream_t st) {
   if (const int nsc = hw4_sc_ok(op)) {
-    if (nsc == 1) return launch_hwide4_k<128, 128, 2, 0, true, false, 4, 1>(op, st);
-    static const bool off = [] { const char* e = getenv("UPR_HW4_SC2"); return e && atoi(e) == 0; }();
-    if (!off) return launch_hwide4_k<256, 64, 4, 0, true, false, 4, 2>(op, st);  // (UPR_HW4_SC2=0: A/B)
+    if (nsc == 1) return launch_hwide4_k<128, 128, 2, true, false, 4, 1>(op, st);
+    return launch_hwide4_k<256, 64, 4, true, false, 4, 2>(op, st);
   }
   if (op.nseg != 1 || op.store != kStoreNHWC) return kErrUnsupported;
   const ConvSeg& s = op.seg[0];
@@ -1711,8 +1681,8 @@ static int halo_route(const ConvOp& op, hipStream_t st) {
   if (s.kh == 3 && s.kw == 3 && s.stride == 1 && s.dil > 1 && s.pad == s.dil && s.dil < 64 && s.pre == kPreNone &&
       s.kbase == 0 && s.C == 256 && s.Hin == op.Ho && s.Win == op.Wo && op.Wo == 64 && op.N % 256 == 0 &&
       (op.Ho * op.Wo) % WBM == 0 && hw4_ds_ok(op)) {
-    if (!op.res1 && !op.res2) return launch_hwide4_k<256, 64, 4, 0, true, true, 4, 0, false, false, true>(op, st);
-    return launch_hwide4_k<256, 64, 4, 0, true, true>(op, st);
+    if (!op.res1 && !op.res2) return launch_hwide4_k<256, 64, 4, true, true, 4, 0, false, false, true>(op, st);
+    return launch_hwide4_k<256, 64, 4, true, true>(op, st);
   }
   if (s.kh != 3 || s.kw != 3 || s.stride != 1 || s.pad != 1 || s.dil != 1 || s.pre != kPreNone) return kErrUnsupported;
   if (s.Hin != op.Ho || s.Win != op.Wo || s.C % WBK || (op.Ho * op.Wo) % WBM) return kErrUnsupported;
@@ -1838,9 +1808,7 @@ int launch_conv_wide(const ConvOp& op, hipStream_t st, bool probe) {
     if (sg.pre != kPreNone || sg.C % WBK || sg.cs % 8 || sg.coff % 8 || sg.kbase % 8) return kErrUnsupported;
     if ((uintptr_t)sg.src % 16) return kErrUnsupported;
   }
-  // UPR_HALO=0: skip the halo-tiled forms (A/B against the gathered kernel, tools/convbench.py)
-  static const bool halo_off = [] { const char* e = getenv("UPR_HALO"); return e && atoi(e) == 0; }();
-  if (!halo_off && !split && !probe) {
+  if (!split && !probe) {
     const int rc = halo_route(op, st);
     if (rc != kErrUnsupported) return rc;
   }

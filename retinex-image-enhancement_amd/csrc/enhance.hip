@@ -594,267 +594,28 @@ __global__ __launch_bounds__(256) void ms_sums_kernel(const T* __restrict__ x, u
   }
 }
 
-// One pass for all three scales (H % 4 == 0, W % 4 == 0: the 0.5 / 0.25
-// bilinear samples are then 2x2 blends of full-resolution pixels, taps at
-// rows / columns 2y, 2y + 1 and 4y + 1, 4y + 2, weights exactly 0.5).  A block
-// owns a 32 x 64 full-resolution tile = a 16 x 32 half and an 8 x 16 quarter
-// tile; it stages the full-resolution region with a 4-pixel halo in LDS
-// (every pixel of the image is read from HBM once, halos from L2), forms the
-// half / quarter samples (+ their 1-sample halos) from LDS with sample_s's
-// arithmetic, and sums the 7 features of all three tiles.  The three block
-// sums are stored to the tile's partial slot and the block ends; ms_fin_kernel
-// adds an image's partials in tile order (fp64, deterministic) and writes the
-// sums and the factor.  (An earlier form ended every block with fixed-point
-// atomics and an arrival counter, the last block finishing the image: the
-// blocks' atomic tails held their LDS and cost more than the extra launch.)
-constexpr int M3_TH = 32, M3_TW = 64, M3_HALO = 4;
-constexpr int M3_RH = M3_TH + 2 * M3_HALO, M3_RW = M3_TW + 2 * M3_HALO;
-constexpr int M3_H1 = M3_TH / 2 + 2, M3_W1 = M3_TW / 2 + 2, M3_H2 = M3_TH / 4 + 2, M3_W2 = M3_TW / 4 + 2;
-// half / quarter sample planes: interior columns from 4 (16-byte aligned
-// quads), the 1-sample halo at columns 3 and 4 + width
-constexpr int M3_P1 = M3_TW / 2 + 8, M3_P2 = M3_TW / 4 + 8;
-
 __device__ __forceinline__ float blend_half(float v00, float v01, float v10, float v11) {
   const float ly = 0.5f, lx = 0.5f;  // sample_s with fy - y0 = fx - x0 = 0.5
   return (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
 }
 
-// the 7 features of pixel (R, C) of an LDS image P (3 planes of PH x PW)
-// whose pixel (R, C) is image pixel (y, x) of an hs x ws scale (torch.gradient:
-// central differences, one-sided at the borders).  The gradient magnitude
-// takes the hardware square root (v_sqrt_f32, <= 1 ulp) instead of the
-// correctly rounded expansion (~15 instructions each, 3 per pixel: that
-// expansion was a third of this pass's VALU work); the sums feed means over
-// >= 10^5 pixels, and the factor stays within 1e-8 of the oracle's (tests
-// hold it to 1e-6).  The feature MAPS (ms_features_kernel) keep sqrtf.
-template <int PH, int PW>
-__device__ __forceinline__ float ms_feat(const float (&P)[3][PH][PW], int R, int C, int y, int x, int hs, int ws) {
-  float c3[3];
-  float fsum = 0.f;
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    const float v = P[ch][R][C];
-    c3[ch] = v;
-    float gx, gy;
-    if (ws < 2) gx = 0.f;
-    else if (x == 0) gx = P[ch][R][C + 1] - v;
-    else if (x == ws - 1) gx = v - P[ch][R][C - 1];
-    else gx = (P[ch][R][C + 1] - P[ch][R][C - 1]) / 2.f;
-    if (hs < 2) gy = 0.f;
-    else if (y == 0) gy = P[ch][R + 1][C] - v;
-    else if (y == hs - 1) gy = v - P[ch][R - 1][C];
-    else gy = (P[ch][R + 1][C] - P[ch][R - 1][C]) / 2.f;
-    fsum += v + __builtin_amdgcn_sqrtf(gx * gx + gy * gy);
-  }
-  fsum += 0.299f * c3[0] + 0.587f * c3[1] + 0.114f * c3[2];
-  return fsum;
-}
-
-// the features of the 4 pixels (R, C .. C + 3) (C 16-byte aligned) of image
-// row y, columns x .. x + 3, summed in fp64 as ms_feat's per-pixel floats
-// (same expression, same order: bit-identical to ms_feat on every pixel).
-// Every lane of the wave calls it (DPP below): lanes whose quad lies outside
-// the hs x ws image contribute 0, as do the pixels of a quad past ws.  A
-// lane's quads sit along a DPP row of 16 lanes: the left / right neighbour
-// columns come from the adjacent lanes' quads (row_shr / row_shl by 1) and
-// only a row's first / last lane (first / last) reads them from LDS -- the
-// stride-4 single-float LDS reads were 4-way bank conflicts on every lane.
-// Image borders: a missing neighbour is replaced by the centre pixel and the
-// difference is not halved (torch.gradient's one-sided edge difference).
-__device__ __forceinline__ float dpp_from_left(float v) {  // lane i <- lane i - 1 within its row of 16
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x111, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float dpp_from_right(float v) {  // lane i <- lane i + 1 within its row of 16
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x101, 0xF, 0xF, false));
-}
-
-// EDGE false: the caller's block holds no image border (block-uniform), so
-// none of the border selects are needed
-template <bool EDGE, int PH, int PW>
-__device__ __forceinline__ double ms_quad(const float (&P)[3][PH][PW], int R, int C, int y, int x, int hs, int ws,
-                                          bool first, bool last) {
-  const bool top = EDGE && y == 0, bot = EDGE && y >= hs - 1;  // (hs < 2: both)
-  const float sy = top || bot ? 1.f : 0.5f;
-  float fs[4] = {0.f, 0.f, 0.f, 0.f}, c3[3][4];
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    const float4 ce = *(const float4*)&P[ch][R][C];
-    float4 up = *(const float4*)&P[ch][R - 1][C];
-    float4 dn = *(const float4*)&P[ch][R + 1][C];
-    float l = dpp_from_left(ce.w), r = dpp_from_right(ce.x);
-    if (first) l = P[ch][R][C - 1];
-    if (last) r = P[ch][R][C + 4];
-    if (top) up = ce;
-    if (bot) dn = ce;
-    const float v[6] = {l, ce.x, ce.y, ce.z, ce.w, r};
-    const float u[4] = {up.x, up.y, up.z, up.w}, d[4] = {dn.x, dn.y, dn.z, dn.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const bool lft = EDGE && x + k == 0, rgt = EDGE && x + k >= ws - 1;
-      const float a = lft ? v[k + 1] : v[k], b = rgt ? v[k + 1] : v[k + 2];
-      const float gx = (b - a) * (lft || rgt ? 1.f : 0.5f);
-      const float gy = (d[k] - u[k]) * sy;
-      fs[k] += v[k + 1] + __builtin_amdgcn_sqrtf(gx * gx + gy * gy);
-      c3[ch][k] = v[k + 1];
-    }
-  }
-  double a = 0.0;
-  if (!EDGE || y < hs) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (!EDGE || x + k < ws) a += (double)(fs[k] + (0.299f * c3[0][k] + 0.587f * c3[1][k] + 0.114f * c3[2][k]));
-  }
-  return a;
-}
-
-// the block's feature quads: 512 of the full tile (2 per thread), 128 half
-// (threads 0-127), 32 quarter (128-159)
-template <bool E>
-__device__ __forceinline__ void ms_tile_quads(const float (&full)[3][M3_RH][M3_RW], const float (&s1)[3][M3_H1][M3_P1],
-                                              const float (&s2)[3][M3_H2][M3_P2], int t, int ty0, int tx0, int H,
-                                              int W, double& a0, double& a1, double& a2) {
-  a0 = 0.0;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int i = t + 256 * k, r = i >> 4, q = i & 15;
-    a0 += ms_quad<E>(full, r + M3_HALO, 4 * q + M3_HALO, ty0 + r, tx0 + 4 * q, H, W, q == 0, q == 15);
-  }
-  // (one value selected afterwards: assigning a1 / a2 inside the branches
-  // became a dynamically indexed scratch pair)
-  double ah = 0.0;
-  if (t < 128) {  // (waves 0, 1: whole)
-    const int r = t >> 3, q = t & 7;
-    ah = ms_quad<E>(s1, r + 1, 4 * q + 4, ty0 / 2 + r, tx0 / 2 + 4 * q, H / 2, W / 2, q == 0, q == 7);
-  } else if (t < 160) {  // (lanes 0-31 of wave 2: two whole DPP rows)
-    const int r = (t - 128) >> 2, q = (t - 128) & 3;
-    ah = ms_quad<E>(s2, r + 1, 4 * q + 4, ty0 / 4 + r, tx0 / 4 + 4 * q, H / 4, W / 4, q == 0, q == 3);
-  }
-  a1 = t < 128 ? ah : 0.0;
-  a2 = t < 128 ? 0.0 : ah;
-}
-
-__device__ __forceinline__ double ms_factor(const double* sums, int b, double n0, double n1, double n2);
-
-template <typename T>
-__global__ __launch_bounds__(256) void ms_sums3_kernel(const T* __restrict__ x, double* __restrict__ part, int H,
-                                                       int W, int tiles_x) {
-  __shared__ float full[3][M3_RH][M3_RW];
-  __shared__ __attribute__((aligned(16))) float s1[3][M3_H1][M3_P1];
-  __shared__ __attribute__((aligned(16))) float s2[3][M3_H2][M3_P2];
-  __shared__ double red[4][3];
-  const int t = threadIdx.x;
-  // tiles in XCD-contiguous order (blocks i, i + 8, ... share an XCD: they take
-  // neighbouring tiles, whose 4-pixel halo lines then come from that XCD's L2;
-  // dealt round-robin, every tile's halos were fetched from HBM twice)
-  const int nb = gridDim.x * gridDim.y, bid = blockIdx.y * gridDim.x + blockIdx.x;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7, k8 = bid >> 3;
-  const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + k8;
-  const int b = tile / gridDim.x, tin = tile - b * gridDim.x;
-  const int ty0 = (tin / tiles_x) * M3_TH, tx0 = (tin % tiles_x) * M3_TW;
-  const size_t HW = (size_t)H * W;
-  const T* img = x + (size_t)b * 3 * HW;
-  // full-resolution region: rows ty0 - 4 .., columns tx0 - 4 .. in 4-pixel quads
-  // every quad's load is issued before the first LDS store (NLD loads in
-  // flight per thread: one HBM round trip per block, not one per quad).  (A
-  // persistent form loading tile j + 1 under tile j's work measured no faster:
-  // 0.074 vs 0.071 ms)
-  // thread (lr, lq) = quad lq of region rows lr + 14 k (k < 3 covers the 40
-  // rows), all three channels: the 9 loads' offsets are compile-time steps
-  // from one base (the per-quad division / modulo of a flat index was a fifth
-  // of this pass's VALU work)
-  constexpr int QPR = M3_RW / 4, LR = 256 / QPR, NK = (M3_RH + LR - 1) / LR;
-  const int lr = t / QPR, lq = t - lr * QPR;
-  const bool lact = t < LR * QPR;
-  const int xs = tx0 - M3_HALO + 4 * lq, ys0 = ty0 - M3_HALO + lr;
-  const bool xok = lact && (unsigned)xs < (unsigned)W;
-  float v[3][NK][4];
-#pragma unroll
-  for (int k = 0; k < NK; ++k) {
-    const int ys = ys0 + LR * k;
-    const bool ok = xok && lr + LR * k < M3_RH && (unsigned)ys < (unsigned)H;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      v[ch][k][0] = v[ch][k][1] = v[ch][k][2] = v[ch][k][3] = 0.f;
-      if (ok) Vec4<T>::load(img + ch * HW + (size_t)ys * W + xs, v[ch][k]);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < NK; ++k) {
-    if (lact && lr + LR * k < M3_RH) {
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch)
-        *(float4*)&full[ch][lr + LR * k][4 * lq] = make_float4(v[ch][k][0], v[ch][k][1], v[ch][k][2], v[ch][k][3]);
-    }
-  }
-  __syncthreads();
-  const int h1 = H / 2, w1 = W / 2, h2 = H / 4, w2 = W / 4;
-  // half / quarter samples with their 1-sample halos (LDS rows of sample r:
-  // 2r + 2, 2r + 3 / 4r + 1, 4r + 2 of the region, by the halo of 4); sample
-  // column c at plane column c + 3.  Half: thread (r0, c) = (t / 34, t % 34)
-  // takes rows r0 + 7 j (j < 3); quarter: threads 238.. and a second pass
-  {
-    constexpr int R1 = 256 / M3_W1;  // 7 half rows per pass
-    const int r0 = t / M3_W1, c = t - r0 * M3_W1;
-    const int xs1 = tx0 / 2 - 1 + c;
-    if (t < R1 * M3_W1 && (unsigned)xs1 < (unsigned)w1) {
-#pragma unroll
-      for (int j = 0; j < (M3_H1 + R1 - 1) / R1; ++j) {
-        const int r = r0 + R1 * j, ys = ty0 / 2 - 1 + r;
-        if (r < M3_H1 && (unsigned)ys < (unsigned)h1) {
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch)
-            s1[ch][r][c + 3] = blend_half(full[ch][2 * r + 2][2 * c + 2], full[ch][2 * r + 2][2 * c + 3],
-                                          full[ch][2 * r + 3][2 * c + 2], full[ch][2 * r + 3][2 * c + 3]);
-        }
-      }
-    }
-    // quarter: 10 x 18 samples over threads 0..179
-    const int r2 = t / M3_W2, c2 = t - r2 * M3_W2;
-    const int ys2 = ty0 / 4 - 1 + r2, xs2 = tx0 / 4 - 1 + c2;
-    if (t < M3_H2 * M3_W2 && (unsigned)ys2 < (unsigned)h2 && (unsigned)xs2 < (unsigned)w2) {
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch)
-        s2[ch][r2][c2 + 3] = blend_half(full[ch][4 * r2 + 1][4 * c2 + 1], full[ch][4 * r2 + 1][4 * c2 + 2],
-                                        full[ch][4 * r2 + 2][4 * c2 + 1], full[ch][4 * r2 + 2][4 * c2 + 2]);
-    }
-  }
-  __syncthreads();
-  double a0, a1, a2;
-  // a tile touching no image border (at any of the three scales: the half /
-  // quarter tiles' borders are the full tile's) takes the select-free form
-  if (ty0 == 0 || tx0 == 0 || ty0 + M3_TH >= H || tx0 + M3_TW >= W)
-    ms_tile_quads<true>(full, s1, s2, t, ty0, tx0, H, W, a0, a1, a2);
-  else
-    ms_tile_quads<false>(full, s1, s2, t, ty0, tx0, H, W, a0, a1, a2);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    a0 += __shfl_xor(a0, o, 64);
-    a1 += __shfl_xor(a1, o, 64);
-    a2 += __shfl_xor(a2, o, 64);
-  }
-  if ((t & 63) == 0) { red[t >> 6][0] = a0; red[t >> 6][1] = a1; red[t >> 6][2] = a2; }
-  __syncthreads();
-  // the block's three sums, plain stores: no atomics or arrival counter to
-  // wait for at the end of every block (ms_fin_kernel adds them in order)
-  if (t < 3) part[((size_t)b * gridDim.x + tin) * 3 + t] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
-}
-
-// Register-streaming form of the one-pass multi-scale sums (round 6): one
-// WAVE owns a strip of 256 full-resolution columns (a 4-pixel quad per lane)
-// of a band of MSR_BH rows and walks the band's rows top to bottom (plus 3
-// halo rows above and below), all three scales from registers -- no LDS, no
-// barriers.  Row j's quads arrive MSR_PF rows ahead of their use; full-row
-// features take the rows above / below from the register window and the
-// left / right neighbour columns from the adjacent lanes (DPP wave_shr:1 /
-// wave_shl:1), lane 0 / 63 from a quad of the neighbouring strip that only they
-// load.  Half samples (rows 2h, 2h + 1, columns 2c, 2c + 1) and quarter samples
-// (rows 4q + 1, 4q + 2, columns 4c + 1, 4c + 2) are blended in registers as rows
-// complete and take their neighbours the same way.  Per pixel the arithmetic
-// is ms_quad's (bit-identical features); the wave's three fp64 sums go to its
-// partial slot, ms_fin_kernel adds an image's slots in order.  (The tiled
-// ms_sums3_kernel staged a 40 x 72 region, its half / quarter planes and ran
-// three barrier-separated phases per block: 44 us for 32 x 512^2.)
-constexpr int MSR_BH = 16, MSR_PF = 2, MSR_NR = MSR_BH + 6;
+// One pass for all three scales (H % 4 == 0, W % 4 == 0: the 0.5 / 0.25
+// bilinear samples are then 2x2 blends of full-resolution pixels, taps at
+// rows / columns 2y, 2y + 1 and 4y + 1, 4y + 2, weights exactly 0.5), register
+// streaming: one WAVE owns one colour plane of a strip of 256 full-resolution
+// columns (a 4-pixel quad per lane) of a band of MSR_BH rows and walks the
+// band's rows top to bottom (plus 3 halo rows above and below), all three
+// scales from registers -- no LDS, no barriers.  Row j's quads arrive MSR_PF
+// rows ahead of their use; full-row features take the rows above / below from
+// the register window and the left / right neighbour columns from the
+// adjacent lanes (DPP wave_shr:1 / wave_shl:1), lane 0 / 63 from a quad of the
+// neighbouring strip that only they load.  Half samples (rows 2h, 2h + 1,
+// columns 2c, 2c + 1) and quarter samples (rows 4q + 1, 4q + 2, columns 4c + 1,
+// 4c + 2) are blended in registers as rows complete and take their neighbours
+// the same way.  The wave's sums go to its partial slot; ms_fin1_kernel adds
+// an image's slots in a fixed order (fp64, deterministic: no atomics or
+// arrival counter at the end of a block).
+constexpr int MSR_BH = 16, MSR_PF = 2;
 
 template <typename F, int... S>
 __device__ __forceinline__ void ms_steps(F&& f, std::integer_sequence<int, S...>) {
@@ -872,243 +633,39 @@ __device__ __forceinline__ float wave_from_right(float v, float edge) {  // lane
   return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x130, 0xF, 0xF, false));
 }
 
-// features of N consecutive pixels of one row (c[ch][k], neighbours l / r of
-// the first / last, rows u / d above / below), ms_quad's expression per pixel
 // a value select (an lvalue ?: between array elements became a pointer phi
 // that kept the arrays in scratch)
 __device__ __forceinline__ float fsel(bool p, float a, float b) { return p ? a : b; }
 
-template <int N>
-__device__ __forceinline__ double ms_row_feat(const float (&c)[3][N], const float (&u)[3][N], const float (&d)[3][N],
-                                              const float (&l)[3], const float (&r)[3], int y, int x, int hs, int ws) {
-  // y is wave-uniform: rows off the image contribute nothing, and only the
-  // image's first / last row takes the one-sided vertical difference (a
-  // uniform branch); horizontally (W % 4 == 0, aligned quads) only a run's
-  // first pixel can sit on column 0 and only its last on column ws - 1, and a
-  // run lies wholly inside or outside the image
-  if (y < 0 || y >= hs) return 0.0;
-  const bool top = y == 0, bot = y >= hs - 1;
-  float fs[N];
-#pragma unroll
-  for (int k = 0; k < N; ++k) fs[k] = 0.f;
-  auto body = [&](auto VB_) {
-    constexpr bool VB = decltype(VB_)::value;  // vertical border row
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      ms_sfor<N>([&](auto K_) {
-        constexpr int k = decltype(K_)::value;
-        float vl, vr;
-        if constexpr (k == 0) vl = l[ch]; else vl = c[ch][k - 1];
-        if constexpr (k == N - 1) vr = r[ch]; else vr = c[ch][k + 1];
-        const float v = c[ch][k];
-        float gx;
-        if constexpr (k == 0 || k == N - 1) {
-          const bool lft = k == 0 && x == 0, rgt = k == N - 1 && x + k >= ws - 1;
-          const float a = fsel(lft, v, vl), b = fsel(rgt, v, vr);
-          gx = (b - a) * fsel(lft || rgt, 1.f, 0.5f);
-        } else {
-          gx = (vr - vl) * 0.5f;
-        }
-        float gy;
-        if constexpr (VB) {
-          const float uu = fsel(top, v, u[ch][k]), dd = fsel(bot, v, d[ch][k]);
-          gy = (dd - uu) * fsel(top || bot, 1.f, 0.5f);
-        } else {
-          gy = (d[ch][k] - u[ch][k]) * 0.5f;
-        }
-        fs[k] += v + __builtin_amdgcn_sqrtf(gx * gx + gy * gy);
-      });
-    }
-  };
-  if (top || bot) body(std::true_type{});
-  else body(std::false_type{});
-  double a = 0.0;
-  if (x < ws) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) a += (double)(fs[k] + (0.299f * c[0][k] + 0.587f * c[1][k] + 0.114f * c[2][k]));
-  }
-  return a;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256, 2) void ms_rows_kernel(const T* __restrict__ x, double* __restrict__ part, int B,
-                                                      int H, int W, int strips, int nwav) {
-  const int lane = threadIdx.x & 63;
-  // waves in XCD-contiguous order over (image, wave): blocks i, i + 8, ... share
-  // an XCD and take neighbouring bands, whose halo rows then hit that L2
-  const int nb = gridDim.x, bid = blockIdx.x;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7, k8 = bid >> 3;
-  const int blk = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + k8;
-  // global wave = image * nwav + wave; readfirstlane: everything derived from
-  // it is wave-uniform (SGPRs), or every buffer load became a waterfall loop
-  const int gw = blk * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int b = gw / nwav, wv = gw - b * nwav;
-  if (b >= B) return;  // (the last block's spare waves)
-  const int band = wv / strips, strip = wv - band * strips;
-  const int y0 = band * MSR_BH, xs = strip * 256, xq = xs + 4 * lane;
-  const int hs1 = H / 2, ws1 = W / 2, hs2 = H / 4, ws2 = W / 4;
-  const size_t HW = (size_t)H * W;
-  const T* img = x + (size_t)b * 3 * HW;
-  const bool qin = xq < W;
-  // the neighbouring strip's quad of the edge lanes: lane 0 cols xs - 4 .. xs - 1, lane 63 xs + 256 .. + 259
-  const int xe = lane == 0 ? xs - 4 : xs + 256;  // (fp32 reads 3 columns from xe + 1 / xe on lane 0 / 63)
-  const bool ein = (lane == 0 || lane == 63) && xe >= 0 && xe < W;
-  // row j of the window = image row y0 - 3 + j; V: the lane's quad, E: the edge quad's
-  // three columns that the neighbours use (lane 0: xs - 3, xs - 2, xs - 1; lane 63: xs + 256 .. + 258)
-  float V[MSR_NR][3][4], E[MSR_NR][3][3];
-  // loads are unconditional, from clamped (always valid) addresses, and zeroed
-  // by a select after the fact: a load under a divergent branch came with a
-  // vmcnt(0) at the branch's merge, serialising every row's loads.  They are
-  // buffer loads: a per-lane 32-bit column offset fixed for the wave + a
-  // wave-uniform row offset (64-bit per-lane addresses for every row of the
-  // unrolled walk took 264 registers)
-  // the buffer's range is the image: a lane whose quad lies off the image (and
-  // every lane but 0 / 63 for the edge load) reads at an offset past it, which
-  // returns zeros without a memory access
-  const int ib = 3 * (int)HW * (int)sizeof(T);
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)img, 0, ib, 0x00020000);
-  constexpr int kOff = 0x40000000;
-  const int vq = qin ? xq * (int)sizeof(T) : kOff;
-  const int ve = ein ? (sizeof(T) == 4 && lane == 0 ? xe + 1 : xe) * (int)sizeof(T) : kOff;
-  auto bld = [&](int voff, int soff, float (&v)[4]) {
-    if constexpr (sizeof(T) == 4) {
-      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-      const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0);
-      v[0] = __uint_as_float(q[0]); v[1] = __uint_as_float(q[1]); v[2] = __uint_as_float(q[2]); v[3] = __uint_as_float(q[3]);
-    } else {
-      typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-      typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-      const u32x2 q = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 0);
-      const h4 hv = __builtin_bit_cast(h4, q);
-      v[0] = (float)hv[0]; v[1] = (float)hv[1]; v[2] = (float)hv[2]; v[3] = (float)hv[3];
-    }
-  };
-  auto load_row = [&](auto J_) {
-    constexpr int j = decltype(J_)::value;
-    const int y = y0 - 3 + j;
-    const bool yin = y >= 0 && y < H;  // (wave-uniform)
-    // rows off the image: every lane's offset out of range (the range check is
-    // on the per-lane offset; the row's soffset stays a valid one)
-    const int ro = yin ? y * W : 0;
-    const int vqr = yin ? vq : kOff, ver = yin ? ve : kOff;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      float v[4];
-      const int so = (ch * (int)HW + ro) * (int)sizeof(T);
-      bld(vqr, so, v);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) V[j][ch][k] = v[k];
-      if constexpr (sizeof(T) == 4) {
-        // the three edge columns straight from one 12-byte load (lane 0: xs - 3 ..; lane 63: xs + 256 ..)
-        typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
-        const u32x3 q = __builtin_amdgcn_raw_buffer_load_b96(rs, ver, so, 0);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) E[j][ch][k] = __uint_as_float(q[k]);
-      } else {
-        float e[4];
-        bld(ver, so, e);
-        const bool l0 = lane == 0;
-        E[j][ch][0] = fsel(l0, e[1], e[0]);
-        E[j][ch][1] = fsel(l0, e[2], e[1]);
-        E[j][ch][2] = fsel(l0, e[3], e[2]);
-      }
-    }
-  };
-  // half samples: sample row k (k = 0 .. MSR_BH / 2 + 1) = half row y0 / 2 - 1 + k from window rows 1 + 2k, 2 + 2k;
-  // quarter sample row k (k = 0 .. MSR_BH / 4 + 1) = quarter row y0 / 4 - 1 + k from window rows 4k, 4k + 1
-  float S1[MSR_BH / 2 + 2][3][2], S1e[MSR_BH / 2 + 2][3];  // the lane's 2 half pixels, the edge lane's neighbour
-  float S2[MSR_BH / 4 + 2][3], S2e[MSR_BH / 4 + 2][3];
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-  ms_sfor<MSR_PF + 1>([&](auto J_) { load_row(J_); });
-  ms_sfor<MSR_NR>([&](auto J_) {
-    constexpr int j = decltype(J_)::value;
-    // (a compiler-only fence per row: without it every row's loads were hoisted
-    // to the top -- 316 registers, one wave per SIMD)
-    asm volatile("" ::: "memory");
-    if constexpr (j + MSR_PF + 1 < MSR_NR) load_row(std::integral_constant<int, j + MSR_PF + 1>{});
-    // full features of window row j - 1 (image rows y0 .. y0 + MSR_BH - 1: j - 1 in 3 .. MSR_BH + 2)
-    if constexpr (j - 1 >= 3 && j - 1 < MSR_BH + 3) {
-      constexpr int m = j - 1;
-      float l[3], r[3];
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        l[ch] = wave_from_left(V[m][ch][3], E[m][ch][2]);
-        r[ch] = wave_from_right(V[m][ch][0], E[m][ch][0]);
-      }
-      a0 += ms_row_feat<4>(V[m], V[m - 1], V[m + 1], l, r, y0 - 3 + m, xq, H, W);
-    }
-    // half sample row k once window row 2 + 2k is in
-    if constexpr (j >= 2 && j % 2 == 0) {
-      constexpr int k = (j - 2) / 2;
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        S1[k][ch][0] = blend_half(V[j - 1][ch][0], V[j - 1][ch][1], V[j][ch][0], V[j][ch][1]);
-        S1[k][ch][1] = blend_half(V[j - 1][ch][2], V[j - 1][ch][3], V[j][ch][2], V[j][ch][3]);
-        const bool l0 = lane == 0;  // (value selects: a ?: of two blend calls became pointer phis into scratch)
-        S1e[k][ch] = blend_half(fsel(l0, E[j - 1][ch][1], E[j - 1][ch][0]), fsel(l0, E[j - 1][ch][2], E[j - 1][ch][1]),
-                                fsel(l0, E[j][ch][1], E[j][ch][0]), fsel(l0, E[j][ch][2], E[j][ch][1]));
-      }
-      // half features of sample row k - 1 (half rows y0 / 2 .. y0 / 2 + MSR_BH / 2 - 1: k - 1 in 1 .. MSR_BH / 2)
-      if constexpr (k - 1 >= 1 && k - 1 <= MSR_BH / 2) {
-        constexpr int m = k - 1;
-        float l[3], r[3];
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-          l[ch] = wave_from_left(S1[m][ch][1], S1e[m][ch]);
-          r[ch] = wave_from_right(S1[m][ch][0], S1e[m][ch]);
-        }
-        a1 += ms_row_feat<2>(S1[m], S1[m - 1], S1[m + 1], l, r, y0 / 2 - 1 + m, xq / 2, hs1, ws1);
-      }
-    }
-    // quarter sample row k once window row 4k + 1 is in
-    if constexpr (j % 4 == 1) {
-      constexpr int k = (j - 1) / 4;
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        S2[k][ch] = blend_half(V[j - 1][ch][1], V[j - 1][ch][2], V[j][ch][1], V[j][ch][2]);
-        const bool l0 = lane == 0;
-        S2e[k][ch] = blend_half(fsel(l0, E[j - 1][ch][0], E[j - 1][ch][1]), fsel(l0, E[j - 1][ch][1], E[j - 1][ch][2]),
-                                fsel(l0, E[j][ch][0], E[j][ch][1]), fsel(l0, E[j][ch][1], E[j][ch][2]));
-      }
-      if constexpr (k - 1 >= 1 && k - 1 <= MSR_BH / 4) {
-        constexpr int m = k - 1;
-        float l[3], r[3], c1[3][1], u1[3][1], d1[3][1];
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-          l[ch] = wave_from_left(S2[m][ch], S2e[m][ch]);
-          r[ch] = wave_from_right(S2[m][ch], S2e[m][ch]);
-          c1[ch][0] = S2[m][ch];
-          u1[ch][0] = S2[m - 1][ch];
-          d1[ch][0] = S2[m + 1][ch];
-        }
-        a2 += ms_row_feat<1>(c1, u1, d1, l, r, y0 / 4 - 1 + m, xq / 4, hs2, ws2);
-      }
-    }
-  });
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    a0 += __shfl_xor(a0, o, 64);
-    a1 += __shfl_xor(a1, o, 64);
-    a2 += __shfl_xor(a2, o, 64);
-  }
-  if (lane < 3) part[((size_t)b * nwav + wv) * 3 + lane] = lane == 0 ? a0 : lane == 1 ? a1 : a2;
-}
-
-// One CHANNEL per wave (round 6, the default): the register-streaming walk of
-// ms_rows_kernel over one colour plane.  SQ counters on ms_rows_kernel
-// (profiles/r6_ms_rows_sq_counters.txt) showed its waves issue-stalled (47% of
-// their cycles waiting on dependent VALU results, 27% issuing) at two waves
-// per SIMD (256 VGPRs: three planes' windows and loads in flight): with one
-// plane a wave needs a third of the registers, and four-plus waves per SIMD
-// hide each other's dependency chains.  The 7 features of a pixel are summed
+// One CHANNEL per wave: a wave walking all three colour planes holds three
+// planes' row windows and loads in flight (256 VGPRs, two waves per SIMD) and
+// is issue-stalled there (47% of its cycles waiting on dependent VALU results,
+// 27% issuing: profiles/r6_ms_rows_sq_counters.txt).  With one plane a wave
+// needs a third of the registers, and four-plus waves per SIMD hide each
+// other's dependency chains.  The 7 features of a pixel are summed
 // as sum over channels of (v + |grad v|) plus the luminance, and the
 // luminance's sum is linear in the planes: 0.299f * sum r + 0.587f * sum g +
 // 0.114f * sum b (the sampled half / quarter planes are linear blends too).
 // So a wave keeps, per scale, the sum of v + |grad v| and the sum of v over
 // its pixels (fp32 over a lane's run of a row, fp64 across rows and lanes),
 // and ms_fin1_kernel combines an image's 3 planes in a fixed order.  The
-// rounding differs from ms_rows_kernel's per-pixel fp32 sum of the 7 terms
-// at the 1e-7 relative level (the sums test holds 1e-6 vs the oracle's maps).
+// rounding differs from a per-pixel fp32 sum of the 7 terms at the 1e-7
+// relative level (the sums test holds 1e-6 vs the oracle's maps).
+//
+// Features of N consecutive pixels of one row of one plane (c[k], neighbours
+// l / r of the first / last, rows u / d above / below); torch.gradient:
+// central differences, one-sided at the image borders (a missing neighbour is
+// replaced by the centre pixel and the difference is not halved).  y is
+// wave-uniform: rows off the image contribute nothing, and only the image's
+// first / last row takes the one-sided vertical difference (a uniform
+// branch); horizontally (W % 4 == 0, aligned quads) only a run's first pixel
+// can sit on column 0 and only its last on column ws - 1, and a run lies
+// wholly inside or outside the image.  The gradient magnitude takes the
+// hardware square root (v_sqrt_f32, <= 1 ulp) instead of the correctly
+// rounded expansion (~15 instructions each, 3 per pixel: a third of the
+// pass's VALU work); the sums feed means over >= 10^5 pixels, and the factor
+// stays within 1e-8 of the oracle's (tests hold it to 1e-6).  The feature
+// MAPS (ms_features_kernel) keep sqrtf.
 template <int N>
 __device__ __forceinline__ void ms_row_feat1(const float (&c)[N], const float (&u)[N], const float (&d)[N], float l,
                                              float r, int y, int x, int hs, int ws, double& af, double& av) {
@@ -1156,10 +713,14 @@ __global__ __launch_bounds__(256, 4) void ms_rows1_kernel(const T* __restrict__ 
   constexpr int NR = BH + 6;
   static_assert(BH % 4 == 0, "bands of whole quarter rows");
   const int lane = threadIdx.x & 63;
+  // waves in XCD-contiguous order: blocks i, i + 8, ... share an XCD and take
+  // neighbouring bands, whose halo rows then hit that L2
   const int nb = gridDim.x, bid = blockIdx.x;
   const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7, k8 = bid >> 3;
   const int blk = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + k8;
-  // global wave = (image * 3 + channel) * nwav + wave (readfirstlane: wave-uniform)
+  // global wave = (image * 3 + channel) * nwav + wave; readfirstlane: everything
+  // derived from it is wave-uniform (SGPRs), or every buffer load became a
+  // waterfall loop
   const int gw = blk * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int bc = gw / nwav, wv = gw - bc * nwav;
   if (bc >= 3 * B) return;  // (the last block's spare waves)
@@ -1169,11 +730,20 @@ __global__ __launch_bounds__(256, 4) void ms_rows1_kernel(const T* __restrict__ 
   const size_t HW = (size_t)H * W;
   const T* plane = x + (size_t)bc * HW;
   const bool qin = xq < W;
-  const int xe = lane == 0 ? xs - 4 : xs + 256;
+  // the neighbouring strip's quad of the edge lanes: lane 0 cols xs - 4 .. xs - 1, lane 63 xs + 256 .. + 259
+  const int xe = lane == 0 ? xs - 4 : xs + 256;  // (fp32 reads 3 columns from xe + 1 / xe on lane 0 / 63)
   const bool ein = (lane == 0 || lane == 63) && xe >= 0 && xe < W;
+  // row j of the window = image row y0 - 3 + j; V: the lane's quad, E: the edge quad's
+  // three columns that the neighbours use (lane 0: xs - 3, xs - 2, xs - 1; lane 63: xs + 256 .. + 258)
   float V[NR][4], E[NR][3];
-  // buffer over the plane: off-image lanes read zeros without a memory access
-  // (ms_rows_kernel's scheme, one plane)
+  // loads are unconditional and zeroed by the buffer's range check: a load
+  // under a divergent branch came with a vmcnt(0) at the branch's merge,
+  // serialising every row's loads.  They are buffer loads: a per-lane 32-bit
+  // column offset fixed for the wave + a wave-uniform row offset (64-bit
+  // per-lane addresses for every row of the unrolled walk cost registers).
+  // The buffer's range is the plane: a lane whose quad lies off the image (and
+  // every lane but 0 / 63 for the edge load) reads at an offset past it, which
+  // returns zeros without a memory access
   const int ib = (int)HW * (int)sizeof(T);
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)plane, 0, ib, 0x00020000);
   constexpr int kOff = 0x40000000;
@@ -1183,6 +753,8 @@ __global__ __launch_bounds__(256, 4) void ms_rows1_kernel(const T* __restrict__ 
     constexpr int j = decltype(J_)::value;
     const int y = y0 - 3 + j;
     const bool yin = y >= 0 && y < H;  // (wave-uniform)
+    // rows off the image: every lane's offset out of range (the range check is
+    // on the per-lane offset; the row's soffset stays a valid one)
     const int so = (yin ? y * W : 0) * (int)sizeof(T);
     const int vqr = yin ? vq : kOff, ver = yin ? ve : kOff;
     if constexpr (sizeof(T) == 4) {
@@ -1207,14 +779,20 @@ __global__ __launch_bounds__(256, 4) void ms_rows1_kernel(const T* __restrict__ 
       E[j][2] = fsel(l0, (float)he[3], (float)he[2]);
     }
   };
+  // half samples: sample row k (k = 0 .. BH / 2 + 1) = half row y0 / 2 - 1 + k from window rows 1 + 2k, 2 + 2k
+  // (the lane's 2 half pixels, the edge lane's neighbour); quarter sample row k (k = 0 .. BH / 4 + 1) =
+  // quarter row y0 / 4 - 1 + k from window rows 4k, 4k + 1
   float S1[BH / 2 + 2][2], S1e[BH / 2 + 2];
   float S2[BH / 4 + 2], S2e[BH / 4 + 2];
   double f0 = 0.0, v0 = 0.0, f1 = 0.0, v1 = 0.0, f2 = 0.0, v2 = 0.0;
   ms_sfor<MSR_PF + 1>([&](auto J_) { load_row(J_); });
   ms_sfor<NR>([&](auto J_) {
     constexpr int j = decltype(J_)::value;
+    // (a compiler-only fence per row: without it every row's loads were hoisted
+    // to the top, at one wave per SIMD)
     asm volatile("" ::: "memory");
     if constexpr (j + MSR_PF + 1 < NR) load_row(std::integral_constant<int, j + MSR_PF + 1>{});
+    // full features of window row j - 1 (image rows y0 .. y0 + BH - 1: j - 1 in 3 .. BH + 2)
     if constexpr (j - 1 >= 3 && j - 1 < BH + 3) {
       constexpr int m = j - 1;
       const float l = wave_from_left(V[m][3], E[m][2]), r = wave_from_right(V[m][0], E[m][0]);
@@ -1308,32 +886,6 @@ __global__ __launch_bounds__(256) void ms_fin1_kernel(const double* __restrict__
       }
       sums[b * 3 + s] = f + l;
     }
-    if (factor) factor[b] = ms_factor(sums, b, n0, n1, n2);
-  }
-}
-
-// per image: the tile partials of ms_sums3_kernel added in a fixed order (one
-// block per image; deterministic fp64), then sums and the factor
-__global__ __launch_bounds__(256) void ms_fin_kernel(const double* __restrict__ part, int nblk, double* __restrict__ sums,
-                                                     double* __restrict__ factor, double n0, double n1, double n2) {
-  __shared__ double red[3][256];
-  const int b = blockIdx.x, t = threadIdx.x;
-  double a[3] = {0.0, 0.0, 0.0};
-  for (int i = t; i < nblk; i += 256)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) a[k] += part[((size_t)b * nblk + i) * 3 + k];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) red[k][t] = a[k];
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) red[k][t] += red[k][t + o];
-    __syncthreads();
-  }
-  if (t == 0) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) sums[b * 3 + k] = red[k][0];
     if (factor) factor[b] = ms_factor(sums, b, n0, n1, n2);
   }
 }
@@ -1532,10 +1084,11 @@ int launch_multiscale(const void* x, const void* enh, void* out, double* sums, d
     fac = (double*)scratch(kSlotTmp, sizeof(double) * B, st);
     if (!fac) return (int)hipErrorOutOfMemory;
   }
-  // UPR_MS_ROWS=0: the tiled single pass (ms_sums3_kernel); 1: the three-plane
-  // register-streaming walk (ms_rows_kernel); default 2: one plane per wave (A/B)
-  static const int rows = [] { const char* e = getenv("UPR_MS_ROWS"); return e ? atoi(e) : 2; }();
-  if (rows == 2 && H % 4 == 0 && W % 4 == 0 && (uintptr_t)x % (dtype == kF16 ? 8 : 16) == 0) {
+  // one register-streaming pass for the three scales where the half / quarter
+  // samples are 2x2 blends (tiled-LDS and three-planes-per-wave forms measured
+  // 44.7 / 40.9 us against its 35.4 for 32 x 512^2, profiles/r6_ms_rows1_ab.txt);
+  // one launch per scale otherwise
+  if (H % 4 == 0 && W % 4 == 0 && (uintptr_t)x % (dtype == kF16 ? 8 : 16) == 0) {
     const int strips = (W + 255) / 256, nwav = strips * ((H + MSR_BH - 1) / MSR_BH);
     double* part = (double*)scratch(kSlotMs, (size_t)B * 3 * nwav * 6 * sizeof(double), st);
     if (!part) return (int)hipErrorOutOfMemory;
@@ -1549,37 +1102,6 @@ int launch_multiscale(const void* x, const void* enh, void* out, double* sums, d
                          W, strips, nwav);
     UPR_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(ms_fin1_kernel, dim3(B), dim3(256), 0, st, (const double*)part, nwav, sums, fac, n0, n1, n2);
-    UPR_CHECK_HIP(hipGetLastError());
-  } else if (rows == 1 && H % 4 == 0 && W % 4 == 0 && (uintptr_t)x % (dtype == kF16 ? 8 : 16) == 0) {
-    const int strips = (W + 255) / 256, nwav = strips * ((H + MSR_BH - 1) / MSR_BH);
-    double* part = (double*)scratch(kSlotMs, (size_t)B * nwav * 3 * sizeof(double), st);
-    if (!part) return (int)hipErrorOutOfMemory;
-    const int nblk = (B * nwav + 3) / 4;
-    if (dtype == kF16)
-      hipLaunchKernelGGL((ms_rows_kernel<half_t>), dim3(nblk), dim3(256), 0, st, (const half_t*)x, part, B, H, W,
-                         strips, nwav);
-    else
-      hipLaunchKernelGGL((ms_rows_kernel<float>), dim3(nblk), dim3(256), 0, st, (const float*)x, part, B, H, W, strips,
-                         nwav);
-    UPR_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ms_fin_kernel, dim3(B), dim3(256), 0, st, (const double*)part, nwav, sums, fac, n0, n1, n2);
-    UPR_CHECK_HIP(hipGetLastError());
-  } else if (H % 4 == 0 && W % 4 == 0 && (uintptr_t)x % (dtype == kF16 ? 8 : 16) == 0) {
-    // single pass (ms_sums3_kernel): per-tile partials in a scratch slot,
-    // added in order by ms_fin_kernel.  (A streamed form -- 64-column strips
-    // walked in 4-row bands through LDS row rings, one band of prefetch --
-    // measured 0.281 ms against this kernel's 0.085: too little in flight per
-    // block, profiles/r5_ms_strip_vs_tiled.txt)
-    const int tx = (W + M3_TW - 1) / M3_TW;
-    const int nblk = tx * ((H + M3_TH - 1) / M3_TH);
-    double* part = (double*)scratch(kSlotMs, (size_t)B * nblk * 3 * sizeof(double), st);
-    if (!part) return (int)hipErrorOutOfMemory;
-    if (dtype == kF16)
-      hipLaunchKernelGGL((ms_sums3_kernel<half_t>), dim3(nblk, B), dim3(256), 0, st, (const half_t*)x, part, H, W, tx);
-    else
-      hipLaunchKernelGGL((ms_sums3_kernel<float>), dim3(nblk, B), dim3(256), 0, st, (const float*)x, part, H, W, tx);
-    UPR_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ms_fin_kernel, dim3(B), dim3(256), 0, st, (const double*)part, nblk, sums, fac, n0, n1, n2);
     UPR_CHECK_HIP(hipGetLastError());
   } else {
     UPR_CHECK_HIP(hipMemsetAsync(sums, 0, sizeof(double) * 3 * B, st));

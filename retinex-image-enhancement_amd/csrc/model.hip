@@ -1195,16 +1195,12 @@ static int run_forward(UprModel* m, const void* x, int B, int H, int W, void* en
     // HBM-bound encoder for bandwidth (fp16 preact+ASPP bs 32: 5.47 ms forking
     // after op 0, 5.37-5.41 before the bottleneck, 5.40-5.43 before enc3, 5.45
     // before enc2, 5.50 before dec3; profiles/r5_ms_fork_ab.txt).  The side ops
-    // need only op 0's outputs, so any fork point is exact.  UPR_MS_FORK=<op
-    // name prefix> overrides ("-": right after op 0)
-    static const std::string fork_at = [] {
-      const char* e = getenv("UPR_MS_FORK");
-      return std::string(e ? e : "ie_net.bottleneck");
-    }();
+    // need only op 0's outputs, so any fork point is exact (a graph without a
+    // bottleneck op forks right after op 0)
+    static const std::string fork_at = "ie_net.bottleneck";
     int fk = 1;
-    if (fork_at != "-")
-      for (int oi = 1; oi < m->side_begin; ++oi)
-        if (m->ops[oi].name.compare(0, fork_at.size(), fork_at) == 0) { fk = oi; break; }
+    for (int oi = 1; oi < m->side_begin; ++oi)
+      if (m->ops[oi].name.compare(0, fork_at.size(), fork_at) == 0) { fk = oi; break; }
     int rc = kOk;
     m->forks.fetch_add(1, std::memory_order_relaxed);
     for (int oi = 0; oi < fk; ++oi)

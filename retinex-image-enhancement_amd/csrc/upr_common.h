@@ -112,8 +112,10 @@ struct ConvOp {
   // input pixel (b, i, j) lands at output pixel (b, 2i, 2j) of a 2H x 2W map,
   // the others are not written (the 1x1 stride-2 conv's input gradient)
   int out_s2;
-  // hwide4 pointwise form (set by its dispatcher, 0 elsewhere): each tile walks
-  // its K chunks starting at chunk mtile % NCH instead of 0
+  // hwide4 pointwise form (its dispatcher sets 1, 0 elsewhere): each tile walks
+  // its K chunks starting at chunk mtile % NCH instead of 0.  Always on where
+  // it is read; the field stays because the kernel without the test of it
+  // allocates 8 more VGPRs in the 4-chunk program (248 -> 256)
   int krot;
   // Split-fp16 form of an fp32 conv (launch_conv_wide only).  A split tensor
   // stores C fp32 channels per pixel as 2C fp16: [hi(C) | lo(C)], hi = (half)v,

@@ -2,8 +2,8 @@
 
 The scalar adjustment factor 1 + 0.1 * sum_i w_i * mean(features_i) is
 computed on the device per image in one pass over the image for all three
-scales (ms_sums3_kernel: fp64 per-tile partials, added in tile order by
-ms_fin_kernel, which writes the factor); the reference syncs three times
+scales (ms_rows1_kernel: fp64 per-wave partials, added in a fixed order by
+ms_fin1_kernel, which writes the factor); the reference syncs three times
 through .item() (:313-314) and means over the whole batch — it only ever runs
 B = 1.
 """

@@ -61,7 +61,7 @@ def main():
     alg = 36.0 * px
     # bytes the passes move (partials negligible); the three-kernel form: lap (x 12 in, 8 out), gauss rows
     # (8 / 8), gauss cols (8 / 8), att (x 12 + lap 8 in, att 4 out), apply (att 4 + enh 12 in, 12 out)
-    fused = os.environ.get("UPR_CA_FUSED", "1") != "0" and (S * S) % 4 == 0
+    fused = (S * S) % 4 == 0
     # fused: saliency (x 12 in, fp64 map 8 out), att (map 8 + x 12 in, att 4 out), apply (att 4 + enh 12 in, 12 out)
     passes = (12 + 8) + (8 + 12 + 4) + (4 + 12 + 12) if fused else \
         (12 + 8) + (8 + 8) + (8 + 8) + (12 + 8 + 4) + (4 + 12 + 12)

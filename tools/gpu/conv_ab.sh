@@ -1,6 +1,6 @@
 # Same-box A/B of conv kernels: conv parity (the -m gpu conv cases, under the B env), then
 # tools/convbench.py on $SHAPES alternating env A ($AENV) and env B ($BENV) $ROUNDS times.
-#   AENV="UPR_HW4_DS=0" BENV="UPR_HW4_DS=1" SHAPES=bneck,bneckr bash tools/gpu/conv_ab.sh
+#   AENV="UPR_RING_SPLIT_LDS=0" BENV="UPR_RING_SPLIT_LDS=2" DTYPE=fp32regs SHAPES=dec2p bash tools/gpu/conv_ab.sh
 # (the round-3 direct-store / dilated / 2-row-tile A/Bs in profiles/r3_*_ab.txt ran this way)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/${CK:-convab}

@@ -1,7 +1,7 @@
 # Same-box A/B of whole forward steps under different env settings, after the forward parity files
 # (run under the B env): fp16 preact+ASPP (configs[2]) and fp32 plain (configs[1]), alternating
 # A / B (/ C) $ROUNDS times, --no-profile (every timed step on the production path).
-#   AENV="UPR_MS_STREAMS=0" BENV="UPR_MS_STREAMS=1" CENV="UPR_MS_PRIO=1" bash tools/gpu/env_ab.sh
+#   AENV="UPR_MS_STREAMS=0" BENV="UPR_MS_STREAMS=1" CENV="UPR_FP32_SPLIT=0" bash tools/gpu/env_ab.sh
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/${CK:-envab}
 mkdir -p $out

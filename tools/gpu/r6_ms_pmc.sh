@@ -1,5 +1,5 @@
 #!/bin/bash
-# ms_rows_kernel SQ counters (one pass) over the enhance leg + the new content-aware shape test
+# multi-scale sums kernel SQ counters (one pass) over the enhance leg + the new content-aware shape test
 set -o pipefail
 mkdir -p gpurun_out/r6
 R=$GRAFT_REPO_ROOT
