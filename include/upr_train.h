@@ -597,6 +597,29 @@ int upr_t_scale_acc(const double* acc, int n, float scale, float* out, void* str
 int upr_t_loss_total(float* terms, float w_exp, float w_col, float w_spa, float w_dec, float w_per, float w_freq,
                      void* stream);
 
+/* ---- paired terms against a ground truth (no reference counterpart) ------- */
+/* The tile of upr_t_loss_paired's kernel (rows, columns). */
+#define UPR_PAIRED_TILE_H 16
+#define UPR_PAIRED_TILE_W 32
+/* Workspace bytes of upr_t_loss_paired (two fp64 partial sums per tile and
+ * plane); 0 for a shape the entry refuses (B, H or W < 1, H * W >= 2^31). */
+size_t upr_t_loss_paired_workspace(int B, int H, int W);
+/* enh, target [B,3,H,W] fp32 NCHW, any H, W >= 1; n = B * 3 * H * W.
+ *   out2[0] = mean sqrt((enh - target)^2 + eps^2)                (Charbonnier)
+ *   out2[1] = 1 - mean SSIM, the SSIM of upr_image_metrics: 11 x 11 box / 121
+ *             over a zero border of 5, C1 = 0.01^2, C2 = 0.03^2, the map at every
+ *             position per channel, the mean over batch, channel and pixels
+ * both always computed, unweighted.  total (nullable): *total += w_rec *
+ * out2[0] + w_ssim * out2[1] (fp32, product by product).  g_enh (nullable):
+ * g_enh += d(w_rec * out2[0] + w_ssim * out2[1]) / d enh -- accumulated, never
+ * overwritten.  Window sums, quotient and both box passes are fp64, the
+ * gradient is rounded to fp32 once before the add; out2 repeats bit for bit
+ * (per-tile fp64 partials added in a fixed order, no floating-point atomics).
+ * Every access is a scalar one: alignment changes nothing.  B == 0: UPR_OK,
+ * nothing touched.  ws: 8-byte aligned, ws_bytes >= the workspace. */
+int upr_t_loss_paired(const float* enh, const float* target, int B, int H, int W, float eps, float w_rec, float w_ssim,
+                      void* ws, size_t ws_bytes, float* out2, float* total, float* g_enh, void* stream);
+
 /* ---- optimiser (torch.nn.utils.clip_grad_norm_ + torch.optim.Adam) ------ */
 /* GradScaler.unscale_ (trainers/train.py:84-86 with use_amp; torch.amp.GradScaler):
  * g[i] *= 1 / *scale over n elements; *found_inf (caller-zeroed) = 1 when any

@@ -1,2 +1,2 @@
-from .dataset import (LowLightDataset, LowLightTestDataset, DeviceLoader, draw_params,  # noqa: F401
-                      get_train_dataloader, get_test_dataloader)
+from .dataset import (LowLightDataset, LowLightTestDataset, PairedLowLightDataset, DeviceLoader,  # noqa: F401
+                      draw_params, get_train_dataloader, get_test_dataloader)

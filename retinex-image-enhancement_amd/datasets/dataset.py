@@ -66,6 +66,21 @@ def _list_images(image_dir):
     return sorted(files)
 
 
+def match_by_stem(files, reference_files, reference_dir):
+    """The ground truth of every NAME.ext of `files`: the file of reference_files
+    with stem NAME (the first in sorted order when several share it), in the
+    order of `files`.  A file without one raises ValueError naming it."""
+    by_stem = {}
+    for f in reference_files:
+        by_stem.setdefault(os.path.splitext(os.path.basename(f))[0], f)
+    stems = [os.path.splitext(os.path.basename(f))[0] for f in files]
+    missing = [f for f, st in zip(files, stems) if st not in by_stem]
+    if missing:
+        raise ValueError(f"no ground truth in '{reference_dir}' for {', '.join(repr(m) for m in missing)} "
+                         f"(matched by file stem)")
+    return [by_stem[st] for st in stems]
+
+
 def decode_u8(path):
     """PIL decode -> uint8 [H,W,3] (the only per-sample work left on the host)."""
     return np.array(Image.open(path).convert('RGB'), dtype=np.uint8)
@@ -113,6 +128,42 @@ class LowLightDataset:
         return uaug.augment(x[None], uaug.pack([p], [idx]), seed=self.seed)[0]
 
 
+class PairedLowLightDataset(LowLightDataset):
+    """Low-light images with their ground truth (an addition: the reference
+    trains without labels).  reference_files[i] is the file of reference_dir
+    whose stem is that of image_files[i] (match_by_stem).  An item is (low,
+    target): both letterboxed the same way, the target given the sample's flips
+    and rot90 and none of its photometric stages."""
+
+    def __init__(self, image_dir, reference_dir, image_size=640, random_crop=True, augment=True,
+                 advanced_augment=True):
+        super().__init__(image_dir, image_size=image_size, random_crop=random_crop, augment=augment,
+                         advanced_augment=advanced_augment)
+        self.reference_dir = reference_dir
+        self.reference_files = match_by_stem(self.image_files, _list_images(reference_dir), reference_dir)
+
+    def __getitem__(self, idx):
+        dev = _default_device(self.device)
+        low, gt = decode_pair(self.image_files[idx], self.reference_files[idx])
+        x, y = self.letterboxed(low, dev), self.letterboxed(gt, dev)
+        p = draw_params(self.augment, self.advanced_augment)
+        return (uaug.augment(x[None], uaug.pack([p], [idx]), seed=self.seed)[0],
+                uaug.augment(y[None], uaug.target_records([p], [idx]), seed=self.seed)[0])
+
+
+def check_pair(low, gt, low_file, gt_file):
+    """A pair whose decoded sizes differ is refused, naming the two files."""
+    if low.shape != gt.shape:
+        raise ValueError(f"'{low_file}' decodes to {low.shape[1]}x{low.shape[0]} and its ground truth '{gt_file}' to "
+                         f"{gt.shape[1]}x{gt.shape[0]}: a pair must have one size")
+
+
+def decode_pair(low_file, gt_file):
+    low, gt = decode_u8(low_file), decode_u8(gt_file)
+    check_pair(low, gt, low_file, gt_file)
+    return low, gt
+
+
 class LowLightTestDataset:
     """Reference dataset.py:186-258: no augmentation; (image [3,H,W] on the device, file name)."""
 
@@ -137,7 +188,12 @@ class LowLightTestDataset:
 
 
 class DeviceLoader:
-    """Batches of a LowLightDataset as [B,3,H,W] float32 device tensors.
+    """Batches of a LowLightDataset as [B,3,H,W] float32 device tensors; of a
+    PairedLowLightDataset as (low, target) pairs of them: both files go through
+    the decode threads and the same letterbox, the target through a second
+    augment call whose records carry the sample's geometry alone
+    (upr.augment.target_records), and the parameter draws are those of the
+    unpaired loader.
 
     min(num_workers, 16) threads decode ahead (0: decode inline); the main
     thread uploads, letterboxes, draws the parameters in sample order and makes
@@ -173,36 +229,56 @@ class DeviceLoader:
             rng.shuffle(order)
         return order
 
-    def _assemble(self, idxs, images, epoch, rng, dev):
-        ds = self.dataset
-        files = [ds.image_files[i] for i in idxs]
-        shapes = [letterbox_shape(im.shape[:2], ds.image_size, auto=True, scaleup=True) for im in images]
-        if any(s != shapes[0] for s in shapes):
-            raise RuntimeError("images of one batch letterbox to different shapes: " +
-                               ", ".join(f"{f} {s}" for f, s in zip(files, shapes)))
-        H, W = shapes[0]
-        x = torch.empty((len(idxs), 3, H, W), dtype=torch.float32, device=dev)
-        params = []
-        for slot, im in enumerate(images):
-            ds.letterboxed(im, dev, out=x[slot])
-            params.append(draw_params(ds.augment, ds.advanced_augment, rng))
-        if H != W and len({p["k"] & 1 for p in params}) > 1:
-            raise RuntimeError("rot90 gives the images of one batch different shapes: " +
-                               ", ".join(f"{f} k={p['k']}" for f, p in zip(files, params)))
-        records = uaug.pack(params, [epoch * len(ds) + i for i in idxs])
-        return uaug.augment(x, records, seed=self.noise_seed)
-
-    def __iter__(self):
-        epoch = self.epoch
-        self.epoch += 1
-        dev = _default_device(self.device if self.device is not None else self.dataset.device)
+    def _plan(self, epoch):
+        """(the epoch's batches of sample indices, the generator of its parameter draws)."""
         order = self._order(epoch)
         bs = self.batch_size
         batches = [order[i:i + bs] for i in range(0, len(order), bs)]
         if self.drop_last and batches and len(batches[-1]) < bs:
             batches.pop()
         rng = random.Random(self.seed * 1000003 + epoch + 500009) if self.seed is not None else random
+        return batches, rng
+
+    def _draw(self, count, rng):
+        """One batch's draws, in sample order."""
+        ds = self.dataset
+        return [draw_params(ds.augment, ds.advanced_augment, rng) for _ in range(count)]
+
+    def _assemble(self, idxs, images, epoch, rng, dev, targets=None):
+        ds = self.dataset
+        files = [ds.image_files[i] for i in idxs]
+        if targets is not None:
+            for i, im, gt in zip(idxs, images, targets):
+                check_pair(im, gt, ds.image_files[i], ds.reference_files[i])
+        shapes = [letterbox_shape(im.shape[:2], ds.image_size, auto=True, scaleup=True) for im in images]
+        if any(s != shapes[0] for s in shapes):
+            raise RuntimeError("images of one batch letterbox to different shapes: " +
+                               ", ".join(f"{f} {s}" for f, s in zip(files, shapes)))
+        H, W = shapes[0]
+        x = torch.empty((len(idxs), 3, H, W), dtype=torch.float32, device=dev)
+        for slot, im in enumerate(images):
+            ds.letterboxed(im, dev, out=x[slot])
+        params = self._draw(len(images), rng)
+        if H != W and len({p["k"] & 1 for p in params}) > 1:
+            raise RuntimeError("rot90 gives the images of one batch different shapes: " +
+                               ", ".join(f"{f} k={p['k']}" for f, p in zip(files, params)))
+        ids = [epoch * len(ds) + i for i in idxs]
+        low = uaug.augment(x, uaug.pack(params, ids), seed=self.noise_seed)
+        if targets is None:
+            return low
+        y = torch.empty_like(x)
+        for slot, gt in enumerate(targets):
+            ds.letterboxed(gt, dev, out=y[slot])
+        return low, uaug.augment(y, uaug.target_records(params, ids), seed=self.noise_seed)
+
+    def __iter__(self):
+        epoch = self.epoch
+        self.epoch += 1
+        dev = _default_device(self.device if self.device is not None else self.dataset.device)
+        batches, rng = self._plan(epoch)
         files = self.dataset.image_files
+        # a paired dataset: the ground truth of a batch is decoded behind its low-light files, by the same threads
+        gts = getattr(self.dataset, "reference_files", None)
         pool = ThreadPoolExecutor(max_workers=self.num_workers) if self.num_workers else None
         try:
             todo, decoding, ready = iter(batches), deque(), deque()
@@ -212,15 +288,18 @@ class DeviceLoader:
                     idxs = next(todo, None)
                     if idxs is None:
                         return
-                    decoding.append((idxs, [pool.submit(decode_u8, files[i]) for i in idxs] if pool else None))
+                    paths = [files[i] for i in idxs] + ([gts[i] for i in idxs] if gts is not None else [])
+                    decoding.append((idxs, [pool.submit(decode_u8, f) for f in paths] if pool else None, paths))
 
             decode_ahead()
             while decoding or ready:
                 while decoding and len(ready) < 2:
-                    idxs, futs = decoding.popleft()
+                    idxs, futs, paths = decoding.popleft()
                     decode_ahead()
-                    images = [f.result() for f in futs] if futs else [decode_u8(files[i]) for i in idxs]
-                    ready.append(self._assemble(idxs, images, epoch, rng, dev))
+                    images = [f.result() for f in futs] if futs else [decode_u8(f) for f in paths]
+                    n = len(idxs)
+                    ready.append(self._assemble(idxs, images[:n], epoch, rng, dev, images[n:] if gts is not None
+                                                else None))
                 yield ready.popleft()
         finally:
             if pool is not None:
@@ -228,10 +307,15 @@ class DeviceLoader:
 
 
 def get_train_dataloader(image_dir, batch_size=8, image_size=640, num_workers=4, shuffle=True,
-                         advanced_augment=False, drop_last=False, *, device=None, seed=None):
-    """Reference dataset.py:261-300 (augment=True always), plus device= and seed=."""
-    dataset = LowLightDataset(image_dir=image_dir, image_size=image_size, random_crop=True, augment=True,
-                              advanced_augment=advanced_augment)
+                         advanced_augment=False, drop_last=False, *, device=None, seed=None, reference_dir=None):
+    """Reference dataset.py:261-300 (augment=True always), plus device= and seed=;
+    reference_dir= makes it a paired loader of (low, target) batches."""
+    if reference_dir is not None:
+        dataset = PairedLowLightDataset(image_dir, reference_dir, image_size=image_size, random_crop=True,
+                                        augment=True, advanced_augment=advanced_augment)
+    else:
+        dataset = LowLightDataset(image_dir=image_dir, image_size=image_size, random_crop=True, augment=True,
+                                  advanced_augment=advanced_augment)
     dataset.device = device
     if seed is not None:
         dataset.seed = int(seed)

@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from upr import loss_engine as E
-from upr.autograd import loss_forward
+from upr.autograd import loss_forward, paired_forward
 
 _VGG_SEED = 1234
 
@@ -206,13 +206,49 @@ class FrequencyLoss(_Term):
         return self._eval(img_low, img_enhanced, _dummy_illu(img_enhanced), img_enhanced)
 
 
+class _PairedTerm(nn.Module):
+    """One paired term against a ground truth as its own differentiable module
+    (an addition: the reference trains without labels).  Any H, W >= 1; the
+    gradient goes to img_enhanced only (a target that requires grad is refused)."""
+
+    _index = None
+    eps = E.REC_EPS
+
+    def forward(self, img_enhanced, target):
+        _require(img_enhanced, "img_enhanced")
+        _require(target, "target")
+        return paired_forward(img_enhanced.contiguous(), target.contiguous(), self._index, float(self.eps))
+
+
+class ReconstructionLoss(_PairedTerm):
+    """Charbonnier: mean sqrt((img_enhanced - target)^2 + eps^2)."""
+
+    _index = 0
+
+    def __init__(self, eps=1e-3):
+        super().__init__()
+        self.eps = eps
+
+
+class SSIMLoss(_PairedTerm):
+    """1 - mean SSIM, the SSIM of utils.utils.calculate_ssim (11 x 11 box window
+    over a zero border, per channel, every position)."""
+
+    _index = 1
+
+
 class TotalLoss(_EngineHolder):
-    """TotalLoss (reference :586-753)."""
+    """TotalLoss (reference :586-753).  Additions: weight_rec / weight_ssim /
+    rec_eps and criterion(..., target=): with a ground truth the Charbonnier and
+    1 - SSIM terms against it join the total under those two weights (outside
+    DWA) and the loss_dict as 'reconstruction' and 'ssim_loss'."""
 
     def __init__(self, weight_exp=10.0, weight_smooth=1.0, weight_col=0.5, weight_spa=1.0, weight_decouple=0.1,
                  weight_perceptual=1.0, weight_freq=0.5, use_freq_loss=True, adaptive_weights=False,
-                 use_dynamic_smooth_weight=True, texture_method='tv', vgg_weights=None, vgg_seed=_VGG_SEED):
+                 use_dynamic_smooth_weight=True, texture_method='tv', vgg_weights=None, vgg_seed=_VGG_SEED,
+                 weight_rec=0.0, weight_ssim=0.0, rec_eps=1e-3):
         super().__init__()
+        self.weight_rec, self.weight_ssim, self.rec_eps = float(weight_rec), float(weight_ssim), float(rec_eps)
         if texture_method not in E.TEXTURE:
             raise ValueError(f"不支持的纹理复杂度计算方法: {texture_method}")
         self.features = _features(vgg_weights, vgg_seed)
@@ -227,10 +263,20 @@ class TotalLoss(_EngineHolder):
         if adaptive_weights:
             self.loss_history = {k: [] for k in _DWA_KEYS}
 
+    def __call__(self, *args, target=None, **kwargs):
+        """criterion(img_low, img_enhanced, illu_map, reflectance=None, epoch=0, target=None).  forward keeps
+        the reference's five parameters; a ground truth is a keyword of the call and takes the paired path."""
+        if target is None:
+            return super().__call__(*args, **kwargs)
+        return self._forward(*args, target=target, **kwargs)
+
     def forward(self, img_low, img_enhanced, illu_map, reflectance=None, epoch=0):
+        return self._forward(img_low, img_enhanced, illu_map, reflectance, epoch)
+
+    def _forward(self, img_low, img_enhanced, illu_map, reflectance=None, epoch=0, target=None):
         no_refl = reflectance is None
         for t, n in ((img_low, "img_low"), (img_enhanced, "img_enhanced"), (illu_map, "illu_map"),
-                     (reflectance, "reflectance")):
+                     (reflectance, "reflectance"), (target, "target")):
             if t is not None:
                 _require(t, n)
         if no_refl:
@@ -245,7 +291,9 @@ class TotalLoss(_EngineHolder):
         if no_refl:
             eng.w["decouple"] = 0.0
         eng.zero_decouple = no_refl
-        total, terms = loss_forward(eng, img_low.contiguous(), img_enhanced, illu_map, reflectance)
+        eng.w_rec, eng.w_ssim, eng.rec_eps = self.weight_rec, self.weight_ssim, self.rec_eps
+        total, terms = loss_forward(eng, img_low.contiguous(), img_enhanced, illu_map, reflectance,
+                                    target=None if target is None else target.contiguous())
         d = E.terms_dict(terms, lazy=_defer_readback() and not self.adaptive_weights)
         if self.adaptive_weights:
             for k in _DWA_KEYS:

@@ -39,6 +39,11 @@ TotalLoss forward only, the metrics and LOE; --val_reference_dir adds psnr /
 ssim / mse), appends val_* columns to results.csv, lets --best_by choose what
 picks best_model.pth, and writes --val_samples comparison panels under
 <save_dir>/samples/.
+--train_reference_dir DIR (an addition, --mode train) trains on pairs: the ground
+truth of every --train_dir file is the file of DIR with its stem, and the
+Charbonnier and 1 - SSIM terms against it join the loss under --weight_rec /
+--weight_ssim (default 1.0 each; --rec_eps 1e-3) and results.csv as the columns
+reconstruction and ssim_loss.
 """
 import argparse
 import os
@@ -162,6 +167,14 @@ def build_parser():
     p.add_argument('--val_samples', type=_non_negative, default=4,
                    help='--val_dir: [input | enhanced | illumination] panels of the first K validation images under '
                         '<save_dir>/samples/epoch_NNNN/ on validated --save_freq epochs and the last (0: none)')
+    p.add_argument('--train_reference_dir', type=str, default=None,
+                   help='--mode train: ground truth of --train_dir matched by file stem; training adds the paired '
+                        'terms reconstruction (Charbonnier) and ssim_loss (1 - SSIM) against it')
+    p.add_argument('--weight_rec', type=float, default=None,
+                   help='--train_reference_dir: weight of the reconstruction term (default 1.0)')
+    p.add_argument('--weight_ssim', type=float, default=None,
+                   help='--train_reference_dir: weight of the ssim_loss term (default 1.0)')
+    p.add_argument('--rec_eps', type=float, default=1e-3, help='--train_reference_dir: the Charbonnier eps')
     return p
 
 
@@ -174,6 +187,13 @@ def parse_args(argv=None):
         parser.error(f"--best_by {args.best_by} needs --val_dir")
     if args.best_by == 'val_psnr' and not args.val_reference_dir:
         parser.error("--best_by val_psnr needs --val_reference_dir")
+    if args.train_reference_dir is None:
+        for flag, v in (('--weight_rec', args.weight_rec), ('--weight_ssim', args.weight_ssim)):
+            if v is not None:
+                parser.error(f"{flag} needs --train_reference_dir")
+    else:
+        args.weight_rec = 1.0 if args.weight_rec is None else args.weight_rec
+        args.weight_ssim = 1.0 if args.weight_ssim is None else args.weight_ssim
     if args.val_reference_dir and not args.val_dir:
         parser.error("--val_reference_dir needs --val_dir")
     return args

@@ -49,10 +49,11 @@ def make_optimizer(model, lr=1e-4, weight_decay=1e-5):
 
 
 def train_step(model, img_low, criterion, optimizer, max_norm=1.0, scaler=None, use_amp=False, grad_hook=None,
-               amp_fp16=True):
+               amp_fp16=True, target=None):
     """One step body (train.py:63-103).  Returns (loss, loss_dict).  grad_hook
     (e.g. upr.dist.allreduce_grads for data parallelism) runs between the
-    backward and the unscale / clip."""
+    backward and the unscale / clip.  target (an addition): the batch's ground
+    truth, handed to the criterion (TotalLoss's paired terms)."""
     optimizer.zero_grad()
     scaler = _as_upr_scaler(scaler) if use_amp else None
     # the loss_dict's floats are read back after the backward / optimizer work is
@@ -60,7 +61,10 @@ def train_step(model, img_low, criterion, optimizer, max_norm=1.0, scaler=None, 
     with torch.autocast("cuda", dtype=torch.float16, enabled=scaler is not None and amp_fp16), \
             deferred_readback():
         img_enhanced, reflectance, illu_map = model(img_low)
-        loss, loss_dict = criterion(img_low, img_enhanced, illu_map, reflectance)
+        if target is None:
+            loss, loss_dict = criterion(img_low, img_enhanced, illu_map, reflectance)
+        else:
+            loss, loss_dict = criterion(img_low, img_enhanced, illu_map, reflectance, target=target)
     if scaler is not None:
         scaler.scale(loss).backward()
         if grad_hook is not None:
@@ -79,16 +83,21 @@ def train_step(model, img_low, criterion, optimizer, max_norm=1.0, scaler=None, 
 
 
 def train_one_epoch(model, dataloader, criterion, optimizer, device, epoch, writer=None, scaler=None, use_amp=False):
+    """A batch of the loader is a low-light tensor, or a (low, target) pair of a
+    paired loader: the averages then carry PAIRED_KEYS too."""
     model.train()
     keys = ('total', 'exposure', 'smoothness', 'color', 'spatial', 'decouple', 'perceptual')
     totals = {k: 0.0 for k in keys}
     n = 0
     t0 = time.time()
-    for batch_idx, img_low in enumerate(dataloader):
+    for batch_idx, batch in enumerate(dataloader):
+        img_low, target = batch if isinstance(batch, (tuple, list)) else (batch, None)
         img_low = img_low.to(device, torch.float32)
-        _, loss_dict = train_step(model, img_low, criterion, optimizer, scaler=scaler, use_amp=use_amp)
-        for k in keys:
-            totals[k] += loss_dict[k]
+        if target is not None:
+            target = target.to(device, torch.float32)
+        _, loss_dict = train_step(model, img_low, criterion, optimizer, scaler=scaler, use_amp=use_amp, target=target)
+        for k in keys + (PAIRED_KEYS if target is not None else ()):
+            totals[k] = totals.get(k, 0.0) + loss_dict[k]
         n += 1
         if writer is not None and batch_idx % 100 == 0:
             for k, v in loss_dict.items():
@@ -101,6 +110,8 @@ def train_one_epoch(model, dataloader, criterion, optimizer, device, epoch, writ
 
 # ---- the epoch driver (reference trainers/train.py:134-396, :520-600) --------
 LOSS_KEYS = ('total', 'exposure', 'smoothness', 'color', 'spatial', 'decouple', 'perceptual')
+# the columns a paired run (--train_reference_dir) adds after them
+PAIRED_KEYS = ('reconstruction', 'ssim_loss')
 
 
 class StepLR:
@@ -246,7 +257,8 @@ def save_results_to_csv(loss_history, save_dir, val_history=None):
 
 # ---- validation on held-out images (an addition: the reference's README names --val_data_path,
 # its parser has no such flag) ----------------------------------------------------------------
-BEST_BY = ('train_total', 'val_total', 'val_psnr', 'val_loe')
+BEST_BY = ('train_total', 'val_total', 'val_psnr', 'val_ssim', 'val_loe')
+BEST_BY_PAIRED = ('val_psnr', 'val_ssim')  # need the ground truth; higher is better
 
 
 def val_columns(paired):
@@ -257,24 +269,36 @@ def val_columns(paired):
 
 
 def check_best_by(best_by, has_val, has_reference):
-    """The rules of --best_by: a val_* choice needs --val_dir, val_psnr also --val_reference_dir."""
+    """The rules of --best_by: a val_* choice needs --val_dir, val_psnr and val_ssim also --val_reference_dir."""
     if best_by not in BEST_BY:
         raise ValueError(f"best_by must be one of {BEST_BY}, got {best_by!r}")
     if best_by.startswith('val_') and not has_val:
         raise ValueError(f"--best_by {best_by} needs --val_dir")
-    if best_by == 'val_psnr' and not has_reference:
-        raise ValueError("--best_by val_psnr needs --val_reference_dir")
+    if best_by in BEST_BY_PAIRED and not has_reference:
+        raise ValueError(f"--best_by {best_by} needs --val_reference_dir")
+
+
+def paired_weights(train_reference_dir, weight_rec=None, weight_ssim=None):
+    """The rules of --weight_rec / --weight_ssim -> (weight_rec, weight_ssim): both
+    default to 1.0 with --train_reference_dir; without it they are unused (0, 0)
+    and an explicit value is an error."""
+    if train_reference_dir is None:
+        given = [n for n, v in (('--weight_rec', weight_rec), ('--weight_ssim', weight_ssim)) if v is not None]
+        if given:
+            raise ValueError(f"{' and '.join(given)} need{'s' if len(given) == 1 else ''} --train_reference_dir")
+        return 0.0, 0.0
+    return (1.0 if weight_rec is None else float(weight_rec)), (1.0 if weight_ssim is None else float(weight_ssim))
 
 
 class BestTracker:
     """Which epoch is the best so far and how long since (best_model.pth, --patience).
     update(train_total, val) -> True (a new best), False (no improvement: the
     patience counter advanced) or None (a val_* choice on an epoch that was not
-    validated: neither).  val_psnr is better when higher, the others when lower."""
+    validated: neither).  val_psnr and val_ssim are better when higher, the others when lower."""
 
     def __init__(self, best_by='train_total'):
         self.best_by = best_by
-        self.higher = best_by == 'val_psnr'
+        self.higher = best_by in BEST_BY_PAIRED
         self.best = -float('inf') if self.higher else float('inf')
         self.counter = 0
 
@@ -297,7 +321,7 @@ def make_val_loaders(val_dir, reference_dir=None, image_size=640, batch_size=8, 
     without augmentation (every image letterboxed to image_size), in file order,
     the short last batch kept.  The ground truth of NAME.ext is the file of
     reference_dir with stem NAME, loaded the same way."""
-    from datasets.dataset import DeviceLoader, LowLightDataset
+    from datasets.dataset import DeviceLoader, LowLightDataset, match_by_stem
 
     def loader(ds):
         ds.device = device
@@ -309,15 +333,7 @@ def make_val_loaders(val_dir, reference_dir=None, image_size=640, batch_size=8, 
     if reference_dir is None:
         return loader(ds), None
     ref = LowLightDataset(reference_dir, image_size=image_size, augment=False, advanced_augment=False)
-    by_stem = {}
-    for f in ref.image_files:
-        by_stem.setdefault(os.path.splitext(os.path.basename(f))[0], f)
-    stems = [os.path.splitext(os.path.basename(f))[0] for f in ds.image_files]
-    missing = [f for f, st in zip(ds.image_files, stems) if st not in by_stem]
-    if missing:
-        raise ValueError(f"no ground truth in '{reference_dir}' for {', '.join(repr(m) for m in missing)} "
-                         f"(matched by file stem)")
-    ref.image_files = [by_stem[st] for st in stems]
+    ref.image_files = match_by_stem(ds.image_files, ref.image_files, reference_dir)
     return loader(ds), loader(ref)
 
 
@@ -424,14 +440,20 @@ def train(args):
     model = MultiScaleUP_Retinex(use_preact=use_preact, use_aspp=use_aspp).to(device)
     print(f"Number of parameters: {sum(p.numel() for p in model.parameters() if p.requires_grad):,}")
     use_freq_loss, adaptive_weights = getattr(args, 'use_freq_loss', False), getattr(args, 'adaptive_weights', False)
+    train_ref_dir = getattr(args, 'train_reference_dir', None)
+    weight_rec, weight_ssim = paired_weights(train_ref_dir, getattr(args, 'weight_rec', None),
+                                             getattr(args, 'weight_ssim', None))
     criterion = TotalLoss(weight_exp=getattr(args, 'weight_exp', 10.0), weight_smooth=getattr(args, 'weight_smooth', 1.0),
                           weight_col=getattr(args, 'weight_col', 0.5), weight_spa=getattr(args, 'weight_spa', 1.0),
                           weight_decouple=getattr(args, 'weight_decouple', 0.1),
                           weight_perceptual=getattr(args, 'weight_perceptual', 1.0),
                           weight_freq=getattr(args, 'weight_freq', 0.5), use_freq_loss=use_freq_loss,
-                          adaptive_weights=adaptive_weights).to(device)
+                          adaptive_weights=adaptive_weights, weight_rec=weight_rec, weight_ssim=weight_ssim,
+                          rec_eps=getattr(args, 'rec_eps', 1e-3)).to(device)
     print(f"Loss: frequency term {'on' if use_freq_loss else 'off'}, adaptive weights "
-          f"{'on' if adaptive_weights else 'off'}")
+          f"{'on' if adaptive_weights else 'off'}" +
+          (f", paired terms against '{train_ref_dir}': reconstruction x {weight_rec:g}, ssim_loss x {weight_ssim:g}"
+           if train_ref_dir is not None else ""))
     optimizer = make_optimizer(model, lr=args.lr, weight_decay=args.weight_decay)
     use_amp = bool(getattr(args, 'use_amp', False))
     scaler = GradScaler() if use_amp else None
@@ -450,7 +472,8 @@ def train(args):
     advanced_augment = getattr(args, 'advanced_augment', False)
     train_loader = get_train_dataloader(image_dir=args.train_dir, batch_size=args.batch_size,
                                         image_size=args.image_size, num_workers=args.num_workers, shuffle=True,
-                                        advanced_augment=advanced_augment, device=device, seed=seed)
+                                        advanced_augment=advanced_augment, device=device, seed=seed,
+                                        reference_dir=train_ref_dir)
     print(f"Number of training batches: {len(train_loader)}")
     if len(train_loader) == 0:
         print(f"No training batches: {len(train_loader.dataset)} samples, batch_size={args.batch_size}")
@@ -488,7 +511,8 @@ def train(args):
         return val
 
     writer = _summary_writer(os.path.join(args.save_dir, 'logs', datetime.now().strftime('%Y%m%d_%H%M%S')))
-    loss_history = {k: [] for k in LOSS_KEYS}
+    loss_keys = LOSS_KEYS + (PAIRED_KEYS if train_ref_dir is not None else ())
+    loss_history = {k: [] for k in loss_keys}
     tracker = BestTracker(best_by)
     for epoch in range(start_epoch, args.num_epochs):
         train_loader.set_epoch(epoch)
@@ -496,13 +520,13 @@ def train(args):
                               use_amp=use_amp)
         scheduler.step()
         current_lr = optimizer.param_groups[0]['lr']
-        for k in LOSS_KEYS:
+        for k in loss_keys:
             loss_history[k].append(float(avg[k]))
         print(f"\nEpoch {epoch}: {avg['_epoch_seconds']:.2f}s, lr {current_lr:.6g}, " +
-              ", ".join(f"{k} {loss_history[k][-1]:.6f}" for k in LOSS_KEYS))
+              ", ".join(f"{k} {loss_history[k][-1]:.6f}" for k in loss_keys))
         if writer is not None:
             writer.add_scalar('Learning_Rate', current_lr, epoch)
-            for k in LOSS_KEYS:
+            for k in loss_keys:
                 writer.add_scalar(f'Epoch_Loss/{k}', loss_history[k][-1], epoch)
         val, sampled = None, False
         if val_loader is not None:

@@ -213,6 +213,9 @@ UPR_AUG_NOISE = 128
 UPR_AUG_SATURATION = 256
 UPR_AUG_SHIFT = 512
 
+# include/upr_train.h UPR_PAIRED_TILE_H / _W: the tile of upr_t_loss_paired's kernel
+UPR_PAIRED_TILE = (16, 32)
+
 # include/upr_train.h UPR_T_STORE_*: bits of upr_t_conv_mfma / upr_t_conv_mfma16's `store`
 UPR_T_STORE_CONVT2X2 = 1
 UPR_T_STORE_KEEP16 = 2
@@ -322,6 +325,8 @@ SIGNATURES.update({
     "upr_t_add_real": (_i, [_p, _p, c_size_t, _f, _p]),
     "upr_t_scale_acc": (_i, [_p, _i, _f, _p, _p]),
     "upr_t_loss_total": (_i, [_p, _f, _f, _f, _f, _f, _f, _p]),
+    "upr_t_loss_paired_workspace": (c_size_t, [_i, _i, _i]),
+    "upr_t_loss_paired": (_i, [_p, _p, _i, _i, _i, _f, _f, _f, _p, c_size_t, _p, _p, _p, _p]),
     "upr_t_sqsum": (_i, [_p, c_size_t, _p, _p]),
     "upr_t_unscale": (_i, [_p, c_size_t, _p, _p, _p]),
     "upr_t_adam": (_i, [_p, _p, _p, _p, c_size_t, _p, _f, _f, _d, _d, _f, _f, _i, _p, _p]),

@@ -49,6 +49,13 @@ def pack(params, sample_ids, pin=True):
     return host
 
 
+def target_records(params, sample_ids, pin=True):
+    """The records of a batch's ground truth: each sample's flips and rot90, no
+    photometric stage (only the low-light input is degraded further)."""
+    return pack([{"hflip": p.get("hflip"), "vflip": p.get("vflip"), "k": p.get("k", 0)} for p in params],
+                sample_ids, pin=pin)
+
+
 def out_shape(flags, H, W):
     return (W, H) if (flags >> L.UPR_AUG_ROT_SHIFT) & 1 else (H, W)
 

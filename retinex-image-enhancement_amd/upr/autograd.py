@@ -181,8 +181,8 @@ def ienet_train_forward(module, x):
 
 class _LossStep(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, low, enh, illu, refl, engine):
-        terms, grads = engine(low, enh, illu, refl, grads=True)
+    def forward(ctx, low, enh, illu, refl, engine, target=None):
+        terms, grads = engine(low, enh, illu, refl, grads=True, target=target)
         ctx.grads = grads
         total = _scalar_of(terms, 7)
         ctx.mark_non_differentiable(terms)
@@ -198,7 +198,39 @@ class _LossStep(torch.autograd.Function):
                                      ctypes.c_uint64(0), _stream()), "scale_grad")
             outs.append(t)
         g_enh, g_illu, g_refl = outs
-        return None, g_enh, g_illu, g_refl, None
+        return None, g_enh, g_illu, g_refl, None, None
+
+
+class _PairedStep(torch.autograd.Function):
+    """One paired term alone (losses.loss.ReconstructionLoss / SSIMLoss):
+    upr_t_loss_paired with weight 1 on the term; its gradient w.r.t. enh is
+    produced with the forward and scaled by the incoming gradient in backward."""
+
+    @staticmethod
+    def forward(ctx, enh, target, index, eps):
+        from .loss_engine import paired_terms
+        g = torch.empty_like(enh)
+        zero(g)
+        out2 = paired_terms(enh, target, eps, 1.0 - index, float(index), g_enh=g)
+        ctx.g = g
+        return _scalar_of(out2, index)
+
+    @staticmethod
+    def backward(ctx, go):
+        t = ctx.g
+        _chk(L.lib().upr_t_pointwise(_p(t), _p(go.contiguous().to(torch.float32)), _p(t), t.numel(), 5, None, None,
+                                     ctypes.c_float(0), ctypes.c_uint64(0), _stream()), "scale_grad")
+        return t, None, None, None
+
+
+def paired_forward(enh, target, index, eps):
+    """PAIRED_TERMS[index] of (enh, target) as a 0-dim device tensor, differentiable w.r.t. enh only."""
+    from .loss_engine import paired_terms
+    if torch.is_grad_enabled() and target.requires_grad:
+        raise NotImplementedError("UP-Retinex losses: no gradient w.r.t. the target; pass target.detach()")
+    if torch.is_grad_enabled() and enh.requires_grad:
+        return _PairedStep.apply(enh, target, index, eps)
+    return _scalar_of(paired_terms(enh, target, eps), index)
 
 
 def _scalar_of(terms, i):
@@ -210,8 +242,9 @@ def _scalar_of(terms, i):
     return out
 
 
-def loss_forward(engine, low, enh, illu, refl):
-    """TotalLoss.forward on the HIP engine -> (total 0-dim tensor, device terms[9]).
+def loss_forward(engine, low, enh, illu, refl, target=None):
+    """TotalLoss.forward on the HIP engine -> (total 0-dim tensor, device terms[9];
+    terms[11] with a target: the paired terms after the dynamic smooth weight).
     With autograd recording (training), total carries the loss backward.
 
     The engine produces the gradients w.r.t. (enh, illu, refl) only: the
@@ -222,7 +255,10 @@ def loss_forward(engine, low, enh, illu, refl):
         raise NotImplementedError("UP-Retinex losses: no gradient w.r.t. img_low (the HIP loss engine "
                                   "differentiates w.r.t. enhanced / illumination / reflectance); pass "
                                   "img_low.detach() or run under torch.no_grad()")
+    if torch.is_grad_enabled() and target is not None and target.requires_grad:
+        raise NotImplementedError("UP-Retinex losses: no gradient w.r.t. the target (the paired terms "
+                                  "differentiate w.r.t. enhanced only); pass target.detach()")
     if torch.is_grad_enabled() and (enh.requires_grad or illu.requires_grad or refl.requires_grad):
-        return _LossStep.apply(low, enh, illu, refl, engine)
-    terms, _ = engine(low, enh, illu, refl, grads=False)
+        return _LossStep.apply(low, enh, illu, refl, engine, target)
+    terms, _ = engine(low, enh, illu, refl, grads=False, target=target)
     return _scalar_of(terms, 7), terms

@@ -31,6 +31,10 @@ PARAMS = dict(patch=16, base_exposure=0.6, smooth_lambda=10.0, smooth_alpha=1.0,
               freq_high=1.0, freq_low=0.5, dynamic_smooth=True)
 TEXTURE = {"tv": 0, "edge_density": 1}  # calculate_texture_complexity methods (loss.py:523-583)
 TERM_ORDER = ("exposure", "smoothness", "color", "spatial", "decouple", "perceptual", "frequency", "total")
+# the paired terms against a ground truth (upr_t_loss_paired): with a target the engine's scalars
+# grow from 9 to 11, these two after the dynamic smooth weight
+PAIRED_TERMS = ("reconstruction", "ssim_loss")
+REC_EPS = 1e-3
 
 VGG19_E = (64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M", 512, 512, 512, 512, "M")
 
@@ -44,6 +48,34 @@ def texture_complexity(img, method):
         _chk(L.lib().upr_t_texture_complexity(_p(img), B, C, H, W, int(method), _p(acc), _p(out), _stream()),
              "texture_complexity")
     return out
+
+
+def paired_terms(enh, target, eps=REC_EPS, w_rec=1.0, w_ssim=1.0, out2=None, total=None, g_enh=None):
+    """upr_t_loss_paired: enh, target [B,3,H,W] float32 contiguous on the device
+    -> out2 = [reconstruction (Charbonnier, eps), ssim_loss (1 - mean SSIM)],
+    unweighted.  total (a one-element fp32 device tensor) += w_rec * out2[0] +
+    w_ssim * out2[1]; g_enh (enh's shape) += the weighted gradient w.r.t. enh."""
+    lib = L.lib()
+    if enh.dim() != 4 or enh.shape[1] != 3 or enh.shape != target.shape:
+        raise ValueError(f"paired terms: enhanced and target [B,3,H,W] of one shape, got {tuple(enh.shape)} / "
+                         f"{tuple(target.shape)}")
+    for t in (enh, target, g_enh):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != enh.device):
+            raise ValueError("paired terms: contiguous float32 tensors on one device")
+    B, _, H, W = enh.shape
+    if out2 is None:
+        out2 = torch.empty(2, dtype=torch.float32, device=enh.device)
+    if B == 0:
+        raise ValueError("paired terms: an empty batch has no mean")
+    nws = lib.upr_t_loss_paired_workspace(B, H, W)
+    if nws == 0:
+        raise ValueError(f"paired terms: a {B}x3x{H}x{W} batch is refused")
+    ws = torch.empty(nws, dtype=torch.uint8, device=enh.device)
+    with torch.cuda.device(enh.device):
+        _chk(lib.upr_t_loss_paired(_p(enh), _p(target), B, H, W, ctypes.c_float(eps), ctypes.c_float(w_rec),
+                                   ctypes.c_float(w_ssim), _p(ws), nws, _p(out2), _p(total), _p(g_enh), _stream()),
+             "loss_paired")
+    return out2
 
 
 def vgg19_features(seed=None):
@@ -180,6 +212,8 @@ class TotalLossEngine:
             self.params.update(params)
         self.vgg = VGGPerceptual(vgg_features) if vgg_features is not None else None
         self.features = vgg_features
+        # the paired terms' weights and Charbonnier eps: outside `w` (DWA never touches them), used with a target only
+        self.w_rec, self.w_ssim, self.rec_eps = 0.0, 0.0, REC_EPS
 
     def _cparams(self, illu_channels=1):
         p = self.params
@@ -187,10 +221,12 @@ class TotalLossEngine:
                                float(p["smooth_alpha"]), float(p["decouple_lambda"]), float(p["freq_high"]),
                                float(p["freq_low"]), int(bool(p["dynamic_smooth"])), int(illu_channels))
 
-    def __call__(self, low, enh, illu, refl, grads=True):
+    def __call__(self, low, enh, illu, refl, grads=True, target=None):
         """All NCHW fp32 device tensors; illu [B,1,H,W] (the model's) or
         [B,3,H,W] (loss.py:806-844).  Returns (terms [9] device tensor in
-        upr_t_loss_total order, (g_enh, g_illu, g_refl) or None)."""
+        upr_t_loss_total order, (g_enh, g_illu, g_refl) or None).  With a target
+        ([B,3,H,W], the ground truth of enh) terms has 11 entries: [9], [10] =
+        PAIRED_TERMS, unweighted; terms[7] and g_enh include them under w_rec / w_ssim."""
         lib, st = L.lib(), _stream()
         B, C, H, W = enh.shape
         dev = enh.device
@@ -198,7 +234,9 @@ class TotalLossEngine:
             raise NotImplementedError(f"loss: illumination [B,1,H,W] or [B,3,H,W] matching the images, got "
                                       f"{tuple(illu.shape)}")
         w = self.w
-        terms = torch.empty(9, dtype=torch.float32, device=dev)
+        if target is not None and tuple(target.shape) != tuple(enh.shape):
+            raise ValueError(f"loss: target {tuple(target.shape)} against an enhanced image {tuple(enh.shape)}")
+        terms = torch.empty(9 if target is None else 9 + len(PAIRED_TERMS), dtype=torch.float32, device=dev)
         zero(terms)
         prm = self._cparams(illu.shape[1])
         nws = lib.upr_t_loss_workspace_p(B, H, W, prm.patch)
@@ -220,6 +258,9 @@ class TotalLossEngine:
         if self.vgg is not None and w["perceptual"] != 0.0:
             self._perceptual(lib, st, low, enh, B, H, W, terms, acc, grads, g_enh)
         self._frequency(lib, st, low, enh, B, C, H, W, terms, acc, grads, g_enh, prm)
+        if target is not None:  # after the total and the unpaired gradient: both are accumulated into
+            paired_terms(enh, target, self.rec_eps, self.w_rec, self.w_ssim, out2=terms[9:11], total=terms[7:8],
+                         g_enh=g_enh)
         return terms, ((g_enh, g_illu, g_refl) if grads else None)
 
     def _perceptual(self, lib, st, low, enh, B, H, W, terms, acc, grads, g_enh):
@@ -274,7 +315,8 @@ class TotalLossEngine:
 
 class LossDict(dict):
     """The reference's loss_dict (loss.py:741-751: python floats from .item())
-    plus the dynamic smooth weight, read back lazily: the 9 scalars go to a
+    plus the dynamic smooth weight (and, from a call with a target, the two
+    PAIRED_TERMS), read back lazily: the 9 (11) scalars go to a
     pinned host buffer by an asynchronous copy queued behind the loss kernels,
     and the first read of the dict waits for that copy alone.  The reference
     syncs the host in the middle of every step here (its .item()s before the
@@ -297,6 +339,9 @@ class LossDict(dict):
             for i, k in enumerate(TERM_ORDER):
                 dict.__setitem__(self, k, v[i])
             dict.__setitem__(self, "smooth_weight", v[8])
+            for i, k in enumerate(PAIRED_TERMS):
+                if 9 + i < len(v):
+                    dict.__setitem__(self, k, v[9 + i])
             self._ev = self._host = None
         return self
 
@@ -361,7 +406,7 @@ class LossDict(dict):
 
 
 def terms_dict(terms, lazy=False):
-    """The 9 device loss scalars -> the reference's loss_dict.  lazy: a LossDict
+    """The 9 (with a target: 11) device loss scalars -> the reference's loss_dict.  lazy: a LossDict
     still waiting for its copy (the training step reads it back after its
     backward is queued); otherwise read back now, as the reference's .item()s."""
     d = LossDict(terms)
