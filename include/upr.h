@@ -613,6 +613,45 @@ int upr_guided_apply(const uint8_t* src_u8, size_t src_stride, int B, int H, int
                      int nw, uint8_t* enh_u8 /* [B,H,W,3] */, uint8_t* illu_u8 /* [B,H,W,3] or NULL */,
                      uint8_t* cmp_u8 /* [B,H,P*W,3] or NULL */, int cmp_panels /* 2 or 3 */, void* stream);
 
+/* Non-local means on the u8 pixels of an output file, the filter strength per
+ * pixel from the u8 illumination map (the Retinex gain ~ 1 / illumination
+ * amplifies the sensor noise by the same factor; no reference counterpart).
+ * Integers throughout: the device agrees with a numpy restatement byte for
+ * byte (tests/denoise_ref.py).
+ *
+ * upr_denoise_lut (host only, no device call): the strength table of a
+ * (strength, floor, patch) triple, fp64 one operation at a time, with
+ * n = 3 (2 patch + 1)^2 and L = 0..255:
+ *   h = strength * 255.0 / (double)max(L, floor);  h2 = h * h
+ *   lut[L] = (uint32)min(floor(1048576.0 * 32.0 / ((double)n * h2) + 0.5), 4294967295.0)
+ *   lut[L] = 4294967295 when h2 == 0
+ * strength is the assumed noise std of the input in u8 levels before the
+ * enhancement gain.  UPR_ERR_ARG for a NULL lut, strength < 0 or not a number,
+ * floor outside 1..255, patch outside 1..3.
+ *
+ * upr_denoise_nlm_u8: src_u8 and out_u8 are u8 [B,H,W,3]; illu_u8 (NULL: L =
+ * 255 everywhere) is the illumination file's pixels, u8 with a pixel stride of
+ * illu_stride = 1 ([B,H,W]) or 3 ([B,H,W,3], channel 0 is read) bytes.  Only
+ * the content rectangle (top, left, nh, nw) is filtered; the pixels outside it
+ * are copied.  I~(y, x) is src at coordinates clamped to the rectangle.  For a
+ * content pixel p and every candidate q = p + s, |s_y|, |s_x| <= search, that
+ * lies inside the rectangle (the others are skipped):
+ *   d = sum over |o_y|, |o_x| <= patch and c of (I~_c(p + o) - I~_c(q + o))^2
+ *     (an exact integer, <= 147 * 255^2 < 2^24)
+ *   t = ((uint64)d * lut[L(p)]) >> 20          (t / 32 = mean sq. difference / h^2)
+ *   w = EXPW[t] for t < 256, else 0;  EXPW[i] = floor(4095 exp(-i / 32) + 0.5),
+ *     256 literal integers 4095, 3969, 3847, 3729 ... 2, 2, 1, 1
+ *   out_c(p) = (2 sum(w I_c(q)) + sum(w)) / (2 sum(w))   (integer division)
+ * The centre candidate contributes 4095, so sum(w) > 0; every sum fits int32.
+ * No workspace.  UPR_ERR_ARG, with nothing launched, for a NULL src / out /
+ * lut, out_u8 == src_u8 or overlapping it, B < 1, a content rectangle outside
+ * H x W, search outside 1..10, patch outside 1..3, illu_stride other than 1 /
+ * 3 with a map; UPR_ERR_SHAPE for B > 65535. */
+int upr_denoise_lut(double strength, int floor, int patch, uint32_t* lut /* [256] */);
+int upr_denoise_nlm_u8(const uint8_t* src_u8, const uint8_t* illu_u8 /* or NULL */, int illu_stride, int B, int H,
+                       int W, int top, int left, int nh, int nw, int search, int patch,
+                       const uint32_t* lut /* [256], host */, uint8_t* out_u8, void* stream);
+
 /* Host copies of the 8-bit Lab integer tables (for CPU-side verification):
  * gamma[256], cbrt[3072], yf[512], invgamma[4096] (uint16), rgb2xyz[9], xyz2rgb[9]. */
 void upr_lab_tables(uint16_t* gamma, uint16_t* cbrt, uint16_t* yf, uint16_t* invgamma, int32_t* rgb2xyz,

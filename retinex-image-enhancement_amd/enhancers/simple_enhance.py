@@ -21,6 +21,13 @@ output_size="original" (an addition; the default "letterbox" changes nothing) wr
 files at the source's size: the letterboxed result is carried to the decoded image's pixels by
 the guided-filter restore of upr.guided (radius guided_radius, regulariser guided_eps), or, when
 the letterbox resized nothing, by cropping the bars away.
+denoise="nlm" (an addition; the default "off" changes nothing) runs the illumination-weighted
+non-local means of upr.denoise on the enhanced image's u8 pixels before they are written (after
+CLAHE; inside the letterbox's content rectangle; strength denoise_strength * 255 / max(illumination,
+denoise_floor) levels per pixel, search radius denoise_search, patch radius denoise_patch): the
+_enhanced file and the comparison's enhanced panel hold the denoised pixels, the _illumination
+file and the returned tensors do not change.  With output_size="original" the letterboxed pixels
+are denoised and the guided restore carries them to the source's size.
 enhance_batch_images(batch_size > 1) and main.py --infer_batch run the batched
 directory path (run_batched): files grouped by letterboxed shape (plan_batches),
 one upload + upr_letterbox_batch, one forward, one CLAHE, one upr_panels_u8 and
@@ -100,6 +107,35 @@ def _check_output_size(output_size, guided_radius, guided_eps):
         raise ValueError(f"output_size must be one of {OUTPUT_SIZES}, got {output_size!r}")
     from upr import guided
     guided.check_params(guided_radius, guided_eps)
+
+
+DENOISERS = ("off", "nlm")
+
+
+class _Denoise(NamedTuple):
+    """The public denoise* arguments, checked."""
+    mode: str = "off"
+    strength: float = 1.0
+    floor: int = 16
+    search: int = 5
+    patch: int = 2
+
+    @property
+    def on(self):
+        return self.mode == "nlm"
+
+    def apply(self, enh_u8, illu_u8, content):
+        """u8 [B,H,W,3] enhanced / illumination pixels on the device -> the denoised enhanced pixels."""
+        from upr import denoise
+        return denoise.nlm(enh_u8, illu_u8, content, self.strength, self.floor, self.search, self.patch)
+
+
+def _check_denoise(denoise, denoise_strength=1.0, denoise_floor=16, denoise_search=5, denoise_patch=2):
+    if denoise not in DENOISERS:
+        raise ValueError(f"denoise must be one of {DENOISERS}, got {denoise!r}")
+    from upr import denoise as upr_denoise
+    upr_denoise.check_params(denoise_strength, denoise_floor, denoise_search, denoise_patch)
+    return _Denoise(denoise, float(denoise_strength), int(denoise_floor), int(denoise_search), int(denoise_patch))
 
 
 def _writer_count():
@@ -251,13 +287,16 @@ def create_comparison(img_low, img_enhanced, save_path, writer=None, illu_map=No
 
 def save_original_size(src_u8, img_low, img_enhanced, illu_map, paths, max_size=None, comparison=2, writer=None,
                        png_encoder="host", image_format="png", jpeg_quality=95, guided_radius=4, guided_eps=1e-4,
-                       jpeg_subsampling="444", jpeg_optimize=False, jpeg_gray_maps=False):
+                       jpeg_subsampling="444", jpeg_optimize=False, jpeg_gray_maps=False, denoise="off",
+                       denoise_strength=1.0, denoise_floor=16, denoise_search=5, denoise_patch=2):
     """The three files of one image at the source's size (output_size="original").  src_u8: the
     decoded uint8 HWC image; img_low / img_enhanced / illu_map: the [1,C,H',W'] letterboxed
     tensors whose pixels the files hold with output_size="letterbox"; paths: (enhanced,
     illumination, comparison) file names, the last unused with comparison=None (2: [input |
-    enhanced], 3: [input | enhanced | illumination]).  upr.guided.restore on those pixels."""
+    enhanced], 3: [input | enhanced | illumination]).  upr.guided.restore on those pixels;
+    denoise="nlm" denoises the letterboxed enhanced pixels first (the restore's target)."""
     from upr import guided, runtime
+    dn = _check_denoise(denoise, denoise_strength, denoise_floor, denoise_search, denoise_patch)
     H, W = src_u8.shape[:2]
     content = letterbox_content((H, W), max_size if max_size is not None else (H, W), auto=True, scaleup=False)
     dev = img_enhanced.device
@@ -266,8 +305,10 @@ def save_original_size(src_u8, img_low, img_enhanced, illu_map, paths, max_size=
         return runtime.to_u8_hwc(t.detach().squeeze(0).to(dev)).unsqueeze(0)
 
     src = torch.from_numpy(np.ascontiguousarray(src_u8)).to(dev).unsqueeze(0)
-    outs = guided.restore(src, u8(img_low), u8(img_enhanced), u8(illu_map), content, guided_radius, guided_eps,
-                          comparison)
+    target, illu_u8 = u8(img_enhanced), u8(illu_map)
+    if dn.on:
+        target = dn.apply(target, illu_u8, content)
+    outs = guided.restore(src, u8(img_low), target, illu_u8, content, guided_radius, guided_eps, comparison)
     colour = _Jpeg(jpeg_quality, jpeg_subsampling, jpeg_optimize)
     modes = (colour, colour._replace(gray=bool(jpeg_gray_maps)), colour)
     for arr, path, msg, jpeg in zip(outs, paths, ("已保存", "已保存", "已保存对比图像"), modes):
@@ -279,11 +320,38 @@ def save_original_size(src_u8, img_low, img_enhanced, illu_map, paths, max_size=
             _emit(arr[0].cpu().numpy(), path, msg, writer, image_format, jpeg)
 
 
+def save_denoised(img_low, img_enhanced, illu_map, paths, content, comparison=2, writer=None, png_encoder="host",
+                  image_format="png", jpeg_quality=95, jpeg_subsampling="444", jpeg_optimize=False,
+                  jpeg_gray_maps=False, denoise="nlm", denoise_strength=1.0, denoise_floor=16, denoise_search=5,
+                  denoise_patch=2):
+    """The three letterboxed files of one image with denoise="nlm": the pixels save_image and
+    create_comparison write, the enhanced ones denoised inside the content rectangle `content`
+    (utils.letterbox.letterbox_content) with the illumination file's pixels as the strength map.
+    paths and comparison as in save_original_size."""
+    from upr import runtime
+    dn = _check_denoise(denoise, denoise_strength, denoise_floor, denoise_search, denoise_patch)
+    dev = img_enhanced.device
+    low, enh, illu = (runtime.to_u8_hwc(t.detach().squeeze(0).to(dev)) for t in (img_low, img_enhanced, illu_map))
+    if dn.on:
+        enh = dn.apply(enh.unsqueeze(0), illu.unsqueeze(0), content)[0]
+    cmp = torch.cat([low, enh] + ([illu] if comparison == 3 else []), dim=1) if comparison else None
+    colour = _Jpeg(jpeg_quality, jpeg_subsampling, jpeg_optimize)
+    modes = (colour, colour._replace(gray=bool(jpeg_gray_maps)), colour)
+    for arr, path, msg, jpeg in zip((enh, illu, cmp), paths, ("已保存", "已保存", "已保存对比图像"), modes):
+        if arr is None:
+            continue
+        if png_encoder in _DEVICE_MATCHES:
+            _emit_device(arr, [(path, msg)], writer, png_encoder, image_format, jpeg)
+        else:
+            _emit(arr.cpu().numpy(), path, msg, writer, image_format, jpeg)
+
+
 def enhance_single_image(model, image_path, output_dir, device, max_size=None, enable_multi_scale=False,
                          enable_content_aware=False, adjuster=None, precision="fp32", _decoded=None, _writer=None,
                          png_encoder="host", image_format="png", jpeg_quality=95, output_size="letterbox",
                          guided_radius=4, guided_eps=1e-4, jpeg_subsampling="444", jpeg_optimize=False,
-                         jpeg_gray_maps=False):
+                         jpeg_gray_maps=False, denoise="off", denoise_strength=1.0, denoise_floor=16, denoise_search=5,
+                         denoise_patch=2):
     """Enhance one file and write {name}_enhanced/_illumination/_comparison.png (reference :135-199;
     .jpg with image_format="jpg", quality jpeg_quality; jpeg_subsampling and jpeg_optimize apply to
     all three files, jpeg_gray_maps makes _illumination.jpg a one-component file).
@@ -291,12 +359,16 @@ def enhance_single_image(model, image_path, output_dir, device, max_size=None, e
     png_encoder="device" encodes the three files on the GPU (same pixels, larger files),
     "device_lz" does so with LZ77 matching (same pixels, smaller files than "device").
     output_size="original" writes the three files at the source's size (save_original_size);
-    the returned tensors stay the letterboxed ones."""
+    the returned tensors stay the letterboxed ones.  denoise="nlm" writes the enhanced pixels
+    denoised (upr.denoise.nlm, after CLAHE, whichever enhancer ran); the returned tensors are not."""
     _check_encoder(png_encoder)
     _check_format(image_format, jpeg_quality, jpeg_subsampling, jpeg_optimize, jpeg_gray_maps)
     _check_output_size(output_size, guided_radius, guided_eps)
+    dn = _check_denoise(denoise, denoise_strength, denoise_floor, denoise_search, denoise_patch)
+    noise = dict(denoise=dn.mode, denoise_strength=dn.strength, denoise_floor=dn.floor, denoise_search=dn.search,
+                 denoise_patch=dn.patch)
     print(f"正在处理: {os.path.basename(image_path)}")
-    if _decoded is None and output_size == "original":
+    if _decoded is None and (output_size == "original" or dn.on):
         _decoded = _decode(image_path)
     img_low, _ = load_image(image_path, max_size, decoded=_decoded)
     if precision == "fp16":
@@ -323,7 +395,16 @@ def enhance_single_image(model, image_path, output_dir, device, max_size=None, e
                            [os.path.join(output_dir, f"{name}_{kind}.{image_format}")
                             for kind in ("enhanced", "illumination", "comparison")], max_size, 2, _writer,
                            png_encoder, guided_radius=guided_radius, guided_eps=guided_eps,
-                           jpeg_gray_maps=jpeg_gray_maps, **fmt)
+                           jpeg_gray_maps=jpeg_gray_maps, **fmt, **noise)
+        print("图像增强完成！")
+        return img_enhanced, illu_map
+    if dn.on:
+        shape = _decoded[0].shape[:2]
+        save_denoised(img_low, img_enhanced, illu_map,
+                      [os.path.join(output_dir, f"{name}_{kind}.{image_format}")
+                       for kind in ("enhanced", "illumination", "comparison")],
+                      letterbox_content(shape, max_size if max_size is not None else shape, auto=True, scaleup=False),
+                      2, _writer, png_encoder, jpeg_gray_maps=jpeg_gray_maps, **fmt, **noise)
         print("图像增强完成！")
         return img_enhanced, illu_map
     save_image(img_enhanced, os.path.join(output_dir, f"{name}_enhanced.{image_format}"), _writer, png_encoder, **fmt)
@@ -388,18 +469,23 @@ def letterboxed_shapes(image_files, max_size=None):
     return shapes
 
 
-def batch_keys(image_files, max_size=None, output_size="letterbox"):
+def batch_keys(image_files, max_size=None, output_size="letterbox", denoise="off"):
     """plan_batches' key of every file: its letterboxed (H, W), followed with
     output_size="original" by its own (H, W) -- a batch then holds images of one size, so its
-    restored outputs are one [B,H,W,3] tensor."""
+    restored outputs are one [B,H,W,3] tensor -- or else, with denoise="nlm", by its content
+    rectangle, which the batch's one denoise launch takes."""
     keys = letterboxed_shapes(image_files, max_size)
-    if output_size != "original":
+    if output_size != "original" and denoise != "nlm":
         return keys
     out = []
     for path, key in zip(image_files, keys):
         with Image.open(path) as im:
             w, h = im.size
-        out.append(tuple(key) + (h, w))
+        if output_size == "original":
+            out.append(tuple(key) + (h, w))
+        else:
+            out.append(tuple(key) + letterbox_content((h, w), max_size if max_size is not None else (h, w), auto=True,
+                                                      scaleup=False))
     return out
 
 
@@ -513,7 +599,8 @@ def _finish_batch(job, writer, clock, image_lines, write_pixels=_write_png, trim
 def run_batched(model, image_files, output_dir, device, *, max_size=None, precision="fp32", png_encoder="host",
                 batch_size=8, decode_threads=4, clahe=True, comparison=2, image_lines=True, timings=None,
                 image_format="png", jpeg_quality=95, output_size="letterbox", guided_radius=4, guided_eps=1e-4,
-                jpeg_subsampling="444", jpeg_optimize=False, jpeg_gray_maps=False):
+                jpeg_subsampling="444", jpeg_optimize=False, jpeg_gray_maps=False, denoise="off", denoise_strength=1.0,
+                denoise_floor=16, denoise_search=5, denoise_patch=2):
     """The batched directory pipeline behind enhance_batch_images(batch_size > 1) and
     main.py --mode predict --infer_batch: for every file {name}_enhanced.png,
     {name}_illumination.png and, unless comparison is None, {name}_comparison.png
@@ -543,15 +630,21 @@ def run_batched(model, image_files, output_dir, device, *, max_size=None, precis
     [B,H,W,3] outputs.  A batch's device and pinned host memory then grow with the
     full-resolution pixel count: 3 + 3 * (2 + comparison) bytes per source pixel on the device
     (the staged source and the three outputs) plus the encoders' buffers, not with the
-    letterboxed one."""
+    letterboxed one.
+
+    denoise="nlm": behind upr_panels_u8 one upr.denoise.nlm launch per batch filters the enhanced
+    pixels inside the content rectangle (batches are then keyed by that rectangle as well); the
+    comparison's enhanced panel is replaced by torch.cat, and with output_size="original" the
+    denoised pixels are the restore's target."""
     from upr import guided, runtime
     _check_encoder(png_encoder)
     _check_format(image_format, jpeg_quality, jpeg_subsampling, jpeg_optimize, jpeg_gray_maps)
     _check_output_size(output_size, guided_radius, guided_eps)
+    dn = _check_denoise(denoise, denoise_strength, denoise_floor, denoise_search, denoise_patch)
     original = output_size == "original"
     if comparison not in (None, 2, 3):
         raise ValueError(f"comparison must be None, 2 or 3, got {comparison!r}")
-    batches = plan_batches(batch_keys(image_files, max_size, output_size), batch_size)
+    batches = plan_batches(batch_keys(image_files, max_size, output_size, dn.mode), batch_size)
     dev = torch.device(device)
     if dev.type == "cuda" and dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -576,13 +669,21 @@ def run_batched(model, image_files, output_dir, device, *, max_size=None, precis
             enh, _, illu = model(x)
         if clahe:
             enh = adjuster.apply_clahe_enhancement(enh)
+        content = letterbox_content(images[0].shape[:2], new_shape, auto=True, scaleup=False)
         if original:
             enh_u8, illu_u8, _ = runtime.panels_u8(x, enh, illu, None)
-            u8s = guided.restore(sources, runtime.panels_u8(x, x, None, None)[0], enh_u8, illu_u8,
-                                 letterbox_content(images[0].shape[:2], new_shape, auto=True, scaleup=False),
+            if dn.on:
+                enh_u8 = dn.apply(enh_u8, illu_u8, content)
+            u8s = guided.restore(sources, runtime.panels_u8(x, x, None, None)[0], enh_u8, illu_u8, content,
                                  guided_radius, guided_eps, comparison)
         else:
             u8s = runtime.panels_u8(x, enh, illu, comparison)
+            if dn.on:
+                den, cmp = dn.apply(u8s[0], u8s[1], content), u8s[2]
+                if cmp is not None:  # [input | enhanced (| illumination)]: the middle panel is the denoised one
+                    Wl = den.shape[2]
+                    cmp = torch.cat([cmp[:, :, :Wl], den, cmp[:, :, 2 * Wl:]], dim=2)
+                u8s = (den, u8s[1], cmp)
         outputs = []
         for (_, msg), u8, jpeg in zip(kinds, u8s, jpegs):
             if png_encoder in _DEVICE_MATCHES:
@@ -647,7 +748,8 @@ def run_batched(model, image_files, output_dir, device, *, max_size=None, precis
 def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preact=True, use_aspp=True, seed=None,
                          precision="fp32", png_encoder="host", batch_size=1, decode_threads=4, timings=None,
                          image_format="png", jpeg_quality=95, output_size="letterbox", guided_radius=4,
-                         guided_eps=1e-4, jpeg_subsampling="444", jpeg_optimize=False, jpeg_gray_maps=False):
+                         guided_eps=1e-4, jpeg_subsampling="444", jpeg_optimize=False, jpeg_gray_maps=False,
+                         denoise="off", denoise_strength=1.0, denoise_floor=16, denoise_search=5, denoise_patch=2):
     """Enhance every image of a directory (reference :202-250).
 
     batch_size=1 (the default) is the reference's one-image-at-a-time loop with a decode
@@ -660,12 +762,17 @@ def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preac
     that batch: DESIGN.md 4.5).  timings: see run_batched (batched path only).  image_format="jpg"
     writes the three files as .jpg of quality jpeg_quality (jpeg_subsampling, jpeg_optimize and
     jpeg_gray_maps as in enhance_single_image).  output_size="original" writes them
-    at each source's size (run_batched / save_original_size; guided_radius, guided_eps)."""
+    at each source's size (run_batched / save_original_size; guided_radius, guided_eps).
+    denoise="nlm" writes the enhanced pixels denoised (denoise_strength, denoise_floor,
+    denoise_search, denoise_patch as in enhance_single_image)."""
     _check_encoder(png_encoder)
     _check_format(image_format, jpeg_quality, jpeg_subsampling, jpeg_optimize, jpeg_gray_maps)
     _check_output_size(output_size, guided_radius, guided_eps)
+    dn = _check_denoise(denoise, denoise_strength, denoise_floor, denoise_search, denoise_patch)
     restore = dict(output_size=output_size, guided_radius=guided_radius, guided_eps=guided_eps,
-                   jpeg_subsampling=jpeg_subsampling, jpeg_optimize=jpeg_optimize, jpeg_gray_maps=jpeg_gray_maps)
+                   jpeg_subsampling=jpeg_subsampling, jpeg_optimize=jpeg_optimize, jpeg_gray_maps=jpeg_gray_maps,
+                   denoise=dn.mode, denoise_strength=dn.strength, denoise_floor=dn.floor, denoise_search=dn.search,
+                   denoise_patch=dn.patch)
     batch_size = int(batch_size)
     if batch_size < 1:
         raise ValueError(f"batch_size must be >= 1, got {batch_size}")

@@ -20,6 +20,10 @@ model's 3-tuple (reference predict.py:163 raises ValueError).
 --guided_radius R / --guided_eps E: original writes the enhance / predict files
 at the source's size -- the letterboxed result carried to the decoded pixels by
 the guided-filter restore (upr.guided), the bars cropped away.
+--denoise {off,nlm} (an addition, default off) with --denoise_strength /
+--denoise_floor / --denoise_search / --denoise_patch: nlm writes the enhance /
+predict files with the enhanced pixels denoised by the illumination-weighted
+non-local means of upr.denoise (the illumination file does not change).
 --infer_batch N (an addition, default 1) runs --mode enhance / predict on a
 directory N images at a time (enhancers/simple_enhance.py run_batched).
 --mode train runs trainers.train.train(args): images of --train_dir are decoded
@@ -59,8 +63,9 @@ if _HERE not in sys.path:
 from models.model import UP_Retinex  # noqa: E402
 from enhancers.simple_enhance import (enhance_single_image, enhance_batch_images, list_images,  # noqa: E402
                                       load_image, save_image, create_comparison, run_batched, save_original_size,
-                                      _decode)
+                                      save_denoised, _decode)
 from enhancers.adaptive_params import AdaptiveParameterAdjuster  # noqa: E402
+from utils.letterbox import letterbox_content  # noqa: E402
 
 
 def _jpeg_quality(text):
@@ -143,6 +148,15 @@ def build_parser():
                         'or the source\'s (guided-filter restore of the result to the decoded image)')
     p.add_argument('--guided_radius', type=int, default=4, help='--output_size original: window radius, 1..32')
     p.add_argument('--guided_eps', type=float, default=1e-4, help='--output_size original: regulariser, > 0')
+    p.add_argument('--denoise', choices=['off', 'nlm'], default='off',
+                   help='--mode enhance / predict: nlm denoises the enhanced image\'s u8 pixels before they are '
+                        'written (non-local means, stronger where the illumination map is darker)')
+    p.add_argument('--denoise_strength', type=float, default=1.0,
+                   help='--denoise nlm: assumed noise std of the input in u8 levels, >= 0')
+    p.add_argument('--denoise_floor', type=int, default=16,
+                   help='--denoise nlm: the illumination level below which the strength stops growing, 1..255')
+    p.add_argument('--denoise_search', type=int, default=5, help='--denoise nlm: search radius, 1..10')
+    p.add_argument('--denoise_patch', type=int, default=2, help='--denoise nlm: patch radius, 1..3')
     p.add_argument('--infer_batch', type=int, default=1,
                    help='--mode enhance / predict on a directory: images per batch (1: one image at a time; '
                         '> 1: the batched path, files grouped by letterboxed shape, --num_workers decode threads; '
@@ -196,6 +210,11 @@ def parse_args(argv=None):
         args.weight_ssim = 1.0 if args.weight_ssim is None else args.weight_ssim
     if args.val_reference_dir and not args.val_dir:
         parser.error("--val_reference_dir needs --val_dir")
+    try:
+        from upr import denoise
+        denoise.check_params(args.denoise_strength, args.denoise_floor, args.denoise_search, args.denoise_patch)
+    except ValueError as e:
+        parser.error(str(e))
     return args
 
 
@@ -217,8 +236,14 @@ def _output_format(args):
                 jpeg_gray_maps=args.jpeg_gray_maps)
 
 
+def _denoise(args):
+    return dict(denoise=args.denoise, denoise_strength=args.denoise_strength, denoise_floor=args.denoise_floor,
+                denoise_search=args.denoise_search, denoise_patch=args.denoise_patch)
+
+
 def _restore(args):
-    return dict(output_size=args.output_size, guided_radius=args.guided_radius, guided_eps=args.guided_eps)
+    return dict(output_size=args.output_size, guided_radius=args.guided_radius, guided_eps=args.guided_eps,
+                **_denoise(args))
 
 
 def _predict_one(model, path, args):
@@ -240,7 +265,16 @@ def _predict_one(model, path, args):
                            [os.path.join(args.output_dir, f"{name}_{kind}.{ext}")
                             for kind in ("enhanced", "illumination", "comparison")], args.max_size,
                            None if args.no_comparison else 3, guided_radius=args.guided_radius,
-                           guided_eps=args.guided_eps, **enc)
+                           guided_eps=args.guided_eps, **enc, **_denoise(args))
+        return
+    if args.denoise == 'nlm':
+        shape = decoded[0].shape[:2]
+        save_denoised(x, enh, illu,
+                      [os.path.join(args.output_dir, f"{name}_{kind}.{ext}")
+                       for kind in ("enhanced", "illumination", "comparison")],
+                      letterbox_content(shape, args.max_size if args.max_size is not None else shape, auto=True,
+                                        scaleup=False),
+                      None if args.no_comparison else 3, **enc, **_denoise(args))
         return
     save_image(enh, os.path.join(args.output_dir, f"{name}_enhanced.{ext}"), **dict(enc, jpeg_gray_maps=False))
     save_image(illu, os.path.join(args.output_dir, f"{name}_illumination.{ext}"), **enc)

@@ -4,7 +4,9 @@
 --output_size {letterbox,original} with --guided_radius / --guided_eps (original: the files
 have the source's size, upr.guided), and --image_format {png,jpg} with --jpeg_quality,
 --jpeg_subsampling {444,420}, --jpeg_optimize and --jpeg_gray_maps (jpg: the three files as
-JPEGs, as main.py's flags of the same names)."""
+JPEGs, as main.py's flags of the same names), and --denoise {off,nlm} with --denoise_strength /
+--denoise_floor / --denoise_search / --denoise_patch (nlm: the enhanced pixels are denoised
+before they are written, upr.denoise)."""
 import argparse
 import os
 import sys
@@ -41,12 +43,23 @@ def build_parser():
     ap.add_argument('--jpeg_optimize', action='store_true', help='--image_format jpg: Huffman tables built per file')
     ap.add_argument('--jpeg_gray_maps', action='store_true',
                     help='--image_format jpg: write _illumination.jpg as a one-component (grayscale) file')
+    ap.add_argument('--denoise', choices=['off', 'nlm'], default='off',
+                    help='nlm: denoise the enhanced image\'s u8 pixels before they are written (non-local means, '
+                         'stronger where the illumination map is darker)')
+    ap.add_argument('--denoise_strength', type=float, default=1.0,
+                    help='--denoise nlm: assumed noise std of the input in u8 levels, >= 0')
+    ap.add_argument('--denoise_floor', type=int, default=16,
+                    help='--denoise nlm: the illumination level below which the strength stops growing, 1..255')
+    ap.add_argument('--denoise_search', type=int, default=5, help='--denoise nlm: search radius, 1..10')
+    ap.add_argument('--denoise_patch', type=int, default=2, help='--denoise nlm: patch radius, 1..3')
     return ap
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     restore = dict(output_size=args.output_size, guided_radius=args.guided_radius, guided_eps=args.guided_eps,
+                   denoise=args.denoise, denoise_strength=args.denoise_strength, denoise_floor=args.denoise_floor,
+                   denoise_search=args.denoise_search, denoise_patch=args.denoise_patch,
                    image_format=args.image_format, jpeg_quality=args.jpeg_quality,
                    jpeg_subsampling=args.jpeg_subsampling, jpeg_optimize=args.jpeg_optimize,
                    jpeg_gray_maps=args.jpeg_gray_maps)

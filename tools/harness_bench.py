@@ -8,6 +8,7 @@ enhance_batch_images over N synthetic low-light PNGs, images/s including IO.
                                 [--image_format jpg [--jpeg_quality 95] [--jpeg_subsampling 420] [--jpeg_optimize]
                                  [--jpeg_gray_maps] [--jpeg_modes_compare [--rounds 3] [--out FILE]]]
                                 [--max_size 512 [--output_size original]] [--restore_compare [--rounds 3]]
+                                [--denoise nlm]
 
 --batch_size > 1 runs the batched path and adds its per-stage wall-time sums
 (`stage_seconds`) to the JSON; --mixed writes images of --size and of half of it,
@@ -21,6 +22,8 @@ and images/s as median and range.
 --restore_compare times the two routes to source-sized files on the same directory, alternating,
 --rounds times each: `--max_size M --output_size original` against no --max_size (the forward at
 the sources' own size); images/s as median and range of the rounds.
+--denoise nlm passes denoise="nlm" on (upr.denoise at its defaults; tools/denoise_bench.py
+alternates it with off).
 """
 import argparse
 import contextlib
@@ -50,7 +53,7 @@ def write_inputs(src, n, size, mixed=False):
 
 def run(src, out, n, size, precision="fp32", png_encoder="host", batch_size=1, decode_threads=4, mixed=False,
         warm=True, image_format="png", jpeg_quality=95, max_size=None, output_size="letterbox",
-        jpeg_subsampling="444", jpeg_optimize=False, jpeg_gray_maps=False):
+        jpeg_subsampling="444", jpeg_optimize=False, jpeg_gray_maps=False, denoise="off"):
     """One timed enhance_batch_images over the files of `src` -> the result dict."""
     from enhancers.simple_enhance import enhance_batch_images
     kw = {"png_encoder": png_encoder} if png_encoder != "host" else {}
@@ -62,6 +65,8 @@ def run(src, out, n, size, precision="fp32", png_encoder="host", batch_size=1, d
         kw["max_size"] = max_size
     if output_size != "letterbox":
         kw["output_size"] = output_size
+    if denoise != "off":
+        kw["denoise"] = denoise
     timings = None
     if batch_size != 1:
         timings = {}
@@ -81,6 +86,7 @@ def run(src, out, n, size, precision="fp32", png_encoder="host", batch_size=1, d
            "n": n, "size": size, "precision": precision, "png_encoder": png_encoder,
            "batch_size": batch_size, "mixed": bool(mixed), "seconds": el, "files_written": len(os.listdir(out)),
            "image_format": image_format, "max_size": max_size, "output_size": output_size,
+           "denoise": denoise,
            "output_bytes": sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out))}
     if image_format == "jpg":
         res["jpeg_quality"] = jpeg_quality
@@ -159,6 +165,7 @@ def main():
     ap.add_argument("--output_size", choices=["letterbox", "original"], default="letterbox")
     ap.add_argument("--restore_compare", action="store_true")
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--denoise", choices=["off", "nlm"], default="off")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory(dir="/tmp") as d:
         src, out = os.path.join(d, "in"), os.path.join(d, "out")
@@ -172,7 +179,7 @@ def main():
                       args.decode_threads, args.mixed, image_format=args.image_format,
                       jpeg_quality=args.jpeg_quality, max_size=args.max_size, output_size=args.output_size,
                       jpeg_subsampling=args.jpeg_subsampling, jpeg_optimize=args.jpeg_optimize,
-                      jpeg_gray_maps=args.jpeg_gray_maps)
+                      jpeg_gray_maps=args.jpeg_gray_maps, denoise=args.denoise)
     print(json.dumps(res))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
