@@ -652,6 +652,52 @@ int upr_denoise_nlm_u8(const uint8_t* src_u8, const uint8_t* illu_u8 /* or NULL 
                        int W, int top, int left, int nh, int nw, int search, int patch,
                        const uint32_t* lut /* [256], host */, uint8_t* out_u8, void* stream);
 
+/* Blind denoising: the noise level of each image measured on the device, a
+ * strength table per image built from it, and the filter reading those tables
+ * (no host round trip; tests/noise_ref.py restates all three, bit for bit).
+ *
+ * upr_noise_sigma_u8: the Laplacian-difference estimator (Immerkaer 1996) with
+ * a median.  src_u8 is u8 [B,H,W,3], the letterboxed low-light INPUT's pixels
+ * (not the enhanced image's), with the content rectangle (top, left, nh, nw).
+ * For every channel c and interior content pixel 1 <= y <= nh-2, 1 <= x <= nw-2
+ * (content coordinates; nothing is clamped, no pixel outside the rectangle
+ * counts):
+ *   r = I(y-1,x-1) + I(y-1,x+1) + I(y+1,x-1) + I(y+1,x+1)
+ *       - 2 (I(y-1,x) + I(y+1,x) + I(y,x-1) + I(y,x+1)) + 4 I(y,x)      |r| <= 2040
+ *   the sample is skipped when one of its nine values is 0 or 255 (clipped
+ *   pixels understate the noise), else hist[|r|] += 1: one histogram of 2041
+ *   uint32 counts per image, the three channels pooled.
+ * Independent noise of std s gives r a std of 6 s (the squared coefficients
+ * sum to 36).  Then, per image:
+ *   n = sum(hist);  sigma = 0 when n == 0, else
+ *   b = the smallest bin with 2 cum(b) >= n, below = cum(b - 1) (0 for b = 0)
+ *   (lo, wd) = (b - 0.5, 1.0), or (0.0, 0.5) for b = 0
+ *   frac = (double)(n - 2 below) / (double)(2 hist[b])
+ *   med = lo + wd * frac;  sigma = med / 4.0469385011764905   (6 x 0.6744897501960817)
+ * in fp64, one operation at a time.  sigma: double [B] on the device.
+ * workspace: upr_noise_sigma_workspace(B) bytes, 16-byte aligned; the call
+ * zeroes it itself.  A rectangle with nh < 3 or nw < 3 is legal: sigma = 0.
+ * UPR_ERR_ARG, with nothing launched, for a NULL src / sigma / workspace (or a
+ * misaligned one), B < 1, a rectangle outside H x W; UPR_ERR_SHAPE for
+ * 3 nh nw >= 2^31 or B > 65535; UPR_ERR_WORKSPACE for too little workspace.
+ *
+ * upr_denoise_lut_dev: lut[b] = upr_denoise_lut(scale * sigma[b], floor, patch)
+ * for every image, entry for entry (the same fp64 steps, the h2 == 0 entry
+ * included), one launch of B x 256 threads.  UPR_ERR_ARG as upr_denoise_lut,
+ * and for a NULL sigma, B < 1, scale < 0 or not finite.
+ *
+ * upr_denoise_nlm_u8_luts: upr_denoise_nlm_u8 with `luts` a DEVICE pointer to
+ * uint32 [B,256]; image b is filtered with row b.  Everything else, errors
+ * included, as upr_denoise_nlm_u8. */
+size_t upr_noise_sigma_workspace(int B);
+int upr_noise_sigma_u8(const uint8_t* src_u8, int B, int H, int W, int top, int left, int nh, int nw,
+                       double* sigma /* [B], device */, void* workspace, size_t workspace_bytes, void* stream);
+int upr_denoise_lut_dev(const double* sigma /* [B], device */, int B, double scale, int floor, int patch,
+                        uint32_t* lut /* [B,256], device */, void* stream);
+int upr_denoise_nlm_u8_luts(const uint8_t* src_u8, const uint8_t* illu_u8 /* or NULL */, int illu_stride, int B, int H,
+                            int W, int top, int left, int nh, int nw, int search, int patch,
+                            const uint32_t* luts /* [B,256], device */, uint8_t* out_u8, void* stream);
+
 /* Host copies of the 8-bit Lab integer tables (for CPU-side verification):
  * gamma[256], cbrt[3072], yf[512], invgamma[4096] (uint16), rgb2xyz[9], xyz2rgb[9]. */
 void upr_lab_tables(uint16_t* gamma, uint16_t* cbrt, uint16_t* yf, uint16_t* invgamma, int32_t* rgb2xyz,

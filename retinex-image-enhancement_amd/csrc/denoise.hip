@@ -19,9 +19,16 @@
 //                   either side only feed their neighbours.  The weight's index
 //                   (d * lut) >> 20 needs no 64-bit product: it is below 256
 //                   exactly when d <= dmax = (2^28 - 1) / lut, a per-pixel bound.
+//                   The strength table is a kernel argument (one for the batch,
+//                   upr_denoise_nlm_u8) or a row per image in device memory
+//                   (upr_denoise_nlm_u8_luts): two instantiations per patch
+//                   radius that differ in the one load that fills sLut.
 //  nlm_bars_kernel  copies the pixels outside the content rectangle.
+//  lut_rows_kernel  upr_denoise_lut_dev: a table per image from a device array of
+//                   noise levels (upr_noise_sigma_u8, noise.hip), a thread per entry.
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "upr_common.h"
 #include "../../include/upr.h"
@@ -53,8 +60,15 @@ __device__ const uint16_t kExpW[257] = {
     2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 1, 1,
     0};
 
+// the strength table of a launch: one for the whole batch, passed as a kernel argument (1 KB), or a
+// row per image in device memory (upr_denoise_nlm_u8_luts)
 struct NlmLut {
   uint32_t v[256];
+  __device__ __forceinline__ uint32_t at(int, int i) const { return v[i]; }
+};
+struct NlmLutRows {
+  const uint32_t* rows;  // [B,256]
+  __device__ __forceinline__ uint32_t at(int b, int i) const { return rows[(size_t)b * 256 + i]; }
 };
 
 // sum over the three channels of a_c * b_c of two packed pixels (byte 3 is zero)
@@ -71,10 +85,10 @@ __device__ __forceinline__ uint32_t from_right(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130 /* wave_shl:1 */, 0xF, 0xF, true);
 }
 
-template <int P>
+template <int P, typename Lut>
 __global__ __launch_bounds__(256) void nlm_kernel(const uint8_t* __restrict__ src, const uint8_t* __restrict__ illu,
                                                   int istride, int H, int W, int top, int left, int nh, int nw, int S,
-                                                  NlmLut lut, uint8_t* __restrict__ out) {
+                                                  Lut lut, uint8_t* __restrict__ out) {
   extern __shared__ __align__(16) uint8_t smem[];
   constexpr int TW = 64 - 2 * P, NR = kRows + 2 * P;
   const int R = S + P;
@@ -93,7 +107,7 @@ __global__ __launch_bounds__(256) void nlm_kernel(const uint8_t* __restrict__ sr
     tile[i] = make_uint2(r | g << 8 | bl << 16, r * r + g * g + bl * bl);
   }
   for (int i = tid; i < 257; i += 256) sExp[i] = kExpW[i];
-  sLut[tid] = lut.v[tid];
+  sLut[tid] = lut.at(b, tid);
   __syncthreads();
 
   const int lane = tid & 63, wv = tid >> 6;
@@ -180,15 +194,59 @@ __global__ __launch_bounds__(256) void nlm_bars_kernel(const uint8_t* __restrict
   }
 }
 
-template <int P>
+template <int P, typename Lut>
 int launch_nlm(const uint8_t* src, const uint8_t* illu, int istride, int B, int H, int W, int top, int left, int nh,
-               int nw, int S, const NlmLut& lut, uint8_t* out, hipStream_t st) {
+               int nw, int S, const Lut& lut, uint8_t* out, hipStream_t st) {
   const int R = S + P;
   const size_t lds = (size_t)(kTileH + 2 * R) * (64 + 2 * S) * sizeof(uint2) + (257 + 256) * sizeof(uint32_t);
-  hipLaunchKernelGGL(nlm_kernel<P>, dim3(cdiv(nw, 64 - 2 * P), cdiv(nh, kTileH), B), dim3(256), lds, st, src, illu,
-                     istride, H, W, top, left, nh, nw, S, lut, out);
+  hipLaunchKernelGGL((nlm_kernel<P, Lut>), dim3(cdiv(nw, 64 - 2 * P), cdiv(nh, kTileH), B), dim3(256), lds, st, src,
+                     illu, istride, H, W, top, left, nh, nw, S, lut, out);
   UPR_CHECK_HIP(hipGetLastError());
   return kOk;
+}
+
+// both entry points: the checks, the bars, the kernel of the patch radius
+template <typename Lut>
+int run_nlm(const uint8_t* src_u8, const uint8_t* illu_u8, int illu_stride, int B, int H, int W, int top, int left,
+            int nh, int nw, int search, int patch, const uint32_t* lut, uint8_t* out_u8, void* stream) {
+  if (!src_u8 || !out_u8 || !lut || B < 1 || H < 1 || W < 1 || nh < 1 || nw < 1 || top < 0 || left < 0 ||
+      top > H - nh || left > W - nw || search < 1 || search > kMaxSearch || patch < 1 || patch > kMaxPatch)
+    return UPR_ERR_ARG;
+  if (illu_u8 && illu_stride != 1 && illu_stride != 3) return UPR_ERR_ARG;
+  if (B > 65535) return UPR_ERR_SHAPE;
+  const size_t npix = (size_t)B * H * W;
+  if (src_u8 < out_u8 + 3 * npix && out_u8 < src_u8 + 3 * npix) return UPR_ERR_ARG;  // out aliases src
+  Lut table;
+  if constexpr (std::is_same<Lut, NlmLut>::value)
+    std::copy(lut, lut + 256, table.v);
+  else
+    table.rows = lut;
+  hipStream_t st = (hipStream_t)stream;
+  if (nh != H || nw != W) {
+    const int blocks = (int)std::min<size_t>((npix + 255) / 256, 4096);
+    hipLaunchKernelGGL(nlm_bars_kernel, dim3(blocks), dim3(256), 0, st, src_u8, out_u8, npix, H, W, top, left, nh, nw);
+    UPR_CHECK_HIP(hipGetLastError());
+  }
+  switch (patch) {
+    case 1: return launch_nlm<1>(src_u8, illu_u8, illu_stride, B, H, W, top, left, nh, nw, search, table, out_u8, st);
+    case 2: return launch_nlm<2>(src_u8, illu_u8, illu_stride, B, H, W, top, left, nh, nw, search, table, out_u8, st);
+    default: return launch_nlm<3>(src_u8, illu_u8, illu_stride, B, H, W, top, left, nh, nw, search, table, out_u8, st);
+  }
+}
+
+// one entry of the strength table (upr_denoise_lut), host and device: fp64, one operation at a time
+__host__ __device__ inline uint32_t lut_entry(double strength, int floor, int patch, int L) {
+  const double n = (double)(3 * (2 * patch + 1) * (2 * patch + 1));
+  const double h = strength * 255.0 / (double)(L > floor ? L : floor);
+  const double h2 = h * h;
+  if (h2 == 0.0) return 4294967295u;
+  const double v = ::floor(1048576.0 * 32.0 / (n * h2) + 0.5);
+  return v < 4294967295.0 ? (uint32_t)v : 4294967295u;
+}
+
+__global__ __launch_bounds__(256) void lut_rows_kernel(const double* __restrict__ sigma, double scale, int floor,
+                                                       int patch, uint32_t* __restrict__ lut) {
+  lut[(size_t)blockIdx.x * 256 + threadIdx.x] = lut_entry(scale * sigma[blockIdx.x], floor, patch, threadIdx.x);
 }
 
 }  // namespace
@@ -202,43 +260,30 @@ int upr_denoise_lut(double strength, int floor, int patch, uint32_t* lut) {
   if (!lut || !(strength >= 0.0) || !std::isfinite(strength) || floor < 1 || floor > 255 || patch < 1 ||
       patch > kMaxPatch)
     return UPR_ERR_ARG;
-  const double n = (double)(3 * (2 * patch + 1) * (2 * patch + 1));
-  for (int L = 0; L < 256; ++L) {
-    const double h = strength * 255.0 / (double)std::max(L, floor);
-    const double h2 = h * h;
-    if (h2 == 0.0) {
-      lut[L] = 4294967295u;
-      continue;
-    }
-    const double v = std::floor(1048576.0 * 32.0 / (n * h2) + 0.5);
-    lut[L] = (uint32_t)std::min(v, 4294967295.0);
-  }
+  for (int L = 0; L < 256; ++L) lut[L] = lut_entry(strength, floor, patch, L);
+  return UPR_OK;
+}
+
+int upr_denoise_lut_dev(const double* sigma, int B, double scale, int floor, int patch, uint32_t* lut, void* stream) {
+  if (!sigma || !lut || B < 1 || !(scale >= 0.0) || !std::isfinite(scale) || floor < 1 || floor > 255 || patch < 1 ||
+      patch > kMaxPatch)
+    return UPR_ERR_ARG;
+  hipLaunchKernelGGL(lut_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, sigma, scale, floor, patch, lut);
+  UPR_CHECK_HIP(hipGetLastError());
   return UPR_OK;
 }
 
 int upr_denoise_nlm_u8(const uint8_t* src_u8, const uint8_t* illu_u8, int illu_stride, int B, int H, int W, int top,
                        int left, int nh, int nw, int search, int patch, const uint32_t* lut, uint8_t* out_u8,
                        void* stream) {
-  if (!src_u8 || !out_u8 || !lut || B < 1 || H < 1 || W < 1 || nh < 1 || nw < 1 || top < 0 || left < 0 ||
-      top > H - nh || left > W - nw || search < 1 || search > kMaxSearch || patch < 1 || patch > kMaxPatch)
-    return UPR_ERR_ARG;
-  if (illu_u8 && illu_stride != 1 && illu_stride != 3) return UPR_ERR_ARG;
-  if (B > 65535) return UPR_ERR_SHAPE;
-  const size_t npix = (size_t)B * H * W;
-  if (src_u8 < out_u8 + 3 * npix && out_u8 < src_u8 + 3 * npix) return UPR_ERR_ARG;  // out aliases src
-  NlmLut table;
-  std::copy(lut, lut + 256, table.v);
-  hipStream_t st = (hipStream_t)stream;
-  if (nh != H || nw != W) {
-    const int blocks = (int)std::min<size_t>((npix + 255) / 256, 4096);
-    hipLaunchKernelGGL(nlm_bars_kernel, dim3(blocks), dim3(256), 0, st, src_u8, out_u8, npix, H, W, top, left, nh, nw);
-    UPR_CHECK_HIP(hipGetLastError());
-  }
-  switch (patch) {
-    case 1: return launch_nlm<1>(src_u8, illu_u8, illu_stride, B, H, W, top, left, nh, nw, search, table, out_u8, st);
-    case 2: return launch_nlm<2>(src_u8, illu_u8, illu_stride, B, H, W, top, left, nh, nw, search, table, out_u8, st);
-    default: return launch_nlm<3>(src_u8, illu_u8, illu_stride, B, H, W, top, left, nh, nw, search, table, out_u8, st);
-  }
+  return run_nlm<NlmLut>(src_u8, illu_u8, illu_stride, B, H, W, top, left, nh, nw, search, patch, lut, out_u8, stream);
+}
+
+int upr_denoise_nlm_u8_luts(const uint8_t* src_u8, const uint8_t* illu_u8, int illu_stride, int B, int H, int W,
+                            int top, int left, int nh, int nw, int search, int patch, const uint32_t* luts,
+                            uint8_t* out_u8, void* stream) {
+  return run_nlm<NlmLutRows>(src_u8, illu_u8, illu_stride, B, H, W, top, left, nh, nw, search, patch, luts, out_u8,
+                             stream);
 }
 
 }  // extern "C"

@@ -28,6 +28,9 @@ denoise_floor) levels per pixel, search radius denoise_search, patch radius deno
 _enhanced file and the comparison's enhanced panel hold the denoised pixels, the _illumination
 file and the returned tensors do not change.  With output_size="original" the letterboxed pixels
 are denoised and the guided restore carries them to the source's size.
+denoise_strength="auto" measures every image's noise level instead (upr.denoise.estimate_sigma on
+the input's u8 pixels, the comparison's left panel, inside the content rectangle) and filters it
+with denoise_auto_scale times that estimate: per image, on the device, nothing comes to the host.
 enhance_batch_images(batch_size > 1) and main.py --infer_batch run the batched
 directory path (run_batched): files grouped by letterboxed shape (plan_batches),
 one upload + upr_letterbox_batch, one forward, one CLAHE, one upr_panels_u8 and
@@ -119,23 +122,36 @@ class _Denoise(NamedTuple):
     floor: int = 16
     search: int = 5
     patch: int = 2
+    auto: bool = False       # denoise_strength="auto": every image's own estimate ...
+    auto_scale: float = 1.0  # ... times this
 
     @property
     def on(self):
         return self.mode == "nlm"
 
-    def apply(self, enh_u8, illu_u8, content):
-        """u8 [B,H,W,3] enhanced / illumination pixels on the device -> the denoised enhanced pixels."""
+    @property
+    def public_strength(self):
+        return "auto" if self.auto else self.strength
+
+    def apply(self, enh_u8, illu_u8, content, low_u8):
+        """u8 [B,H,W,3] enhanced / illumination / input pixels on the device -> the denoised enhanced
+        pixels.  low_u8 is read with auto alone: three launches on the current stream, no host copy."""
         from upr import denoise
+        if self.auto:
+            return denoise.nlm_auto(enh_u8, low_u8, illu_u8, content, self.auto_scale, self.floor, self.search,
+                                    self.patch)
         return denoise.nlm(enh_u8, illu_u8, content, self.strength, self.floor, self.search, self.patch)
 
 
-def _check_denoise(denoise, denoise_strength=1.0, denoise_floor=16, denoise_search=5, denoise_patch=2):
+def _check_denoise(denoise, denoise_strength=1.0, denoise_floor=16, denoise_search=5, denoise_patch=2,
+                   denoise_auto_scale=1.0):
     if denoise not in DENOISERS:
         raise ValueError(f"denoise must be one of {DENOISERS}, got {denoise!r}")
     from upr import denoise as upr_denoise
-    upr_denoise.check_params(denoise_strength, denoise_floor, denoise_search, denoise_patch)
-    return _Denoise(denoise, float(denoise_strength), int(denoise_floor), int(denoise_search), int(denoise_patch))
+    upr_denoise.check_params(denoise_strength, denoise_floor, denoise_search, denoise_patch, denoise_auto_scale)
+    auto = isinstance(denoise_strength, str)
+    return _Denoise(denoise, 1.0 if auto else float(denoise_strength), int(denoise_floor), int(denoise_search),
+                    int(denoise_patch), auto, float(denoise_auto_scale))
 
 
 def _writer_count():
@@ -288,7 +304,8 @@ def create_comparison(img_low, img_enhanced, save_path, writer=None, illu_map=No
 def save_original_size(src_u8, img_low, img_enhanced, illu_map, paths, max_size=None, comparison=2, writer=None,
                        png_encoder="host", image_format="png", jpeg_quality=95, guided_radius=4, guided_eps=1e-4,
                        jpeg_subsampling="444", jpeg_optimize=False, jpeg_gray_maps=False, denoise="off",
-                       denoise_strength=1.0, denoise_floor=16, denoise_search=5, denoise_patch=2):
+                       denoise_strength=1.0, denoise_floor=16, denoise_search=5, denoise_patch=2,
+                       denoise_auto_scale=1.0):
     """The three files of one image at the source's size (output_size="original").  src_u8: the
     decoded uint8 HWC image; img_low / img_enhanced / illu_map: the [1,C,H',W'] letterboxed
     tensors whose pixels the files hold with output_size="letterbox"; paths: (enhanced,
@@ -296,7 +313,7 @@ def save_original_size(src_u8, img_low, img_enhanced, illu_map, paths, max_size=
     enhanced], 3: [input | enhanced | illumination]).  upr.guided.restore on those pixels;
     denoise="nlm" denoises the letterboxed enhanced pixels first (the restore's target)."""
     from upr import guided, runtime
-    dn = _check_denoise(denoise, denoise_strength, denoise_floor, denoise_search, denoise_patch)
+    dn = _check_denoise(denoise, denoise_strength, denoise_floor, denoise_search, denoise_patch, denoise_auto_scale)
     H, W = src_u8.shape[:2]
     content = letterbox_content((H, W), max_size if max_size is not None else (H, W), auto=True, scaleup=False)
     dev = img_enhanced.device
@@ -305,10 +322,10 @@ def save_original_size(src_u8, img_low, img_enhanced, illu_map, paths, max_size=
         return runtime.to_u8_hwc(t.detach().squeeze(0).to(dev)).unsqueeze(0)
 
     src = torch.from_numpy(np.ascontiguousarray(src_u8)).to(dev).unsqueeze(0)
-    target, illu_u8 = u8(img_enhanced), u8(illu_map)
+    low_u8, target, illu_u8 = u8(img_low), u8(img_enhanced), u8(illu_map)
     if dn.on:
-        target = dn.apply(target, illu_u8, content)
-    outs = guided.restore(src, u8(img_low), target, illu_u8, content, guided_radius, guided_eps, comparison)
+        target = dn.apply(target, illu_u8, content, low_u8)
+    outs = guided.restore(src, low_u8, target, illu_u8, content, guided_radius, guided_eps, comparison)
     colour = _Jpeg(jpeg_quality, jpeg_subsampling, jpeg_optimize)
     modes = (colour, colour._replace(gray=bool(jpeg_gray_maps)), colour)
     for arr, path, msg, jpeg in zip(outs, paths, ("已保存", "已保存", "已保存对比图像"), modes):
@@ -323,17 +340,17 @@ def save_original_size(src_u8, img_low, img_enhanced, illu_map, paths, max_size=
 def save_denoised(img_low, img_enhanced, illu_map, paths, content, comparison=2, writer=None, png_encoder="host",
                   image_format="png", jpeg_quality=95, jpeg_subsampling="444", jpeg_optimize=False,
                   jpeg_gray_maps=False, denoise="nlm", denoise_strength=1.0, denoise_floor=16, denoise_search=5,
-                  denoise_patch=2):
+                  denoise_patch=2, denoise_auto_scale=1.0):
     """The three letterboxed files of one image with denoise="nlm": the pixels save_image and
     create_comparison write, the enhanced ones denoised inside the content rectangle `content`
     (utils.letterbox.letterbox_content) with the illumination file's pixels as the strength map.
     paths and comparison as in save_original_size."""
     from upr import runtime
-    dn = _check_denoise(denoise, denoise_strength, denoise_floor, denoise_search, denoise_patch)
+    dn = _check_denoise(denoise, denoise_strength, denoise_floor, denoise_search, denoise_patch, denoise_auto_scale)
     dev = img_enhanced.device
     low, enh, illu = (runtime.to_u8_hwc(t.detach().squeeze(0).to(dev)) for t in (img_low, img_enhanced, illu_map))
     if dn.on:
-        enh = dn.apply(enh.unsqueeze(0), illu.unsqueeze(0), content)[0]
+        enh = dn.apply(enh.unsqueeze(0), illu.unsqueeze(0), content, low.unsqueeze(0))[0]
     cmp = torch.cat([low, enh] + ([illu] if comparison == 3 else []), dim=1) if comparison else None
     colour = _Jpeg(jpeg_quality, jpeg_subsampling, jpeg_optimize)
     modes = (colour, colour._replace(gray=bool(jpeg_gray_maps)), colour)
@@ -351,7 +368,7 @@ def enhance_single_image(model, image_path, output_dir, device, max_size=None, e
                          png_encoder="host", image_format="png", jpeg_quality=95, output_size="letterbox",
                          guided_radius=4, guided_eps=1e-4, jpeg_subsampling="444", jpeg_optimize=False,
                          jpeg_gray_maps=False, denoise="off", denoise_strength=1.0, denoise_floor=16, denoise_search=5,
-                         denoise_patch=2):
+                         denoise_patch=2, denoise_auto_scale=1.0):
     """Enhance one file and write {name}_enhanced/_illumination/_comparison.png (reference :135-199;
     .jpg with image_format="jpg", quality jpeg_quality; jpeg_subsampling and jpeg_optimize apply to
     all three files, jpeg_gray_maps makes _illumination.jpg a one-component file).
@@ -360,13 +377,14 @@ def enhance_single_image(model, image_path, output_dir, device, max_size=None, e
     "device_lz" does so with LZ77 matching (same pixels, smaller files than "device").
     output_size="original" writes the three files at the source's size (save_original_size);
     the returned tensors stay the letterboxed ones.  denoise="nlm" writes the enhanced pixels
-    denoised (upr.denoise.nlm, after CLAHE, whichever enhancer ran); the returned tensors are not."""
+    denoised (upr.denoise.nlm, after CLAHE, whichever enhancer ran); the returned tensors are not.
+    denoise_strength="auto": the strength is denoise_auto_scale times the input's measured noise level."""
     _check_encoder(png_encoder)
     _check_format(image_format, jpeg_quality, jpeg_subsampling, jpeg_optimize, jpeg_gray_maps)
     _check_output_size(output_size, guided_radius, guided_eps)
-    dn = _check_denoise(denoise, denoise_strength, denoise_floor, denoise_search, denoise_patch)
-    noise = dict(denoise=dn.mode, denoise_strength=dn.strength, denoise_floor=dn.floor, denoise_search=dn.search,
-                 denoise_patch=dn.patch)
+    dn = _check_denoise(denoise, denoise_strength, denoise_floor, denoise_search, denoise_patch, denoise_auto_scale)
+    noise = dict(denoise=dn.mode, denoise_strength=dn.public_strength, denoise_floor=dn.floor,
+                 denoise_search=dn.search, denoise_patch=dn.patch, denoise_auto_scale=dn.auto_scale)
     print(f"正在处理: {os.path.basename(image_path)}")
     if _decoded is None and (output_size == "original" or dn.on):
         _decoded = _decode(image_path)
@@ -600,7 +618,7 @@ def run_batched(model, image_files, output_dir, device, *, max_size=None, precis
                 batch_size=8, decode_threads=4, clahe=True, comparison=2, image_lines=True, timings=None,
                 image_format="png", jpeg_quality=95, output_size="letterbox", guided_radius=4, guided_eps=1e-4,
                 jpeg_subsampling="444", jpeg_optimize=False, jpeg_gray_maps=False, denoise="off", denoise_strength=1.0,
-                denoise_floor=16, denoise_search=5, denoise_patch=2):
+                denoise_floor=16, denoise_search=5, denoise_patch=2, denoise_auto_scale=1.0):
     """The batched directory pipeline behind enhance_batch_images(batch_size > 1) and
     main.py --mode predict --infer_batch: for every file {name}_enhanced.png,
     {name}_illumination.png and, unless comparison is None, {name}_comparison.png
@@ -635,12 +653,15 @@ def run_batched(model, image_files, output_dir, device, *, max_size=None, precis
     denoise="nlm": behind upr_panels_u8 one upr.denoise.nlm launch per batch filters the enhanced
     pixels inside the content rectangle (batches are then keyed by that rectangle as well); the
     comparison's enhanced panel is replaced by torch.cat, and with output_size="original" the
-    denoised pixels are the restore's target."""
+    denoised pixels are the restore's target.  denoise_strength="auto": three launches per batch
+    instead, on the batch's stream -- upr.denoise.estimate_sigma on the input's u8 pixels (the
+    comparison's left panel; without a comparison one more upr_panels_u8 makes them), the
+    per-image tables, the filter reading them; the estimates never come to the host."""
     from upr import guided, runtime
     _check_encoder(png_encoder)
     _check_format(image_format, jpeg_quality, jpeg_subsampling, jpeg_optimize, jpeg_gray_maps)
     _check_output_size(output_size, guided_radius, guided_eps)
-    dn = _check_denoise(denoise, denoise_strength, denoise_floor, denoise_search, denoise_patch)
+    dn = _check_denoise(denoise, denoise_strength, denoise_floor, denoise_search, denoise_patch, denoise_auto_scale)
     original = output_size == "original"
     if comparison not in (None, 2, 3):
         raise ValueError(f"comparison must be None, 2 or 3, got {comparison!r}")
@@ -672,16 +693,18 @@ def run_batched(model, image_files, output_dir, device, *, max_size=None, precis
         content = letterbox_content(images[0].shape[:2], new_shape, auto=True, scaleup=False)
         if original:
             enh_u8, illu_u8, _ = runtime.panels_u8(x, enh, illu, None)
+            low_u8 = runtime.panels_u8(x, x, None, None)[0]
             if dn.on:
-                enh_u8 = dn.apply(enh_u8, illu_u8, content)
-            u8s = guided.restore(sources, runtime.panels_u8(x, x, None, None)[0], enh_u8, illu_u8, content,
-                                 guided_radius, guided_eps, comparison)
+                enh_u8 = dn.apply(enh_u8, illu_u8, content, low_u8)
+            u8s = guided.restore(sources, low_u8, enh_u8, illu_u8, content, guided_radius, guided_eps, comparison)
         else:
             u8s = runtime.panels_u8(x, enh, illu, comparison)
             if dn.on:
-                den, cmp = dn.apply(u8s[0], u8s[1], content), u8s[2]
+                cmp, Wl, low_u8 = u8s[2], x.shape[3], None
+                if dn.auto:  # the input's pixels: the comparison's left panel, or a launch of their own
+                    low_u8 = cmp[:, :, :Wl] if cmp is not None else runtime.panels_u8(x, x, None, None)[0]
+                den = dn.apply(u8s[0], u8s[1], content, low_u8)
                 if cmp is not None:  # [input | enhanced (| illumination)]: the middle panel is the denoised one
-                    Wl = den.shape[2]
                     cmp = torch.cat([cmp[:, :, :Wl], den, cmp[:, :, 2 * Wl:]], dim=2)
                 u8s = (den, u8s[1], cmp)
         outputs = []
@@ -749,7 +772,8 @@ def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preac
                          precision="fp32", png_encoder="host", batch_size=1, decode_threads=4, timings=None,
                          image_format="png", jpeg_quality=95, output_size="letterbox", guided_radius=4,
                          guided_eps=1e-4, jpeg_subsampling="444", jpeg_optimize=False, jpeg_gray_maps=False,
-                         denoise="off", denoise_strength=1.0, denoise_floor=16, denoise_search=5, denoise_patch=2):
+                         denoise="off", denoise_strength=1.0, denoise_floor=16, denoise_search=5, denoise_patch=2,
+                         denoise_auto_scale=1.0):
     """Enhance every image of a directory (reference :202-250).
 
     batch_size=1 (the default) is the reference's one-image-at-a-time loop with a decode
@@ -764,15 +788,16 @@ def enhance_batch_images(input_dir, output_dir, device, max_size=None, use_preac
     jpeg_gray_maps as in enhance_single_image).  output_size="original" writes them
     at each source's size (run_batched / save_original_size; guided_radius, guided_eps).
     denoise="nlm" writes the enhanced pixels denoised (denoise_strength, denoise_floor,
-    denoise_search, denoise_patch as in enhance_single_image)."""
+    denoise_search, denoise_patch, denoise_auto_scale as in enhance_single_image; with
+    denoise_strength="auto" every image of a batch is filtered at its own measured noise level)."""
     _check_encoder(png_encoder)
     _check_format(image_format, jpeg_quality, jpeg_subsampling, jpeg_optimize, jpeg_gray_maps)
     _check_output_size(output_size, guided_radius, guided_eps)
-    dn = _check_denoise(denoise, denoise_strength, denoise_floor, denoise_search, denoise_patch)
+    dn = _check_denoise(denoise, denoise_strength, denoise_floor, denoise_search, denoise_patch, denoise_auto_scale)
     restore = dict(output_size=output_size, guided_radius=guided_radius, guided_eps=guided_eps,
                    jpeg_subsampling=jpeg_subsampling, jpeg_optimize=jpeg_optimize, jpeg_gray_maps=jpeg_gray_maps,
-                   denoise=dn.mode, denoise_strength=dn.strength, denoise_floor=dn.floor, denoise_search=dn.search,
-                   denoise_patch=dn.patch)
+                   denoise=dn.mode, denoise_strength=dn.public_strength, denoise_floor=dn.floor,
+                   denoise_search=dn.search, denoise_patch=dn.patch, denoise_auto_scale=dn.auto_scale)
     batch_size = int(batch_size)
     if batch_size < 1:
         raise ValueError(f"batch_size must be >= 1, got {batch_size}")

@@ -24,6 +24,8 @@ the guided-filter restore (upr.guided), the bars cropped away.
 --denoise_floor / --denoise_search / --denoise_patch: nlm writes the enhance /
 predict files with the enhanced pixels denoised by the illumination-weighted
 non-local means of upr.denoise (the illumination file does not change).
+--denoise_strength auto measures each image's noise level on the device and
+filters with --denoise_auto_scale times it.
 --infer_batch N (an addition, default 1) runs --mode enhance / predict on a
 directory N images at a time (enhancers/simple_enhance.py run_batched).
 --mode train runs trainers.train.train(args): images of --train_dir are decoded
@@ -85,6 +87,16 @@ def _int_at_least(lo):
 
 
 _positive, _non_negative = _int_at_least(1), _int_at_least(0)
+
+
+def _strength(text):
+    """--denoise_strength: a number, or `auto`."""
+    if text == 'auto':
+        return text
+    try:
+        return float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"must be a number or 'auto', got {text!r}")
 
 
 def build_parser():
@@ -151,8 +163,12 @@ def build_parser():
     p.add_argument('--denoise', choices=['off', 'nlm'], default='off',
                    help='--mode enhance / predict: nlm denoises the enhanced image\'s u8 pixels before they are '
                         'written (non-local means, stronger where the illumination map is darker)')
-    p.add_argument('--denoise_strength', type=float, default=1.0,
-                   help='--denoise nlm: assumed noise std of the input in u8 levels, >= 0')
+    p.add_argument('--denoise_strength', type=_strength, default=1.0,
+                   help='--denoise nlm: assumed noise std of the input in u8 levels, >= 0, or `auto`: measured per '
+                        'image on the device (upr.denoise.estimate_sigma)')
+    p.add_argument('--denoise_auto_scale', type=float, default=1.0,
+                   help='--denoise_strength auto: multiplies the estimate, >= 0 (a Laplacian estimator reads low on '
+                        'noise that demosaicing or JPEG has correlated)')
     p.add_argument('--denoise_floor', type=int, default=16,
                    help='--denoise nlm: the illumination level below which the strength stops growing, 1..255')
     p.add_argument('--denoise_search', type=int, default=5, help='--denoise nlm: search radius, 1..10')
@@ -166,6 +182,9 @@ def build_parser():
     p.add_argument('--lowlight_dir', type=str, default=None,
                    help='--mode evaluate: the low-light sources, matched by file stem (adds the lightness order '
                         'error column `loe`)')
+    p.add_argument('--noise_sigma', action='store_true',
+                   help='--mode evaluate: adds a last column `noise_sigma`, the blind noise estimate of each image in '
+                        'u8 levels (utils.utils.batch_noise_sigma)')
     p.add_argument('--loe_size', type=_non_negative, default=50,
                    help='--lowlight_dir / --val_dir: LOE sample grid, pixels on the shorter side (0: every pixel)')
     p.add_argument('--val_dir', type=str, default=None,
@@ -212,7 +231,8 @@ def parse_args(argv=None):
         parser.error("--val_reference_dir needs --val_dir")
     try:
         from upr import denoise
-        denoise.check_params(args.denoise_strength, args.denoise_floor, args.denoise_search, args.denoise_patch)
+        denoise.check_params(args.denoise_strength, args.denoise_floor, args.denoise_search, args.denoise_patch,
+                             args.denoise_auto_scale)
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -238,7 +258,8 @@ def _output_format(args):
 
 def _denoise(args):
     return dict(denoise=args.denoise, denoise_strength=args.denoise_strength, denoise_floor=args.denoise_floor,
-                denoise_search=args.denoise_search, denoise_patch=args.denoise_patch)
+                denoise_search=args.denoise_search, denoise_patch=args.denoise_patch,
+                denoise_auto_scale=args.denoise_auto_scale)
 
 
 def _restore(args):
@@ -310,8 +331,9 @@ def evaluate(args):
     Consecutive images of one size share a launch, up to --batch_size.
     With --lowlight_dir a last column `loe` (utils.utils.batch_loe, --loe_size)
     measures each image against its low-light source, matched by stem like the
-    ground truth."""
-    from utils.utils import batch_loe, batch_metrics, metric_names
+    ground truth.  With --noise_sigma a last column `noise_sigma` (after `loe`):
+    utils.utils.batch_noise_sigma of each image."""
+    from utils.utils import batch_loe, batch_metrics, batch_noise_sigma, metric_names
     p = Path(args.input_path)
     files = [str(p)] if p.is_file() else (list_images(str(p)) if p.is_dir() else None)
     if not files:
@@ -319,7 +341,8 @@ def evaluate(args):
         return None
     paired = args.reference_dir is not None
     lowlight = getattr(args, 'lowlight_dir', None)
-    names = metric_names(paired) + (('loe',) if lowlight else ())
+    noise = bool(getattr(args, 'noise_sigma', False))
+    names = metric_names(paired) + (('loe',) if lowlight else ()) + (('noise_sigma',) if noise else ())
     by_stem = _reference_stems(args.reference_dir) if paired else None
     low_by_stem = _reference_stems(lowlight) if lowlight else None
     cols = []  # per launch: [n_metrics, b] device tensors
@@ -330,6 +353,8 @@ def evaluate(args):
             m = batch_metrics(x, torch.cat(ys) if paired else None)
             if lowlight:
                 m['loe'] = batch_loe(torch.cat(ls), x, args.loe_size)
+            if noise:
+                m['noise_sigma'] = batch_noise_sigma(x)
             cols.append(torch.stack([m[n] for n in names]))
 
     xs, ys, ls = [], [], []

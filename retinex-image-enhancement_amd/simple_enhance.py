@@ -6,7 +6,8 @@ have the source's size, upr.guided), and --image_format {png,jpg} with --jpeg_qu
 --jpeg_subsampling {444,420}, --jpeg_optimize and --jpeg_gray_maps (jpg: the three files as
 JPEGs, as main.py's flags of the same names), and --denoise {off,nlm} with --denoise_strength /
 --denoise_floor / --denoise_search / --denoise_patch (nlm: the enhanced pixels are denoised
-before they are written, upr.denoise)."""
+before they are written, upr.denoise; --denoise_strength auto measures each image's noise
+level on the device and filters with --denoise_auto_scale times it)."""
 import argparse
 import os
 import sys
@@ -20,6 +21,15 @@ if _HERE not in sys.path:
 
 from enhancers.simple_enhance import enhance_single_image, enhance_batch_images  # noqa: E402
 from models.model import UP_Retinex  # noqa: E402
+
+
+def _strength(text):
+    if text == 'auto':
+        return text
+    try:
+        return float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"must be a number or 'auto', got {text!r}")
 
 
 def build_parser():
@@ -46,8 +56,11 @@ def build_parser():
     ap.add_argument('--denoise', choices=['off', 'nlm'], default='off',
                     help='nlm: denoise the enhanced image\'s u8 pixels before they are written (non-local means, '
                          'stronger where the illumination map is darker)')
-    ap.add_argument('--denoise_strength', type=float, default=1.0,
-                    help='--denoise nlm: assumed noise std of the input in u8 levels, >= 0')
+    ap.add_argument('--denoise_strength', type=_strength, default=1.0,
+                    help='--denoise nlm: assumed noise std of the input in u8 levels, >= 0, or `auto`: measured per '
+                         'image on the device')
+    ap.add_argument('--denoise_auto_scale', type=float, default=1.0,
+                    help='--denoise_strength auto: multiplies the estimate, >= 0')
     ap.add_argument('--denoise_floor', type=int, default=16,
                     help='--denoise nlm: the illumination level below which the strength stops growing, 1..255')
     ap.add_argument('--denoise_search', type=int, default=5, help='--denoise nlm: search radius, 1..10')
@@ -60,6 +73,7 @@ def main(argv=None):
     restore = dict(output_size=args.output_size, guided_radius=args.guided_radius, guided_eps=args.guided_eps,
                    denoise=args.denoise, denoise_strength=args.denoise_strength, denoise_floor=args.denoise_floor,
                    denoise_search=args.denoise_search, denoise_patch=args.denoise_patch,
+                   denoise_auto_scale=args.denoise_auto_scale,
                    image_format=args.image_format, jpeg_quality=args.jpeg_quality,
                    jpeg_subsampling=args.jpeg_subsampling, jpeg_optimize=args.jpeg_optimize,
                    jpeg_gray_maps=args.jpeg_gray_maps)

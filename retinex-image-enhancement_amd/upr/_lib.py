@@ -153,6 +153,12 @@ SIGNATURES = {
     "upr_denoise_lut": (c_int, [ctypes.c_double, c_int, c_int, ctypes.POINTER(ctypes.c_uint32)]),
     "upr_denoise_nlm_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                    c_int, ctypes.POINTER(ctypes.c_uint32), c_void_p, c_void_p]),
+    "upr_noise_sigma_workspace": (c_size_t, [c_int]),
+    "upr_noise_sigma_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                   c_size_t, c_void_p]),
+    "upr_denoise_lut_dev": (c_int, [c_void_p, c_int, ctypes.c_double, c_int, c_int, c_void_p, c_void_p]),
+    "upr_denoise_nlm_u8_luts": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "upr_lab_tables": (None, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "upr_retinex_decompose": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_void_p]),

@@ -8,7 +8,9 @@ or numpy arrays in the reference's [H,W,C] layout (uploaded to the current
 device); CPU tensors are refused like everywhere else in this package.
 batch_metrics is the batched, non-synchronising form the reference lacks.
 batch_loe / calculate_loe (an addition) give the lightness order error of an
-enhanced image against its own low-light input (upr.runtime.image_loe).
+enhanced image against its own low-light input (upr.runtime.image_loe);
+batch_noise_sigma / calculate_noise_sigma (an addition) the blind noise level
+of an image in u8 levels (upr.denoise.estimate_sigma on its to_u8_hwc pixels).
 
 Divergences: the simplified NIQE clamps a window's variance at 0 (the
 reference's float32 expression yields NaN on flat windows), and a batch is
@@ -136,6 +138,23 @@ def calculate_loe(img_low, img_enhanced, size=50):
     v = batch_loe(img_low, img_enhanced, size)
     if v.shape[0] != 1:
         raise RuntimeError(f"expected one image, got a batch of {v.shape[0]} (use batch_loe)")
+    return float(v.cpu()[0])
+
+
+def batch_noise_sigma(img):
+    """The blind noise estimate of every image of img [B,3,H,W] in u8 levels (the median
+    Laplacian-difference estimator of upr.denoise.estimate_sigma, on the pixels to_u8_hwc
+    gives a float image): float64 device tensor [B].  No synchronisation, no host copy."""
+    from upr import denoise
+    x = _as_batch(img, "img")
+    return denoise.estimate_sigma(runtime.panels_u8(x, x, None, None)[0])
+
+
+def calculate_noise_sigma(img):
+    """batch_noise_sigma of one image as a Python float (inputs as calculate_metrics takes them)."""
+    v = batch_noise_sigma(img)
+    if v.shape[0] != 1:
+        raise RuntimeError(f"expected one image, got a batch of {v.shape[0]} (use batch_noise_sigma)")
     return float(v.cpu()[0])
 
 

@@ -53,7 +53,7 @@ def write_inputs(src, n, size, mixed=False):
 
 def run(src, out, n, size, precision="fp32", png_encoder="host", batch_size=1, decode_threads=4, mixed=False,
         warm=True, image_format="png", jpeg_quality=95, max_size=None, output_size="letterbox",
-        jpeg_subsampling="444", jpeg_optimize=False, jpeg_gray_maps=False, denoise="off"):
+        jpeg_subsampling="444", jpeg_optimize=False, jpeg_gray_maps=False, denoise="off", denoise_strength=None):
     """One timed enhance_batch_images over the files of `src` -> the result dict."""
     from enhancers.simple_enhance import enhance_batch_images
     kw = {"png_encoder": png_encoder} if png_encoder != "host" else {}
@@ -67,6 +67,8 @@ def run(src, out, n, size, precision="fp32", png_encoder="host", batch_size=1, d
         kw["output_size"] = output_size
     if denoise != "off":
         kw["denoise"] = denoise
+        if denoise_strength is not None:  # a number or "auto" (tools/noise_bench.py)
+            kw["denoise_strength"] = denoise_strength
     timings = None
     if batch_size != 1:
         timings = {}
@@ -86,7 +88,7 @@ def run(src, out, n, size, precision="fp32", png_encoder="host", batch_size=1, d
            "n": n, "size": size, "precision": precision, "png_encoder": png_encoder,
            "batch_size": batch_size, "mixed": bool(mixed), "seconds": el, "files_written": len(os.listdir(out)),
            "image_format": image_format, "max_size": max_size, "output_size": output_size,
-           "denoise": denoise,
+           "denoise": denoise, "denoise_strength": denoise_strength,
            "output_bytes": sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out))}
     if image_format == "jpg":
         res["jpeg_quality"] = jpeg_quality
